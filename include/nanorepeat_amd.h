@@ -340,6 +340,48 @@ int  nra_batch2d_fetch(nra_batch_t* b, int8_t* read_strand,
                        int32_t* n_ties, uint8_t* status);
 void nra_batch_destroy(nra_batch_t* b);
 
+/* ---- anchor screen: which regions' anchors a read carries (FASTQ / FASTA input) ------------
+ *      replaces the genome-wide mapping of preprocess_fastq (nanoRepeat.py:41-76) and the BAM
+ *      window fetch of extract_fastq_from_bam (nanoRepeat_bam.py:577-600) as the choice of the
+ *      reads each region sees; the anchor check (find_anchor_locations_in_reads) still decides.
+ *
+ * A k-window counts when all its bases are ACGT (either case); canon(w) = min(code(w), code(revcomp(w))),
+ * 2 bits per base (A=0 C=1 G=2 T=3), first base most significant.  K(g, s) = the distinct canonical k-mers of
+ * side s (0 left, 1 right) of region g, without periodic k-mers (w[i] == w[i+p] for all i, some p in 1..6) and
+ * without k-mers found in more than max_occ of the 2 * n_regions sets.  c(r, g, s) = the window positions of read
+ * r whose canonical k-mer is in K(g, s).  Pair (r, g) passes when c(r,g,s) >= min(min_hits, |K(g,s)|) on both
+ * sides: a region whose two sets are empty takes every read.  DESIGN.md section 13. */
+typedef struct nra_screen nra_screen_t;
+
+typedef struct nra_screen_stats {
+    int64_t n_keys;            /* distinct canonical k-mers in the index */
+    int64_t n_postings;        /* (k-mer, region side) entries of the index */
+    int64_t n_masked_periodic; /* distinct periodic k-mers of the anchors, left out */
+    int64_t n_masked_max_occ;  /* distinct k-mers in more than max_occ sets, left out */
+    int64_t n_empty_regions;   /* regions both of whose sets are empty: every read passes them */
+    int64_t index_bytes;       /* device bytes of the table and the postings */
+    int64_t bases_screened;    /* read bases over every nra_screen_reads call */
+    int64_t n_calls;           /* nra_screen_reads calls that succeeded */
+    double  build_ms;          /* host time of the index build in nra_screen_create */
+    double  kernel_ms;         /* screen kernels of the last call (HIP events) */
+    double  sum_kernel_ms;     /* ... summed over n_calls */
+} nra_screen_stats_t;
+
+/* anchors 2g / 2g+1 = left / right anchor of region g: bytes [anchor_off[i], anchor_off[i+1]) of `anchors`
+ * (2 * n_regions + 1 offsets).  k odd in 11..15, max_occ in 1..255.  Builds the index on the host, keeps it on
+ * the device; the handle serves any number of nra_screen_reads calls (one at a time). */
+int nra_screen_create(int device, int32_t n_regions, const char* anchors, const int64_t* anchor_off,
+                      int32_t k, int32_t max_occ, nra_screen_t** out);
+/* n_reads reads, bytes [seq_off[i], seq_off[i+1]) of `seqs`; min_hits >= 1.  Writes the passing pairs sorted by
+ * read, then region, with c(r, g, left) and c(r, g, right).  *n_pairs is the capacity of the four arrays on entry
+ * and the number of pairs on return; when the pairs exceed the capacity the call writes none, leaves the number
+ * needed in *n_pairs and returns NRA_E_RANGE. */
+int nra_screen_reads(nra_screen_t* s, int32_t n_reads, const char* seqs, const int64_t* seq_off, int32_t min_hits,
+                     int64_t* n_pairs, int32_t* pair_read, int32_t* pair_region,
+                     int32_t* hits_left, int32_t* hits_right);
+int nra_screen_stats(const nra_screen_t* s, nra_screen_stats_t* st);
+int nra_screen_destroy(nra_screen_t* s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,9 +31,11 @@ F_SERIAL_CHAIN = 128  # testing / comparison, 1D: a long read's row blocks one a
 EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count",
            "nra_default_scoring", "nra_release_cached_memory", "nra_round3_1d", "nra_joint_2d", "nra_align_pairs", "nra_align_pairs_cigar", "nra_batch1d_create",
            "nra_batch2d_create", "nra_batch2d_create_reads", "nra_batch2d_set_cells", "nra_joint_grid_cells", "nra_batch2d_set_grid", "nra_batch2d_invalidate", "nra_batch2d_sweep_flanks", "nra_batch2d_refine", "nra_batch_run", "nra_batch_sync", "nra_batch_stats",
-           "nra_batch1d_fetch", "nra_batch2d_fetch", "nra_batch_destroy")
+           "nra_batch1d_fetch", "nra_batch2d_fetch", "nra_batch_destroy",
+           "nra_screen_create", "nra_screen_reads", "nra_screen_stats", "nra_screen_destroy")
 
 
+E_RANGE = -3      # NRA_E_RANGE
 E_STATE = -5      # NRA_E_STATE
 
 
@@ -71,6 +73,15 @@ class Stats(C.Structure):
                 ("sum_score_kernel_ms", C.c_double), ("sum_extent_kernel_ms", C.c_double),
                 ("sum_total_ms", C.c_double), ("sum_score_phase_ms", C.c_double),
                 ("intermediate_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class ScreenStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_keys", "n_postings", "n_masked_periodic", "n_masked_max_occ",
+                                         "n_empty_regions", "index_bytes", "bases_screened", "n_calls")] + \
+               [(n, C.c_double) for n in ("build_ms", "kernel_ms", "sum_kernel_ms")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -147,6 +158,14 @@ def load():
     lib.nra_batch2d_fetch.argtypes = [vp, pi8, pi32, pi32, pi32, pi64, pi64, pi32, p8]
     lib.nra_batch_destroy.restype = None
     lib.nra_batch_destroy.argtypes = [vp]
+    lib.nra_screen_create.restype = C.c_int
+    lib.nra_screen_create.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, C.c_int32, C.c_int32, C.POINTER(vp)]
+    lib.nra_screen_reads.restype = C.c_int
+    lib.nra_screen_reads.argtypes = [vp, C.c_int32, C.c_char_p, pi64, C.c_int32, pi64, pi32, pi32, pi32, pi32]
+    lib.nra_screen_stats.restype = C.c_int
+    lib.nra_screen_stats.argtypes = [vp, C.POINTER(ScreenStats)]
+    lib.nra_screen_destroy.restype = C.c_int
+    lib.nra_screen_destroy.argtypes = [vp]
     _LIB = lib
     return lib
 
@@ -545,3 +564,43 @@ class Batch:
             self.close()
         except Exception:
             pass
+
+
+def screen_create(anchors, k=15, max_occ=16, device=0):
+    """nra_screen_create.  anchors = [(left, right)] per region -> an opaque handle (screen_destroy frees it)."""
+    data, off = pack_reads([a for pair in anchors for a in pair])
+    h = C.c_void_p()
+    _check(load().nra_screen_create(device, len(anchors), data, _ptr(off, C.c_int64), k, max_occ, C.byref(h)))
+    return h
+
+
+def screen_stats(handle):
+    st = ScreenStats()
+    _check(load().nra_screen_stats(handle, C.byref(st)))
+    return st.as_dict()
+
+
+def screen_reads(handle, reads, min_hits=4, capacity=None):
+    """nra_screen_reads -> dict(read, region, hits_left, hits_right) of the passing pairs, sorted by read then
+    region.  When the pairs exceed `capacity` (default: a few per read), the call is repeated once with the
+    capacity the library asked for."""
+    lib = load()
+    seqs, off = pack_reads(reads)
+    n = len(reads)
+    if capacity is None:
+        capacity = n * (4 + screen_stats(handle)["n_empty_regions"]) + 1024
+    while True:
+        out = {key: np.zeros(capacity, np.int32) for key in ("read", "region", "hits_left", "hits_right")}
+        n_pairs = C.c_int64(capacity)
+        rc = lib.nra_screen_reads(handle, n, seqs, _ptr(off, C.c_int64), min_hits, C.byref(n_pairs),
+                                  *(_ptr(out[key], C.c_int32) for key in ("read", "region", "hits_left", "hits_right")))
+        if rc == E_RANGE and n_pairs.value > capacity:
+            capacity = int(n_pairs.value)
+            continue
+        _check(rc)
+        return {key: v[:n_pairs.value] for key, v in out.items()}
+
+
+def screen_destroy(handle):
+    if handle:
+        _check(load().nra_screen_destroy(handle))

@@ -14,7 +14,8 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libnanorepeat_amd.so")
 OBJ = os.path.join(HERE, "csrc", "build")
 
-SOURCES = ["nra_kernels.hip", "nra_sweep.hip", "nra_joint.hip", "nra_trace.hip", "nra_host.cpp", "nra_internal.h", "nra_device.h", "nra_pk16.h"]
+SOURCES = ["nra_kernels.hip", "nra_sweep.hip", "nra_joint.hip", "nra_trace.hip", "nra_screen.hip", "nra_host.cpp",
+           "nra_screen_host.cpp", "nra_internal.h", "nra_device.h", "nra_pk16.h"]
 ARCH = "gfx950"
 
 
@@ -58,9 +59,13 @@ def build_library(force=False, jobs=None, verbose=False):
     o = os.path.join(OBJ, "nra_trace_p9.o")
     objs.append(o)
     cmds.append(common + ["-DNRA_PART=9", "-c", os.path.join(CSRC, "nra_trace.hip"), "-o", o])
-    o = os.path.join(OBJ, "nra_host.o")
+    o = os.path.join(OBJ, "nra_screen_p27.o")
     objs.append(o)
-    cmds.append(common + ["-pthread", "-c", os.path.join(CSRC, "nra_host.cpp"), "-o", o])
+    cmds.append(common + ["-DNRA_PART=27", "-c", os.path.join(CSRC, "nra_screen.hip"), "-o", o])
+    for host in ("nra_host", "nra_screen_host"):
+        o = os.path.join(OBJ, host + ".o")
+        objs.append(o)
+        cmds.append(common + ["-pthread", "-c", os.path.join(CSRC, host + ".cpp"), "-o", o])
 
     # an object is rebuilt when its source, a header next to it or the public header is newer
     headers = [os.path.join(CSRC, h) for h in SOURCES if h.endswith(".h")] + [os.path.join(INCLUDE, "nanorepeat_amd.h")]

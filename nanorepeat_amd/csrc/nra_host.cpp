@@ -943,6 +943,8 @@ int make_events(nra_batch* b, int n)
 // =====================================================================================
 extern "C" {
 
+int nra_set_error(int code, const char* msg) { return fail(code, msg ? msg : ""); }
+
 int nra_abi_version(void) { return NRA_ABI_VERSION; }
 const char* nra_version(void) { return NRA_VERSION_STR; }
 const char* nra_last_error(void) { return g_err.c_str(); }

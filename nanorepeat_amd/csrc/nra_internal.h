@@ -177,9 +177,43 @@ struct NraScoreParams {
 #define NRA_WIDE_R_SMALL 16
 #define NRA_WIDE_R_LARGE 48
 
+// Anchor k-mer screen (nra_screen.hip, nra_screen_host.cpp).  The index is an open-addressing table of 8-byte slots: the
+// canonical k-mer in bits 0..29, its number of postings in bits 30..37 and the first of them in bits 38..63; a posting
+// is region * 2 + side.  An empty slot is all ones (no canonical k-mer has all 30 key bits set: its reverse complement
+// would be smaller).
+#define NRA_SCREEN_TILE 4096                  // window positions per workgroup
+#define NRA_SCREEN_THREADS 256
+#define NRA_SCREEN_MAP 128                    // (region, side) counters per workgroup in LDS; more overflow to global entries
+#define NRA_SCREEN_EMPTY (~0ull)
+#define NRA_SCREEN_KEY_BITS 30
+#define NRA_SCREEN_CNT_BITS 8
+#define NRA_SCREEN_START_BITS 26
+#define NRA_SCREEN_HASH_MUL 0x9E3779B97F4A7C15ull
+
+// one tile: n_win window positions of one read, the first at byte `base` of the chunk's device copy
+struct NraScreenTile {
+    int64_t base;
+    int32_t read;
+    int32_t n_win;
+};
+
+// hits of one tile on one (region, side) set; a (read, set) pair may have several entries (tiles, overflow)
+struct NraScreenEntry {
+    int32_t read, set, count;
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+
+// the error message nra_last_error() returns; returns `code` (nra_host.cpp)
+int nra_set_error(int code, const char* msg);
+
+// anchor screen (nra_screen.hip): one workgroup per tile.  Entries go to entries[0, cap); *count ends as the number of
+// entries wanted, which may exceed cap (the host then grows the list and runs again)
+int nra_launch_screen_hits(hipStream_t st, int64_t n_tiles, const NraScreenTile* tiles, const uint8_t* seqs, int k,
+                           const uint64_t* table, int log2_slots, const uint32_t* postings, NraScreenEntry* entries,
+                           unsigned long long cap, unsigned long long* count);
 
 // launchers (nra_kernels.hip).  All asynchronous on `st`; return hipError_t as int.
 int nra_launch_score_pk16(int R, int has_n, hipStream_t st, int n_tasks,

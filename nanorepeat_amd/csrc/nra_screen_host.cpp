@@ -1,0 +1,354 @@
+// nra_screen_host.cpp -- C ABI of the anchor k-mer screen (nra_screen_*): the index build on the host, the chunked
+// launches of k_screen_hits (nra_screen.hip) and the per-(read, region) reduction with the pass rule.
+#include "nanorepeat_amd.h"
+#include "nra_internal.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+namespace {
+
+int fail(int code, const std::string& msg) { return nra_set_error(code, msg.c_str()); }
+
+#define SCREEN_HIP_TRY(expr)                                                                     \
+    do {                                                                                         \
+        hipError_t e_ = (expr);                                                                  \
+        if (e_ != hipSuccess)                                                                    \
+            return fail(e_ == hipErrorOutOfMemory ? NRA_E_NOMEM : NRA_E_DEVICE,                  \
+                        std::string(#expr) + ": " + hipGetErrorString(e_));                      \
+    } while (0)
+
+const int64_t kSegmentBytes = int64_t(1) << 28;   // read bytes per launch (a longer read goes alone)
+const size_t kPad = 64;                           // bytes after a chunk's copy: the kernel's last 16-byte load stays inside
+
+int base_code(unsigned char ch)
+{
+    switch (ch) {
+    case 'A': case 'a': return 0;
+    case 'C': case 'c': return 1;
+    case 'G': case 'g': return 2;
+    case 'T': case 't': return 3;
+    default: return -1;
+    }
+}
+
+// device buffer that grows and is reused across calls
+template <class T> struct Grow {
+    T* p = nullptr;
+    size_t n = 0;
+    hipError_t reserve(size_t want)
+    {
+        if (want <= n) return hipSuccess;
+        if (p) { (void)hipFree(p); p = nullptr; n = 0; }
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(want, 1) * sizeof(T));
+        if (e == hipSuccess) n = want;
+        return e;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+};
+
+}  // namespace
+
+struct nra_screen {
+    int device = 0;
+    int k = 15;
+    int32_t n_regions = 0;
+    int log2_slots = 0;
+    std::vector<int64_t> set_size;     // |K(g, s)| at 2g + s
+    std::vector<int32_t> empty_regions;
+    nra_screen_stats_t st{};
+    uint64_t* table = nullptr;
+    uint32_t* postings = nullptr;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Grow<uint8_t> seqs;
+    Grow<NraScreenTile> tiles;
+    Grow<NraScreenEntry> entries;
+    Grow<unsigned long long> count;
+
+    ~nra_screen()
+    {
+        seqs.release(); tiles.release(); entries.release(); count.release();
+        if (table) (void)hipFree(table);
+        if (postings) (void)hipFree(postings);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace {
+
+// the canonical k-mers of one anchor's valid windows: non-periodic ones to `keys`, periodic ones to `periodic`
+void anchor_kmers(const char* s, int64_t n, int k, std::vector<uint32_t>& keys, std::vector<uint32_t>& periodic)
+{
+    const uint32_t kmask = (1u << (2 * k)) - 1u;
+    uint32_t fwd = 0, rev = 0;
+    int run = 0;
+    for (int64_t j = 0; j < n; ++j) {
+        const int c = base_code((unsigned char)s[j]);
+        if (c < 0) { run = 0; continue; }
+        fwd = ((fwd << 2) | (uint32_t)c) & kmask;
+        rev = (rev >> 2) | ((uint32_t)(3 - c) << (2 * (k - 1)));
+        if (++run < k) continue;
+        bool per = false;
+        for (int p = 1; p <= 6 && !per; ++p)     // w[i] == w[i + p] for every i: the first k - p bases equal the last k - p
+            per = (fwd >> (2 * p)) == (fwd & ((1u << (2 * (k - p))) - 1u));
+        (per ? periodic : keys).push_back(std::min(fwd, rev));
+    }
+}
+
+int build_index(nra_screen* s, const char* anchors, const int64_t* anchor_off, int max_occ)
+{
+    const int64_t n_sets = 2 * (int64_t)s->n_regions;
+    std::vector<uint64_t> pairs;                   // canonical k-mer << 32 | set, each (k-mer, set) once
+    std::vector<uint32_t> keys, periodic;
+    s->set_size.assign((size_t)n_sets, 0);
+    for (int64_t g = 0; g < n_sets; ++g) {
+        keys.clear();
+        anchor_kmers(anchors + anchor_off[g], anchor_off[g + 1] - anchor_off[g], s->k, keys, periodic);
+        std::sort(keys.begin(), keys.end());
+        keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+        s->set_size[(size_t)g] = (int64_t)keys.size();
+        for (uint32_t key : keys) pairs.push_back((uint64_t)key << 32 | (uint64_t)g);
+    }
+    std::sort(periodic.begin(), periodic.end());
+    s->st.n_masked_periodic = (int64_t)(std::unique(periodic.begin(), periodic.end()) - periodic.begin());
+    std::sort(pairs.begin(), pairs.end());
+
+    // one slot per k-mer in at most max_occ sets; the others leave every set they are in
+    std::vector<uint64_t> slots;                   // key | count << 30 | first << 38, before hashing
+    std::vector<uint32_t> post;
+    for (size_t i = 0; i < pairs.size();) {
+        size_t j = i;
+        const uint32_t key = (uint32_t)(pairs[i] >> 32);
+        while (j < pairs.size() && (uint32_t)(pairs[j] >> 32) == key) ++j;
+        if ((int64_t)(j - i) > max_occ) {
+            for (size_t q = i; q < j; ++q) --s->set_size[(size_t)(uint32_t)pairs[q]];
+            ++s->st.n_masked_max_occ;
+        } else {
+            if (post.size() + (j - i) >= (size_t(1) << NRA_SCREEN_START_BITS))
+                return fail(NRA_E_RANGE, "anchor index: more than 2^26 postings");
+            slots.push_back((uint64_t)key | (uint64_t)(j - i) << NRA_SCREEN_KEY_BITS |
+                            (uint64_t)post.size() << (NRA_SCREEN_KEY_BITS + NRA_SCREEN_CNT_BITS));
+            for (size_t q = i; q < j; ++q) post.push_back((uint32_t)pairs[q]);
+        }
+        i = j;
+    }
+    std::vector<uint64_t>().swap(pairs);
+    for (int32_t g = 0; g < s->n_regions; ++g)
+        if (s->set_size[2 * (size_t)g] == 0 && s->set_size[2 * (size_t)g + 1] == 0) s->empty_regions.push_back(g);
+
+    // open addressing at load factor <= 0.5
+    int log2_slots = 10;
+    while ((size_t(1) << log2_slots) < 2 * slots.size()) ++log2_slots;
+    const size_t n_slots = size_t(1) << log2_slots;
+    std::vector<uint64_t> table(n_slots, NRA_SCREEN_EMPTY);
+    for (uint64_t v : slots) {
+        const uint64_t key = v & ((1ull << NRA_SCREEN_KEY_BITS) - 1);
+        uint64_t h = (key * NRA_SCREEN_HASH_MUL) >> (64 - log2_slots);
+        while (table[h] != NRA_SCREEN_EMPTY) h = (h + 1) & (n_slots - 1);
+        table[h] = v;
+    }
+    s->log2_slots = log2_slots;
+    s->st.n_keys = (int64_t)slots.size();
+    s->st.n_postings = (int64_t)post.size();
+    s->st.n_empty_regions = (int64_t)s->empty_regions.size();
+    s->st.index_bytes = (int64_t)(n_slots * 8 + post.size() * 4);
+
+    SCREEN_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->table), n_slots * 8));
+    SCREEN_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->postings), std::max<size_t>(post.size(), 1) * 4));
+    SCREEN_HIP_TRY(hipMemcpy(s->table, table.data(), n_slots * 8, hipMemcpyHostToDevice));
+    if (!post.empty()) SCREEN_HIP_TRY(hipMemcpy(s->postings, post.data(), post.size() * 4, hipMemcpyHostToDevice));
+    return NRA_OK;
+}
+
+// hits of reads [r0, r1) -> entries appended to `out`
+int screen_segment(nra_screen* s, int32_t r0, int32_t r1, const char* seqs, const int64_t* seq_off,
+                   std::vector<NraScreenEntry>& out, double& kernel_ms)
+{
+    const int64_t b0 = seq_off[r0], bytes = seq_off[r1] - b0;
+    std::vector<NraScreenTile> tiles;
+    for (int32_t r = r0; r < r1; ++r) {
+        const int64_t len = seq_off[r + 1] - seq_off[r];
+        const int64_t n_win = len >= s->k ? len - s->k + 1 : 0;
+        for (int64_t w = 0; w < n_win; w += NRA_SCREEN_TILE)
+            tiles.push_back(NraScreenTile{seq_off[r] - b0 + w, r, (int32_t)std::min<int64_t>(NRA_SCREEN_TILE, n_win - w)});
+    }
+    if (tiles.empty()) return NRA_OK;
+    SCREEN_HIP_TRY(s->seqs.reserve((size_t)bytes + kPad));
+    SCREEN_HIP_TRY(s->tiles.reserve(tiles.size()));
+    SCREEN_HIP_TRY(s->count.reserve(1));
+    SCREEN_HIP_TRY(s->entries.reserve(std::max<size_t>(tiles.size() * 16, size_t(1) << 16)));
+    SCREEN_HIP_TRY(hipMemcpyAsync(s->seqs.p, seqs + b0, (size_t)bytes, hipMemcpyHostToDevice, s->stream));
+    SCREEN_HIP_TRY(hipMemsetAsync(s->seqs.p + bytes, 0, kPad, s->stream));
+    SCREEN_HIP_TRY(hipMemcpyAsync(s->tiles.p, tiles.data(), tiles.size() * sizeof(NraScreenTile), hipMemcpyHostToDevice,
+                                  s->stream));
+    for (;;) {
+        unsigned long long wanted = 0;
+        SCREEN_HIP_TRY(hipMemsetAsync(s->count.p, 0, sizeof(unsigned long long), s->stream));
+        SCREEN_HIP_TRY(hipEventRecord(s->ev0, s->stream));
+        const int e = nra_launch_screen_hits(s->stream, (int64_t)tiles.size(), s->tiles.p, s->seqs.p, s->k, s->table,
+                                             s->log2_slots, s->postings, s->entries.p, s->entries.n, s->count.p);
+        if (e != 0) return fail(NRA_E_DEVICE, std::string("k_screen_hits: ") + hipGetErrorString((hipError_t)e));
+        SCREEN_HIP_TRY(hipEventRecord(s->ev1, s->stream));
+        SCREEN_HIP_TRY(hipMemcpyAsync(&wanted, s->count.p, sizeof(wanted), hipMemcpyDeviceToHost, s->stream));
+        SCREEN_HIP_TRY(hipStreamSynchronize(s->stream));
+        float ms = 0.f;
+        SCREEN_HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+        kernel_ms += ms;
+        if (wanted <= s->entries.n) {
+            const size_t at = out.size();
+            out.resize(at + (size_t)wanted);
+            if (wanted)
+                SCREEN_HIP_TRY(hipMemcpy(out.data() + at, s->entries.p, (size_t)wanted * sizeof(NraScreenEntry),
+                                         hipMemcpyDeviceToHost));
+            return NRA_OK;
+        }
+        // overflowing LDS maps made more entries than the list holds: grow it and run the segment again (how many
+        // overflow depends on the order the lanes arrive in, hence the margin)
+        SCREEN_HIP_TRY(s->entries.reserve((size_t)wanted * 2));
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int nra_screen_create(int device, int32_t n_regions, const char* anchors, const int64_t* anchor_off, int32_t k,
+                      int32_t max_occ, nra_screen_t** out)
+{
+    if (!out) return fail(NRA_E_ARG, "out is NULL");
+    *out = nullptr;
+    if (n_regions <= 0 || n_regions > (1 << 30)) return fail(NRA_E_ARG, "bad region count");
+    if (!anchor_off) return fail(NRA_E_ARG, "anchor_off is NULL");
+    if (k < 11 || k > 15 || k % 2 == 0) return fail(NRA_E_ARG, "k must be odd, 11..15");
+    if (max_occ < 1 || max_occ > 255) return fail(NRA_E_ARG, "max_occ must be in 1..255");
+    if (anchor_off[0] < 0) return fail(NRA_E_ARG, "negative anchor offset");
+    for (int64_t i = 0; i < 2 * (int64_t)n_regions; ++i)
+        if (anchor_off[i + 1] < anchor_off[i]) return fail(NRA_E_ARG, "anchor offsets must not decrease");
+    if (anchor_off[2 * (int64_t)n_regions] > 0 && !anchors) return fail(NRA_E_ARG, "anchors is NULL");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(NRA_E_DEVICE, "no HIP device: nanorepeat_amd has no CPU path");
+    if (device < 0 || device >= ndev) return fail(NRA_E_ARG, "device index out of range");
+    SCREEN_HIP_TRY(hipSetDevice(device));
+    nra_screen* s = new (std::nothrow) nra_screen;
+    if (!s) return fail(NRA_E_NOMEM, "screen handle");
+    s->device = device;
+    s->k = k;
+    s->n_regions = n_regions;
+    int rc = NRA_OK;
+    try {
+        const auto t0 = std::chrono::steady_clock::now();
+        rc = build_index(s, anchors, anchor_off, max_occ);
+        s->st.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    } catch (const std::bad_alloc&) {
+        rc = fail(NRA_E_NOMEM, "anchor index: host allocation failed");
+    }
+    if (rc == NRA_OK) {
+        hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipEventCreate(&s->ev0);
+        if (e == hipSuccess) e = hipEventCreate(&s->ev1);
+        if (e != hipSuccess) rc = fail(NRA_E_DEVICE, std::string("screen stream: ") + hipGetErrorString(e));
+    }
+    if (rc != NRA_OK) { delete s; return rc; }
+    *out = s;
+    return NRA_OK;
+}
+
+int nra_screen_reads(nra_screen_t* s, int32_t n_reads, const char* seqs, const int64_t* seq_off, int32_t min_hits,
+                     int64_t* n_pairs, int32_t* pair_read, int32_t* pair_region, int32_t* hits_left,
+                     int32_t* hits_right)
+{
+    if (!s) return fail(NRA_E_ARG, "screen handle is NULL");
+    if (!n_pairs) return fail(NRA_E_ARG, "n_pairs is NULL");
+    if (n_reads < 0) return fail(NRA_E_ARG, "negative read count");
+    if (min_hits < 1) return fail(NRA_E_ARG, "min_hits must be >= 1");
+    if (*n_pairs < 0) return fail(NRA_E_ARG, "negative pair capacity");
+    if (*n_pairs > 0 && (!pair_read || !pair_region || !hits_left || !hits_right))
+        return fail(NRA_E_ARG, "NULL output array");
+    if (n_reads > 0 && !seq_off) return fail(NRA_E_ARG, "seq_off is NULL");
+    if (n_reads > 0) {
+        if (seq_off[0] < 0) return fail(NRA_E_ARG, "negative read offset");
+        for (int32_t r = 0; r < n_reads; ++r)
+            if (seq_off[r + 1] < seq_off[r]) return fail(NRA_E_ARG, "read offsets must not decrease");
+        if (seq_off[n_reads] > seq_off[0] && !seqs) return fail(NRA_E_ARG, "seqs is NULL");
+    }
+    SCREEN_HIP_TRY(hipSetDevice(s->device));
+    try {
+        std::vector<NraScreenEntry> entries;
+        double kernel_ms = 0.0;
+        for (int32_t r0 = 0; r0 < n_reads;) {
+            int32_t r1 = r0 + 1;
+            while (r1 < n_reads && seq_off[r1 + 1] - seq_off[r0] <= kSegmentBytes) ++r1;
+            const int rc = screen_segment(s, r0, r1, seqs, seq_off, entries, kernel_ms);
+            if (rc != NRA_OK) return rc;
+            r0 = r1;
+        }
+        // sum per (read, set), then per (read, region) with the pass rule; regions with two empty sets take every read
+        std::sort(entries.begin(), entries.end(), [](const NraScreenEntry& a, const NraScreenEntry& b) {
+            return a.read != b.read ? a.read < b.read : a.set < b.set;
+        });
+        struct Pair { int32_t read, region, left, right; };
+        std::vector<Pair> pairs;
+        const auto& empty = s->empty_regions;
+        size_t i = 0;
+        for (int32_t r = 0; r < n_reads; ++r) {
+            size_t e = 0;
+            auto flush_empty_below = [&](int32_t region) {
+                for (; e < empty.size() && empty[e] < region; ++e) pairs.push_back(Pair{r, empty[e], 0, 0});
+            };
+            while (i < entries.size() && entries[i].read == r) {
+                const int32_t g = entries[i].set >> 1;
+                int64_t c[2] = {0, 0};
+                for (; i < entries.size() && entries[i].read == r && (entries[i].set >> 1) == g; ++i)
+                    c[entries[i].set & 1] += entries[i].count;
+                const int64_t need_l = std::min<int64_t>(min_hits, s->set_size[2 * (size_t)g]);
+                const int64_t need_r = std::min<int64_t>(min_hits, s->set_size[2 * (size_t)g + 1]);
+                if (c[0] >= need_l && c[1] >= need_r) {
+                    flush_empty_below(g);
+                    pairs.push_back(Pair{r, g, (int32_t)c[0], (int32_t)c[1]});
+                }
+            }
+            flush_empty_below(s->n_regions);
+        }
+        const int64_t cap = *n_pairs;
+        *n_pairs = (int64_t)pairs.size();
+        if ((int64_t)pairs.size() > cap)
+            return fail(NRA_E_RANGE, "more passing pairs (" + std::to_string(pairs.size()) + ") than the capacity (" +
+                                         std::to_string(cap) + ")");
+        for (size_t q = 0; q < pairs.size(); ++q) {
+            pair_read[q] = pairs[q].read; pair_region[q] = pairs[q].region;
+            hits_left[q] = pairs[q].left; hits_right[q] = pairs[q].right;
+        }
+        s->st.bases_screened += n_reads > 0 ? seq_off[n_reads] - seq_off[0] : 0;
+        s->st.kernel_ms = kernel_ms;
+        s->st.sum_kernel_ms += kernel_ms;
+        s->st.n_calls += 1;
+    } catch (const std::bad_alloc&) {
+        return fail(NRA_E_NOMEM, "screen: host allocation failed");
+    }
+    return NRA_OK;
+}
+
+int nra_screen_stats(const nra_screen_t* s, nra_screen_stats_t* st)
+{
+    if (!s || !st) return fail(NRA_E_ARG, "NULL argument");
+    *st = s->st;
+    return NRA_OK;
+}
+
+int nra_screen_destroy(nra_screen_t* s)
+{
+    if (!s) return NRA_OK;
+    (void)hipSetDevice(s->device);
+    delete s;
+    return NRA_OK;
+}
+
+}  // extern "C"

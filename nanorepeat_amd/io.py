@@ -59,6 +59,54 @@ def read_fastq(fastq_file):
     return reads
 
 
+def iter_reads(path, chunk_bases=1 << 28):
+    """Reads of a FASTQ or FASTA file (gzip-aware) as chunks of (names, seqs, quals) lists of about `chunk_bases`
+    bases each (a chunk ends at the first record that reaches it).  The format is the first record's: `@` FASTQ
+    (4-line records, as read_fastq), `>` FASTA (sequences over any number of lines, quality None).  Names are the
+    first word of the header; sequences are kept as written."""
+    names, seqs, quals, size = [], [], [], 0
+    with gzopen(path) as fp:
+        first = fp.readline()
+        while first and not first.strip():
+            first = fp.readline()
+        if not first:
+            return
+        if first[0] == "@":
+            l1 = first
+            while True:
+                l2, l3, l4 = fp.readline(), fp.readline(), fp.readline()
+                if not l1 or not l2 or not l3 or not l4:
+                    break
+                names.append(l1.strip()[1:].split()[0])
+                seqs.append(l2.strip())
+                quals.append(l4.strip())
+                size += len(seqs[-1])
+                if size >= chunk_bases:
+                    yield names, seqs, quals
+                    names, seqs, quals, size = [], [], [], 0
+                l1 = fp.readline()
+        elif first[0] == ">":
+            name, parts = first.strip()[1:].split()[0], []
+            for line in fp:
+                line = line.strip()
+                if not line:
+                    continue
+                if line[0] != ">":
+                    parts.append(line)
+                    continue
+                names.append(name); seqs.append("".join(parts)); quals.append(None)
+                size += len(seqs[-1])
+                if size >= chunk_bases:
+                    yield names, seqs, quals
+                    names, seqs, quals, size = [], [], [], 0
+                name, parts = line[1:].split()[0], []
+            names.append(name); seqs.append("".join(parts)); quals.append(None)
+        else:
+            raise ValueError(f"{path}: neither FASTQ (@) nor FASTA (>)")
+    if names:
+        yield names, seqs, quals
+
+
 def fastq_file_to_dict(in_fastq_file):
     """nanoRepeat_joint.py:652-673: {read_name: the record's four lines as one string}."""
     fastq_dict = dict()

@@ -1,7 +1,8 @@
 """Steps 1-4 of quantify1repeat_from_bam (nanoRepeat_bam.py:614-686) for one or many regions,
 from reads already extracted for the region: anchors -> core -> rounds 1-2 -> round 3 -> the
 `repeat_size.txt` text -> GMM phasing -> one row of `NanoRepeat_output.tsv` per region.
-`quantify_from_bam` and `quantify_joint` are the two commands from files to files."""
+`quantify_from_bam`, `quantify_from_reads` (FASTQ / FASTA) and `quantify_joint` are the commands from files
+to files."""
 from . import upstream, round3, phasing, joint, io as nr_io
 
 
@@ -151,18 +152,12 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
     here steps 1-2 run region by region and step 3 for all regions in one GPU batch.  Regions
     without reads, or whose reference sequence fails the motif check, get their row with 0
     alleles like in the reference.  Returns the regions."""
-    import os
     from . import bam as nr_bam
     regions = nr_io.read_repeat_region_file(repeat_region_bed, no_details)
     ref_fasta_dict = nr_io.fasta_file2dict(ref_fasta)
     live, reads_of = [], []
     for i, region in enumerate(regions):
-        region.index = i
-        chrom_dir = region.chrom if region.chrom[0:3].lower() == "chr" else "chr" + region.chrom
-        out_dir = f"{out_prefix}.details/{chrom_dir}"
-        os.makedirs(out_dir, exist_ok=True)
-        region.out_prefix = f"{out_dir}/{phasing.outfile_prefix(region)}"
-        region.region_fq_file = f"{region.out_prefix}.reads.fastq"
+        _set_region_paths(region, i, out_prefix)
         n = nr_bam.extract_fastq_from_bam(in_bam_file, region, anchor_len, region.region_fq_file, ref_fasta)
         if n == 0:
             continue
@@ -171,6 +166,25 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
             continue
         live.append(region)
         reads_of.append(nr_io.read_fastq(region.region_fq_file))
+    _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
+                        max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines)
+    return regions
+
+
+def _set_region_paths(region, index, out_prefix):
+    """`<out_prefix>.details/<chr>/<region>` (made here) and the region's `.reads.fastq` beside it."""
+    import os
+    region.index = index
+    chrom_dir = region.chrom if region.chrom[0:3].lower() == "chr" else "chr" + region.chrom
+    out_dir = f"{out_prefix}.details/{chrom_dir}"
+    os.makedirs(out_dir, exist_ok=True)
+    region.out_prefix = f"{out_dir}/{phasing.outfile_prefix(region)}"
+    region.region_fq_file = f"{region.out_prefix}.reads.fastq"
+
+
+def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
+                        max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines):
+    """The commands' common tail: steps 1-4 for the regions with reads, then one TSV row per BED region."""
     quantify_regions(live, reads_of, data_type, fast_mode, num_cpu, device, scoring,
                      engines.get("aligner"), engines.get("scorer"))
     phase_regions(live, data_type, ploidy, max_mutual_overlap, max_num_components, remove_noisy_reads, seed)
@@ -180,4 +194,49 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
     if no_details:
         import shutil
         shutil.rmtree(f"{out_prefix}.details", ignore_errors=True)
+
+
+def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data_type="ont", anchor_len=1000,
+                        fast_mode=False, ploidy=2, max_mutual_overlap=0.15, max_num_components=-1,
+                        remove_noisy_reads=False, no_check_repeat_motif_in_ref=False, no_details=False,
+                        num_cpu=1, device=0, scoring=None, seed=None, screen=True, k=15, min_hits=4, max_occ=16,
+                        chunk_bases=1 << 28, **engines):
+    """The FASTQ / FASTA command (nanoRepeat.py:109, `-t fastq|fasta`) from files to files, without a genome mapper:
+    the reads each region sees are chosen by the anchor k-mer screen (screen.reads_by_region) instead of a
+    genome-wide mapping and a BAM window, then the BAM command's steps run unchanged.  Every region's reference
+    must extract (else the command fails, as the BAM command does); regions that fail the motif check are not
+    screened and get their 0-allele row.  Each region's reads go to `<out_prefix>.details/<chr>/<region>.reads.fastq`
+    (qualities `.` for FASTA input).  screen=False offers every read to every region: exact, and slow beyond small
+    panels.  `engines` may carry aligner / scorer / screener stand-ins.  Returns the regions."""
+    from . import screen as nr_screen
+    regions = nr_io.read_repeat_region_file(repeat_region_bed, no_details)
+    ref_fasta_dict = nr_io.fasta_file2dict(ref_fasta)
+    screened = []
+    for i, region in enumerate(regions):
+        _set_region_paths(region, i, out_prefix)
+        nr_io.extract_ref_sequence(ref_fasta_dict, region, anchor_len)
+        if no_check_repeat_motif_in_ref or nr_io.check_repeat_motif_in_ref(region):
+            screened.append(region)
+    if screen:
+        found = nr_screen.reads_by_region(in_reads, screened, k=k, max_occ=max_occ, min_hits=min_hits,
+                                          chunk_bases=chunk_bases, device=device, screener=engines.get("screener"))
+    else:
+        found = nr_screen.all_reads_by_region(in_reads, len(screened), chunk_bases)
+    found_of = {id(region): reads for region, reads in zip(screened, found)}
+    live, reads_of = [], []
+    for region in regions:
+        reads = found_of.get(id(region), {})
+        _write_region_fastq(region.region_fq_file, reads)
+        if reads:
+            live.append(region)
+            reads_of.append({name: seq for name, (seq, _) in reads.items()})
+    _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
+                        max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines)
     return regions
+
+
+def _write_region_fastq(path, reads):
+    """{name: (seq, qual)} as extract_fastq_from_bam writes it: a missing quality becomes '.' (Phred 13)."""
+    with open(path, "w") as f:
+        for name, (seq, qual) in reads.items():
+            f.write(f"@{name}\n{seq}\n+\n{qual if qual is not None else '.' * len(seq)}\n")

@@ -223,3 +223,122 @@ def make_joint(n_reads, unit1="CAG", unit2="CCG", mid="CAACAGCCGCCAC",
 def config3(n_reads=5000, seed=SEED):
     """BASELINE config 3: HTT amplicon joint CAG+CCG quantification, 5k reads."""
     return make_joint(n_reads, seed=seed)
+
+
+DECOY_KINDS = ("slice", "random", "single", "nrun", "lower", "short")
+
+
+def panel(n_regions=12, n_chroms=3, anchor_len=1000, reads_per_region=10, model="ont", edge_overlaps=(), n_decoys=0,
+          shared=0, shared_len=300, lower_every=7, seed=SEED):
+    """A seeded multi-region panel for the FASTQ / FASTA command (screen + anchors + rounds).
+
+    Regions sit on `n_chroms` chromosomes with at least 4 kb between the windows region +- anchor_len.  Per region:
+    `reads_per_region` spanning reads (both anchors, 0-500 bases beyond each), half of them reverse-complemented,
+    and, for every overlap o in `edge_overlaps`, two reads that start or end inside an anchor with o bases of it
+    (the other side spans); every read goes through the `model` error channel and every `lower_every`-th one is
+    lowercase.  `n_decoys` decoys cycle through DECOY_KINDS: a genome slice outside every window, random sequence,
+    one anchor only, random sequence with N runs, a lowercase genome slice, a read shorter than 11 bases.
+    `shared` > 0: the same `shared_len`-base element replaces the middle of the left anchor of that many regions
+    (k-mers shared by more anchors than max_occ are masked by the screen).
+
+    Returns dict(ref={chrom: seq}, bed=[line], regions=[(chrom, start, end, unit)], reads=[(name, seq)] in a
+    shuffled file order, truth={name: (region, k)}, overlap={name: (left bases, right bases) of the anchors}).
+    """
+    rng = np.random.default_rng(seed)
+    element = rand_seq(rng, shared_len)
+    gap, extra = 3000, 800
+    chroms = {f"chr{c + 1}": [] for c in range(n_chroms)}
+    lengths = {name: 0 for name in chroms}
+    regions, deserts = [], []              # deserts: (chrom, start, end) outside every window
+    for g in range(n_regions):
+        chrom = f"chr{g % n_chroms + 1}"
+        unit = rand_unit(rng, int(rng.integers(3, 7)))
+        kref = int(rng.integers(8, 21))
+        left = rand_seq(rng, anchor_len + extra)
+        if g < shared:
+            mid = len(left) - anchor_len // 2 - shared_len // 2
+            left = left[:mid] + element + left[mid + shared_len:]
+        parts = [rand_seq(rng, gap), left, unit * kref, rand_seq(rng, anchor_len + extra)]
+        at = lengths[chrom]
+        deserts.append((chrom, at, at + gap))
+        start = at + gap + len(left)
+        regions.append((chrom, start, start + len(unit) * kref, unit))
+        chroms[chrom] += parts
+        lengths[chrom] += sum(len(p) for p in parts)
+    for chrom in chroms:                   # a tail gap after the last window
+        deserts.append((chrom, lengths[chrom], lengths[chrom] + gap))
+        chroms[chrom].append(rand_seq(rng, gap))
+    ref = {name: "".join(p) for name, p in chroms.items()}
+
+    raw, truth, overlap = [], {}, {}
+    for g, (chrom, st, en, unit) in enumerate(regions):
+        kref = (en - st) // len(unit)
+        alleles = (max(3, kref + int(rng.integers(-5, 6))), kref + int(rng.integers(6, 25)))
+        plan = [(anchor_len + int(rng.integers(0, 501)), anchor_len + int(rng.integers(0, 501)))
+                for _ in range(reads_per_region)]
+        for o in edge_overlaps:
+            plan += [(int(o), anchor_len + int(rng.integers(0, 501))), (anchor_len + int(rng.integers(0, 501)), int(o))]
+        for i, (lo, ro) in enumerate(plan):
+            k = alleles[i % 2]
+            name = f"p{g:04d}_{i:03d}"
+            raw.append((name, ref[chrom][st - lo:st] + unit * k + ref[chrom][en:en + ro]))
+            truth[name] = (g, k)
+            overlap[name] = (min(lo, anchor_len), min(ro, anchor_len))
+    seqs = apply_errors_batch(rng, [s for _, s in raw], model) if raw else []
+    reads = []
+    for i, ((name, _), s) in enumerate(zip(raw, seqs)):
+        if rng.random() < 0.5:
+            s = revcomp(s)
+        if lower_every and i % lower_every == lower_every - 1:
+            s = s.lower()
+        reads.append((name, s))
+
+    for i in range(n_decoys):
+        kind = DECOY_KINDS[i % len(DECOY_KINDS)]
+        if kind in ("slice", "lower"):
+            chrom, a, b = deserts[int(rng.integers(0, len(deserts)))]
+            ln = int(rng.integers(500, b - a))
+            p = a + int(rng.integers(0, b - a - ln + 1))
+            s = ref[chrom][p:p + ln]
+            s = s.lower() if kind == "lower" else s
+        elif kind == "random":
+            s = rand_seq(rng, int(rng.integers(500, 3000)))
+        elif kind == "single":
+            chrom, st, en, unit = regions[int(rng.integers(0, n_regions))]
+            s = ref[chrom][st - anchor_len:st] + rand_seq(rng, 600)
+            s = apply_errors(rng, s, model)
+        elif kind == "nrun":
+            s = rand_seq(rng, 1500)
+            for _ in range(3):
+                p = int(rng.integers(0, 1400))
+                s = s[:p] + "N" * 50 + s[p + 50:]
+        else:
+            s = rand_seq(rng, int(rng.integers(1, 11)))
+        reads.append((f"decoy_{kind}_{i:04d}", s))
+    order = rng.permutation(len(reads))
+    reads = [reads[i] for i in order]
+    bed = [f"{c}\t{st}\t{en}\t{u}\n" for c, st, en, u in regions]
+    return dict(ref=ref, bed=bed, regions=regions, reads=reads, truth=truth, overlap=overlap)
+
+
+def write_panel(p, directory, fmt="fastq", wrap=80):
+    """The panel's files: ref.fa, panel.bed and reads.fastq (Phred 20 qualities) / reads.fasta (lines of `wrap`
+    bases) / reads.fastq.gz.  Returns (ref, bed, reads) paths."""
+    import gzip
+    import os
+    ref = os.path.join(directory, "ref.fa")
+    with open(ref, "w") as f:
+        for name, seq in p["ref"].items():
+            f.write(f">{name}\n" + "".join(seq[i:i + 80] + "\n" for i in range(0, len(seq), 80)))
+    bed = os.path.join(directory, "panel.bed")
+    with open(bed, "w") as f:
+        f.write("".join(p["bed"]))
+    if fmt == "fasta":
+        text = "".join(f">{n} synthetic\n" + "".join(s[i:i + wrap] + "\n" for i in range(0, len(s), wrap))
+                       for n, s in p["reads"])
+    else:
+        text = "".join(f"@{n} synthetic\n{s}\n+\n{'5' * len(s)}\n" for n, s in p["reads"])
+    reads = os.path.join(directory, {"fastq": "reads.fastq", "fasta": "reads.fasta", "fastq.gz": "reads.fastq.gz"}[fmt])
+    with (gzip.open(reads, "wt") if fmt == "fastq.gz" else open(reads, "w")) as f:
+        f.write(text)
+    return ref, bed, reads
