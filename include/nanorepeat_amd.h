@@ -382,6 +382,30 @@ int nra_screen_reads(nra_screen_t* s, int32_t n_reads, const char* seqs, const i
 int nra_screen_stats(const nra_screen_t* s, nra_screen_stats_t* st);
 int nra_screen_destroy(nra_screen_t* s);
 
+/* ---- repeat structure: what a read's tract is made of (no counterpart in the reference) ---------------------------
+ *
+ * Each read's tract s (n bases, upper-cased first; a byte other than ACGT mismatches every motif base) is aligned
+ * globally in s against its motif u (p bases, 1 <= p <= 64, uppercase ACGT) repeated without end, starting and ending
+ * at any phase (phase j = motif bases consumed mod p).  Unit costs:
+ *   D[0][j] = 0;  for i >= 1, c = s[i-1]:
+ *   T[j]    = min(D[i-1][(j-1) mod p] + (c != u[(j-1) mod p])   diagonal, consumes u[(j-1) mod p]
+ *                 D[i-1][j] + 1)                                insertion; a tie takes the diagonal
+ *   D[i][j] = min(T[j], D[i][(j-1) mod p] + 1)                  deletion, cyclic until stable; a tie keeps T
+ *   edits = min_j D[n][j]; the end phase is the smallest j that attains it.
+ * Traceback from (n, end phase): a deletion stays in row i and moves to phase j-1, an insertion to (i-1, j), a diagonal
+ * step to (i-1, j-1); start_phase = the phase where it reaches row 0.  One path byte per tract base: bits 0-1 the
+ * base's op (0 match, 1 mismatch, 2 insertion), bits 2-7 the motif bases deleted right after it (0..p-1).
+ * DESIGN.md section 14. */
+
+/* motif m = bytes [motif_off[m], motif_off[m+1]) of `motifs` (n_motifs >= 1); read r = bytes [seq_off[r],
+ * seq_off[r+1]) of `seqs` (at most 200 000, NRA_E_RANGE beyond), aligned against motif read_motif[r].  Writes
+ * edits[r], start_phase[r] and the path bytes of read r at path[seq_off[r] ...] (path: seq_off[n_reads] bytes).
+ * A motif of 0 bases or with a byte other than A, C, G, T is NRA_E_ARG, one of more than 64 bases NRA_E_RANGE;
+ * arguments are checked before the device is touched. */
+int nra_read_structure(int device, int32_t n_motifs, const char* motifs, const int64_t* motif_off,
+                       int32_t n_reads, const char* seqs, const int64_t* seq_off, const int32_t* read_motif,
+                       int32_t* edits, int32_t* start_phase, uint8_t* path);
+
 #ifdef __cplusplus
 }
 #endif

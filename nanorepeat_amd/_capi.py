@@ -32,7 +32,8 @@ EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count
            "nra_default_scoring", "nra_release_cached_memory", "nra_round3_1d", "nra_joint_2d", "nra_align_pairs", "nra_align_pairs_cigar", "nra_batch1d_create",
            "nra_batch2d_create", "nra_batch2d_create_reads", "nra_batch2d_set_cells", "nra_joint_grid_cells", "nra_batch2d_set_grid", "nra_batch2d_invalidate", "nra_batch2d_sweep_flanks", "nra_batch2d_refine", "nra_batch_run", "nra_batch_sync", "nra_batch_stats",
            "nra_batch1d_fetch", "nra_batch2d_fetch", "nra_batch_destroy",
-           "nra_screen_create", "nra_screen_reads", "nra_screen_stats", "nra_screen_destroy")
+           "nra_screen_create", "nra_screen_reads", "nra_screen_stats", "nra_screen_destroy",
+           "nra_read_structure")
 
 
 E_RANGE = -3      # NRA_E_RANGE
@@ -166,6 +167,9 @@ def load():
     lib.nra_screen_stats.argtypes = [vp, C.POINTER(ScreenStats)]
     lib.nra_screen_destroy.restype = C.c_int
     lib.nra_screen_destroy.argtypes = [vp]
+    lib.nra_read_structure.restype = C.c_int
+    lib.nra_read_structure.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, C.c_int32, C.c_char_p, pi64, pi32,
+                                       pi32, pi32, p8]
     _LIB = lib
     return lib
 
@@ -604,3 +608,21 @@ def screen_reads(handle, reads, min_hits=4, capacity=None):
 def screen_destroy(handle):
     if handle:
         _check(load().nra_screen_destroy(handle))
+
+
+def read_structure(motifs, tracts, read_motif, device=0):
+    """nra_read_structure: the wraparound alignment of every tract against its motif (motifs[read_motif[i]]) ->
+    dict(edits, start_phase, path, path_off): the path bytes of tract i are path[path_off[i]:path_off[i + 1]]."""
+    lib = load()
+    mdata, moff = pack_reads(list(motifs))
+    data, off = pack_reads(tracts)
+    rm = np.ascontiguousarray(read_motif, np.int32)
+    n = len(tracts)
+    if len(rm) != n:
+        raise ValueError("one motif index per tract")
+    out = dict(edits=np.zeros(n, np.int32), start_phase=np.zeros(n, np.int32),
+               path=np.zeros(int(off[-1]), np.uint8), path_off=off)
+    _check(lib.nra_read_structure(device, len(motifs), mdata, _ptr(moff, C.c_int64), n, data, _ptr(off, C.c_int64),
+                                  _ptr(rm, C.c_int32), _ptr(out["edits"], C.c_int32),
+                                  _ptr(out["start_phase"], C.c_int32), _ptr(out["path"], C.c_uint8)))
+    return out

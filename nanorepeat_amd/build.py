@@ -1,7 +1,7 @@
 """Build nanorepeat_amd/libnanorepeat_amd.so (HIP kernels + C ABI) in-tree for gfx950.
 
 hipcc cross-compiles without a GPU.  The kernel file is split into parts
-(-DNRA_PART=1..27) that compile in parallel; the shared library carries only gfx950 code.
+(-DNRA_PART=1..28) that compile in parallel; the shared library carries only gfx950 code.
 """
 import os
 import subprocess
@@ -14,8 +14,8 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libnanorepeat_amd.so")
 OBJ = os.path.join(HERE, "csrc", "build")
 
-SOURCES = ["nra_kernels.hip", "nra_sweep.hip", "nra_joint.hip", "nra_trace.hip", "nra_screen.hip", "nra_host.cpp",
-           "nra_screen_host.cpp", "nra_internal.h", "nra_device.h", "nra_pk16.h"]
+SOURCES = ["nra_kernels.hip", "nra_sweep.hip", "nra_joint.hip", "nra_trace.hip", "nra_screen.hip", "nra_structure.hip",
+           "nra_host.cpp", "nra_screen_host.cpp", "nra_structure_host.cpp", "nra_internal.h", "nra_device.h", "nra_pk16.h"]
 ARCH = "gfx950"
 
 
@@ -62,7 +62,10 @@ def build_library(force=False, jobs=None, verbose=False):
     o = os.path.join(OBJ, "nra_screen_p27.o")
     objs.append(o)
     cmds.append(common + ["-DNRA_PART=27", "-c", os.path.join(CSRC, "nra_screen.hip"), "-o", o])
-    for host in ("nra_host", "nra_screen_host"):
+    o = os.path.join(OBJ, "nra_structure_p28.o")
+    objs.append(o)
+    cmds.append(common + ["-DNRA_PART=28", "-c", os.path.join(CSRC, "nra_structure.hip"), "-o", o])
+    for host in ("nra_host", "nra_screen_host", "nra_structure_host"):
         o = os.path.join(OBJ, host + ".o")
         objs.append(o)
         cmds.append(common + ["-pthread", "-c", os.path.join(CSRC, host + ".cpp"), "-o", o])

@@ -202,6 +202,33 @@ struct NraScreenEntry {
     int32_t read, set, count;
 };
 
+// Repeat structure (nra_structure.hip, nra_structure_host.cpp): the wraparound edit-distance alignment of a read's tract
+// against its motif repeated without end, one lane per read.  A launch takes reads of one phase
+// capacity P (motif length p <= P), sorted by tract length, descending, 64 to a wave.
+#define NRA_STRUCT_MAX_P 64
+#define NRA_STRUCT_MAX_N 200000
+#define NRA_STRUCT_BLOCK 16                   // tract bases per code load / path store / traceback block (16-byte aligned)
+#define NRA_STRUCT_CODE_OTHER 4               // a tract byte other than ACGT (either case): mismatches every motif base
+
+// eq[c] bit j: the motif base a diagonal step into phase j consumes, u[(j - 1) mod p], has code c (A=0 C=1 G=2 T=3)
+struct NraStructMotif {
+    uint64_t eq[4];
+    int32_t p;
+    int32_t pad;
+};
+
+// one read of a launch: its codes (and its path bytes) start at byte `tract` of the chunk's buffers (a multiple of
+// NRA_STRUCT_BLOCK), its wave's traceback pointers at dword `ptr` ([row][lane] of the wave, the words of a row per lane)
+struct NraStructRead {
+    uint64_t tract;
+    uint64_t ptr;
+    int32_t n;
+    int32_t motif;
+};
+
+// traceback pointer words per (row, lane): ins bits of the P phases, then del bits
+#define NRA_STRUCT_WORDS(P) ((P) <= 16 ? 1 : (P) <= 32 ? 2 : 4)
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -214,6 +241,11 @@ int nra_set_error(int code, const char* msg);
 int nra_launch_screen_hits(hipStream_t st, int64_t n_tiles, const NraScreenTile* tiles, const uint8_t* seqs, int k,
                            const uint64_t* table, int log2_slots, const uint32_t* postings, NraScreenEntry* entries,
                            unsigned long long cap, unsigned long long* count);
+
+// repeat structure (nra_structure.hip): one lane per read, forward DP then traceback.  P in {1..6, 8, 16, 32, 64};
+// res[2 i] = edits, res[2 i + 1] = start phase of read i
+int nra_launch_structure(hipStream_t st, int P, int n_reads, const NraStructRead* reads, const NraStructMotif* motifs,
+                         const uint8_t* codes, uint32_t* ptrs, uint8_t* path, int32_t* res);
 
 // launchers (nra_kernels.hip).  All asynchronous on `st`; return hipError_t as int.
 int nra_launch_score_pk16(int R, int has_n, hipStream_t st, int n_tasks,

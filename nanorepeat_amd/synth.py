@@ -342,3 +342,44 @@ def write_panel(p, directory, fmt="fastq", wrap=80):
     with (gzip.open(reads, "wt") if fmt == "fastq.gz" else open(reads, "w")) as f:
         f.write(text)
     return ref, bed, reads
+
+
+def structure_panel(reads_per_allele=8, anchor_len=1000, model="hifi", seed=SEED):
+    """A small panel whose alleles carry planted interruptions, for the repeat structure (structure.py):
+    an HTT-like CAG tract ending in CAA CAG ((CAG)17 CAA CAG and (CAG)36 CAA CAG), an FMR1-like CGG tract with two
+    AGG interruptions ((CGG)9 AGG (CGG)9 AGG (CGG)m, m = 10 and 28) and a pure TATTG tract (12 and 30 units).  Reads
+    span both anchors, half reverse-complemented, through the `model` error channel.  Its own random stream.
+
+    Returns dict(ref, bed, regions, reads, truth) like panel(), plus planted = [per region, per allele in size order:
+    [(bases, first slot)] of the planted interruptions].
+    """
+    rng = np.random.default_rng(seed)
+    loci = [("CAG", [("CAG" * 17 + "CAA" + "CAG", [("CAA", 17)]), ("CAG" * 36 + "CAA" + "CAG", [("CAA", 36)])],
+             "CAG" * 20 + "CAA" + "CAG"),
+            ("CGG", [("CGG" * 9 + "AGG" + "CGG" * 9 + "AGG" + "CGG" * m, [("AGG", 9), ("AGG", 19)]) for m in (10, 28)],
+             "CGG" * 9 + "AGG" + "CGG" * 9 + "AGG" + "CGG" * 12),
+            ("TATTG", [("TATTG" * 12, []), ("TATTG" * 30, [])], "TATTG" * 16)]
+    gap, extra = 3000, 800
+    parts, regions, at = [], [], 0
+    for unit, _, ref_tract in loci:
+        left, right = rand_seq(rng, anchor_len + extra), rand_seq(rng, anchor_len + extra)
+        start = at + gap + len(left)
+        regions.append(("chr1", start, start + len(ref_tract), unit))
+        parts += [rand_seq(rng, gap), left, ref_tract, right]
+        at += gap + len(left) + len(ref_tract) + len(right)
+    parts.append(rand_seq(rng, gap))
+    chrom = "".join(parts)
+    raw, truth = [], {}
+    for g, ((unit, alleles, _), (_, st, en, _)) in enumerate(zip(loci, regions)):
+        for a, (tract, _) in enumerate(alleles):
+            for i in range(reads_per_allele):
+                lo, ro = anchor_len + int(rng.integers(0, 301)), anchor_len + int(rng.integers(0, 301))
+                name = f"s{g}_{a}_{i:02d}"
+                raw.append((name, chrom[st - lo:st] + tract + chrom[en:en + ro]))
+                truth[name] = (g, a)
+    seqs = apply_errors_batch(rng, [s for _, s in raw], model)
+    reads = [(name, revcomp(s) if rng.random() < 0.5 else s) for (name, _), s in zip(raw, seqs)]
+    order = rng.permutation(len(reads))
+    reads = [reads[i] for i in order]
+    return dict(ref={"chr1": chrom}, bed=[f"{c}\t{st}\t{en}\t{u}\n" for c, st, en, u in regions], regions=regions,
+                reads=reads, truth=truth, planted=[[inter for _, inter in alleles] for _, alleles, _ in loci])
