@@ -76,6 +76,9 @@ extern "C" {
                                  hundred steps (k_sweep_ringq) */
 #define NRA_F_QUANTA_2L 4096  /* accepted and ignored since the sweeps' quanta became parts of a few hundred steps (it ran the three
                                  quanta of round 4's first form as two launches without tickets: measured no better than no quanta) */
+#define NRA_F_FULL_ANCHORS 8192 /* testing / comparison, 1D: the LDS-ring sweeps run the exact cell over every anchor column, instead of
+                                 a relaxed upper-bound cell over the anchor columns far from the junction and an exact re-sweep of the
+                                 read pairs where that bound may have reached a result (same results either way) */
 #define NRA_F_BRUTE_FORCE  4  /* score the K candidates of a read as K independent alignments
                                  (k_score_pk16) instead of the junction decomposition (k_sweep_pk16) */
 
@@ -334,6 +337,9 @@ int  nra_batch_stats(nra_batch_t* b, nra_stats_t* st);   /* after sync */
 int  nra_batch1d_fetch(nra_batch_t* b,
                        int32_t* best_score, int64_t* sum_k, int32_t* n_ties, uint8_t* status,
                        int32_t* cand_score, int32_t* cand_tstart, int32_t* cand_tend);
+/* 1D, after sync: how many sweep tasks (read pairs, or two pairs of the half-wave sweeps) and reads the relaxed anchor
+ * columns sent to the exact re-sweep in the last run, and how many there were in all (0 / 0 with NRA_F_FULL_ANCHORS) */
+int  nra_batch1d_resweeps(nra_batch_t* b, int64_t* tasks, int64_t* reads, int64_t* tasks_total, int64_t* reads_total);
 int  nra_batch2d_fetch(nra_batch_t* b, int8_t* read_strand,
                        int32_t* cell_score, int32_t* cell_wscore,
                        int32_t* best_wscore, int64_t* sum_k1, int64_t* sum_k2,

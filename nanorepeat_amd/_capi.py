@@ -26,12 +26,13 @@ F_JOINT_NO_CHAIN = 512  # testing / comparison, 2D routed grids: the MID part as
 F_NO_QUANTA = 2048    # testing / comparison, 1D: reverse and forward sweeps as two launches instead of one launch of quanta taken by ticket
 F_QUANTA_2L = 4096    # accepted and ignored (round 4's first form of the quanta as two launches)
 F_SERIAL_CHAIN = 128  # testing / comparison, 1D: a long read's row blocks one after the other in one wave
+F_FULL_ANCHORS = 8192  # testing / comparison, 1D: the exact cell over every anchor column (no relaxed cells, no re-sweep)
 
 # every symbol include/nanorepeat_amd.h declares
 EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count",
            "nra_default_scoring", "nra_release_cached_memory", "nra_round3_1d", "nra_joint_2d", "nra_align_pairs", "nra_align_pairs_cigar", "nra_batch1d_create",
            "nra_batch2d_create", "nra_batch2d_create_reads", "nra_batch2d_set_cells", "nra_joint_grid_cells", "nra_batch2d_set_grid", "nra_batch2d_invalidate", "nra_batch2d_sweep_flanks", "nra_batch2d_refine", "nra_batch_run", "nra_batch_sync", "nra_batch_stats",
-           "nra_batch1d_fetch", "nra_batch2d_fetch", "nra_batch_destroy",
+           "nra_batch1d_fetch", "nra_batch1d_resweeps", "nra_batch2d_fetch", "nra_batch_destroy",
            "nra_screen_create", "nra_screen_reads", "nra_screen_stats", "nra_screen_destroy",
            "nra_read_structure")
 
@@ -154,6 +155,8 @@ def load():
     lib.nra_batch_stats.restype = C.c_int
     lib.nra_batch_stats.argtypes = [vp, C.POINTER(Stats)]
     lib.nra_batch1d_fetch.restype = C.c_int
+    lib.nra_batch1d_resweeps.restype = C.c_int
+    lib.nra_batch1d_resweeps.argtypes = [vp, pi64, pi64, pi64, pi64]
     lib.nra_batch1d_fetch.argtypes = [vp, pi32, pi64, pi32, p8, pi32, pi32, pi32]
     lib.nra_batch2d_fetch.restype = C.c_int
     lib.nra_batch2d_fetch.argtypes = [vp, pi8, pi32, pi32, pi32, pi64, pi64, pi32, p8]
@@ -529,6 +532,12 @@ class Batch:
         st = Stats()
         _check(load().nra_batch_stats(self._h, C.byref(st)))
         return st.as_dict()
+
+    def resweeps(self):
+        """1D, after the run: the sweep tasks and reads the relaxed anchor columns sent to the exact re-sweep, of how many."""
+        v = [C.c_int64(0) for _ in range(4)]
+        _check(load().nra_batch1d_resweeps(self._h, *[C.byref(x) for x in v]))
+        return {"tasks": v[0].value, "reads": v[1].value, "tasks_total": v[2].value, "reads_total": v[3].value}
 
     def fetch(self, per_candidate=True):
         lib = load()

@@ -416,6 +416,8 @@ struct Bucket {
     size_t sweep_off = 0;
     bool ring = false;         // k_sweep_ring (LDS hand-off) instead of k_sweep_pk16 (DPP hand-off)
     bool quanta = false;       // ... and its reverse and forward sweeps as ONE launch of quanta taken by ticket (k_sweep_ringq)
+    bool taint = false;        // ... with the relaxed cell over the anchor columns far from the junction, and the exact re-sweep
+                               // of the tasks it flags
     size_t q_off = 0, q_task_off = 0, q_state_off = 0;      // into q_list, q_words' arrivals (2 a task), q_state (int32, 2 slots a task)
     int n_quanta = 0, q_steps = 0;                            // entries of q_list; steps of a part
     int n_jbwd = 0;            // 2D decomposition: reverse sweeps (one per read)
@@ -560,6 +562,9 @@ struct nra_batch {
     DevBuf<NraSweepTask> sweep_tasks;
     DevBuf<int32_t> snap;                      // R side of the junction: per sweep task 3 planes of R x 64 (both reads packed)
     DevBuf<int32_t> read_a1d;                  // A per read: best alignment inside R (origin-bit scheme)
+    int relax_c = 0;                           // the taint scheme's margin (bases of an anchor next to the junction swept exactly); 0: off
+    DevBuf<int32_t> redo;                      // ... per sweep task: a relaxed cell may have reached an output, swept again exactly
+    std::vector<uint8_t> task_reads;           // ... per sweep task: its reads (nra_batch1d_resweeps)
     DevBuf<uint8_t> cand_flag;                 // flank verdict per candidate
     bool brute = false;                        // K independent alignments instead of the sweeps
     DevBuf<int32_t> chain_sweep;                // scratch strips of the chained row blocks (int32 sweep cells)
@@ -1070,6 +1075,15 @@ int nra_batch1d_create(int device, const nra_region_t* regions, int32_t n_region
         // and every state in [0x0400, 0x7bff] (nra_sweep.hip: bias 2048, "minus infinity" 1280)
         const int o2 = sc->gap_open2 + sc->gap_ext2;
         if (2 * sc->gap_ext1 > 256 || 2 * sc->gap_ext2 > 256 || 2 * (o2 + sc->mismatch + sc->sc_ambi) > 700) brute = true;
+        // The taint scheme quadruples the scores: the same bounds at 4x, and the relaxed cell opens its one
+        // gap state at o1 (= min(o1, o2): it shares the exact cell's substitution table).  Other schemes keep the doubled
+        // cells of every sweep.  NRA_RELAX_C (tests, measurements): the margin, in bases; 0 turns the scheme off.
+        b->relax_c = NRA_RELAX_C_DEFAULT;
+        if (const char* e = getenv("NRA_RELAX_C")) b->relax_c = std::max(0, atoi(e));
+        if (b->relax_c > 0) b->relax_c = std::max(b->relax_c, 64);
+        if ((flags & NRA_F_FULL_ANCHORS) || o1 > o2 || 4 * (sc->match + o1) > 127 || 4 * sc->gap_ext1 > 256 ||
+            4 * sc->gap_ext2 > 256 || 4 * (o2 + sc->mismatch + sc->sc_ambi) > 700)
+            b->relax_c = 0;
     }
     // Which reads leave the packed int16 sweeps for the chained int32 ones (one read per wave, any length):
     // more rows than one register block, scores beyond the doubled int16 range, or a template whose
@@ -1278,6 +1292,10 @@ int nra_batch1d_create(int device, const nra_region_t* regions, int32_t n_region
                 bk.ring = (flags & NRA_F_DPP_SWEEP) == 0;
                 for (int32_t r : order)
                     if (dregs[pr.reads[r].region].m1 > NRA_SWEEP_RING_MAX_M) bk.ring = false;
+                // the taint scheme: quadrupled scores <= 27000 in the packed cells (nra_pk16.h)
+                bk.taint = bk.ring && b->relax_c > 0;
+                for (int32_t r : order)
+                    if (4 * max_score(sc, pr.reads[r].qlen) > 27000) bk.taint = false;
             }
             if (bk.half) {
                 // four reads of a region per wave: two pairs, one per half, the union of their windows
@@ -1402,6 +1420,19 @@ int nra_batch1d_create(int device, const nra_region_t* regions, int32_t n_region
     if (!brute) {
         HIP_TRY(b->snap.alloc((size_t)snap_total));
         HIP_TRY(b->read_a1d.alloc((size_t)n_reads));
+        bool any_taint = false;
+        for (const Bucket& bk : b->buckets) any_taint = any_taint || bk.taint;
+        if (any_taint) {
+            HIP_TRY(b->redo.alloc(std::max<size_t>(sweep_tasks.size(), 1)));
+            // (zero before any run, so that nra_batch1d_resweeps reads no flag of a run that has not happened)
+            HIP_TRY(hipMemsetAsync(b->redo.p, 0, b->redo.n * 4, b->stream));
+            HIP_TRY(hipStreamSynchronize(b->stream));
+            b->task_reads.resize(sweep_tasks.size());
+            for (size_t t = 0; t < sweep_tasks.size(); ++t) {
+                const NraSweepTask& x = sweep_tasks[t];
+                b->task_reads[t] = (uint8_t)((x.read_a >= 0) + (x.read_b >= 0) + (x.read_c >= 0) + (x.read_d >= 0));
+            }
+        }
         // Quanta (k_sweep_ringq): for the unchained LDS-ring buckets of a batch whose tasks are few against the wave slots --
         // kernel-length tasks then end a launch with SIMDs holding 3 or 4 of them while others hold 2 or 3; with tens of
         // tasks per slot (BASELINE config 4) two launches already run at 0.98 of the issue ceiling and the states at the
@@ -1547,6 +1578,7 @@ static int run_1d(nra_batch* b)
         HIP_TRY(hipMemsetAsync(b->mt_words.p, getenv("NRA_TEST_MT_GIVEUP") ? 1 : 0, 4, st));
         b->mt_checked = false;
     }
+    if (b->redo.n > 0) HIP_TRY(hipMemsetAsync(b->redo.p, 0, b->redo.n * 4, st));
     if (b->q_words_n > 0) {
         // the sweeps in quanta: tickets and arrival counters start at 0; the give-up word too (NRA_TEST_MT_GIVEUP: set)
         HIP_TRY(hipMemsetAsync(b->q_words.p, 0, b->q_words_n * 4, st));
@@ -1562,6 +1594,25 @@ static int run_1d(nra_batch* b)
         // junction decomposition: per bucket a chain reverse sweep -> forward sweep, each chain on
         // its own stream so that short buckets fill the SIMDs a long bucket's tail leaves idle
         HIP_TRY(hipEventRecord(b->fork_ev, st));
+        // The exact re-sweep of a tainted bucket's flagged tasks: today's two launches, behind the tainted
+        // sweeps on the bucket's stream; every other wave leaves at once.  It rewrites the tasks' R side, A and outputs.
+        auto resweep = [&](const Bucket& bk, hipStream_t q, int32_t* redo) {
+            int rc2 = bk.half ? nra_launch_sweep_ring32_bwd(bk.R, b->has_n, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off, b->reads.p,
+                                                            b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p,
+                                                            b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p, 0, redo)
+                              : nra_launch_sweep_ring_bwd(bk.R, b->has_n, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off, b->reads.p,
+                                                          b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p,
+                                                          b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p, 0, redo);
+            if (rc2) return rc2;
+            return bk.half ? nra_launch_sweep_ring32_fwd(bk.R, b->has_n, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off, b->reads.p,
+                                                         b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p,
+                                                         b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p, b->cand_score.p,
+                                                         b->cand_flag.p, 0, redo)
+                           : nra_launch_sweep_ring_fwd(bk.R, b->has_n, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off, b->reads.p,
+                                                       b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p,
+                                                       b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p, b->cand_score.p,
+                                                       b->cand_flag.p, 0, redo);
+        };
         // (the order the buckets' chains are launched in makes no difference: 5.50 - 5.61 ms either way on config 2;
         // a bucket's tasks as 2 / 3 / 4 groups with chains of their own are slower: 5.65 -> 6.0 / 5.9 / 7.6 ms)
         std::vector<size_t> order;
@@ -1580,6 +1631,8 @@ static int run_1d(nra_batch* b)
             const size_t i = order[oi];
             const Bucket& bk = b->buckets[i];
             hipStream_t q = b->bstreams[i];
+            int32_t* redo = bk.taint ? b->redo.p + bk.sweep_off : nullptr;
+            const int relax_c = bk.taint ? b->relax_c : 0;
             HIP_TRY(hipStreamWaitEvent(q, b->fork_ev, 0));
             if (mt_first && bk.quanta && mt_rev_recorded) HIP_TRY(hipStreamWaitEvent(q, b->mt_rev_ev, 0));
             HIP_TRY(hipEventRecord(b->ev[ev++], q));
@@ -1592,7 +1645,8 @@ static int run_1d(nra_batch* b)
                                   b->q_words.p + b->q_arrivals_off + bk.q_task_off, b->q_words.p, b->q_state.p + bk.q_state_off,
                                   b->sweep_tasks.p + bk.sweep_off, b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p,
                                   b->sp, b->kmin.p, b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p, b->cand_score.p,
-                                  b->cand_flag.p));
+                                  b->cand_flag.p, bk.taint ? b->relax_c : 0, redo));
+                if (bk.taint) LAUNCH_TRY(resweep(bk, q, redo));
                 HIP_TRY(hipEventRecord(b->ev[ev++], q));
                 HIP_TRY(hipEventRecord(b->ev[ev++], q));
                 HIP_TRY(hipEventRecord(b->ev[ev++], q));
@@ -1617,11 +1671,11 @@ static int run_1d(nra_batch* b)
             else if (bk.half)
                 LAUNCH_TRY(nra_launch_sweep_ring32_bwd(bk.R, b->has_n, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off,
                                                        b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp,
-                                                       b->kmin.p, b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p));
+                                                       b->kmin.p, b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p, relax_c, redo));
             else if (bk.ring)
                 LAUNCH_TRY(nra_launch_sweep_ring_bwd(bk.R, b->has_n, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off,
                                                      b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp,
-                                                     b->kmin.p, b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p));
+                                                     b->kmin.p, b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p, relax_c, redo));
             else
                 LAUNCH_TRY(nra_launch_sweep_bwd(bk.R, b->has_n, bk.chain ? 1 : 0, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off,
                                                 b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp,
@@ -1653,18 +1707,19 @@ static int run_1d(nra_batch* b)
                 LAUNCH_TRY(nra_launch_sweep_ring32_fwd(bk.R, b->has_n, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off,
                                                        b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp,
                                                        b->kmin.p, b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p,
-                                                       b->cand_score.p, b->cand_flag.p));
+                                                       b->cand_score.p, b->cand_flag.p, relax_c, redo));
             else if (bk.ring)
                 LAUNCH_TRY(nra_launch_sweep_ring_fwd(bk.R, b->has_n, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off,
                                                      b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp,
                                                      b->kmin.p, b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p,
-                                                     b->cand_score.p, b->cand_flag.p));
+                                                     b->cand_score.p, b->cand_flag.p, relax_c, redo));
             else
                 LAUNCH_TRY(nra_launch_sweep_fwd(bk.R, b->has_n, bk.chain ? 1 : 0, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off,
                                                 b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp,
                                                 b->kmin.p, b->kmax.p, b->coff.p, b->snap.p,
                                                 b->read_a1d.p, b->cand_score.p, b->cand_flag.p,
                                                 strips, b->chain_cap, bk.n_strips));
+            if (bk.taint) LAUNCH_TRY(resweep(bk, q, redo));
             HIP_TRY(hipEventRecord(b->ev[ev++], q));
             b->n_score_ev += 2;
             HIP_TRY(hipEventRecord(b->bdone[i], q));
@@ -3627,6 +3682,31 @@ int nra_batch_sync(nra_batch_t* b)
     const int rc = account_run(b);
     if (rc || b->kind != 1) return rc;
     return check_mt(b);
+}
+
+int nra_batch1d_resweeps(nra_batch_t* b, int64_t* tasks, int64_t* reads, int64_t* tasks_total, int64_t* reads_total)
+{
+    if (!b || b->kind != 1) return fail(NRA_E_ARG, "nra_batch1d_resweeps needs a 1D batch");
+    int64_t nt = 0, nr = 0, tt = 0, tr = 0;
+    if (b->redo.n > 0) {
+        HIP_TRY(hipSetDevice(b->device));
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        std::vector<int32_t> f(b->redo.n);
+        HIP_TRY(hipMemcpy(f.data(), b->redo.p, f.size() * 4, hipMemcpyDeviceToHost));
+        for (const Bucket& bk : b->buckets) {
+            if (!bk.taint) continue;
+            for (int t = 0; t < bk.n_sweep; ++t) {
+                const size_t i = bk.sweep_off + (size_t)t;
+                tt += 1; tr += b->task_reads[i];
+                if (f[i]) { nt += 1; nr += b->task_reads[i]; }
+            }
+        }
+    }
+    if (tasks) *tasks = nt;
+    if (reads) *reads = nr;
+    if (tasks_total) *tasks_total = tt;
+    if (reads_total) *reads_total = tr;
+    return NRA_OK;
 }
 
 int nra_batch_stats(nra_batch_t* b, nra_stats_t* st)

@@ -17,6 +17,10 @@
 //   2048 - 2 * (gap open 2 + a mismatch) ~ 1990, "minus infinity" is NEGB and survives one subtraction of a
 //   gap extension (host: nra_host.cpp keeps doubled scores <= 27000 in these cells and sends scoring
 //   schemes that do not fit the bounds to the brute-force kernel).
+//   The taint scheme of the LDS-ring sweeps (SC = 4, DESIGN §4.1: 4 * score + 2 * taint + origin) quadruples
+//   every score: the same bounds hold as long as QUADRUPLED scores stay <= 27000 (reads of the ring kernels are
+//   <= 3072 bases: 4 * 2 * 3072 = 24576 with the default match score) and 4 * (gap open 2 + a mismatch + N
+//   score) <= 700 (nra_host.cpp sends every other scheme to today's doubled cells).
 #define BIAS 2048
 #define NEGB 1280                     // biased "minus infinity": below any real state, >= 0x0400 after - ext
 
@@ -85,6 +89,34 @@ __device__ __forceinline__ void sweep_cell(int (&Hq)[R], int (&Hq2)[R], int (&E)
         Hq2[i] = hq2;
         F = FF ? mx3<W>(F - v_e1, hq, v_floor) : mx2<W>(F - v_e1, hq);
         F2 = mx2<W>(F2 - v_e2, hq2);
+        d = d_next;
+    }
+}
+
+// The relaxed cell of the taint scheme (packed int16, FF form): ONE affine gap state per direction with open o1 and
+// extension v_er = min(e1, e2) (the host takes it only where o1 <= o2, so o1 = min(o1, o2) and the substitution table
+// of the exact cell serves unchanged).  A gap of length l costs o1 + (l-1) min(e1, e2) <= either piece, so
+// E >= E1, E2, F >= F1, F2 and H >= the two-piece H: an upper bound of every exact state.  The caller feeds tainted
+// floors, so every value it produces carries the taint bit.  8.5 instructions per cell pair against 14.5.
+template <int R>
+__device__ __forceinline__ void sweep_cell_relaxed(int (&Hq)[R], int (&E)[R], const int (&qc)[R], int diag, int& F, int& M,
+                                                   int tbl, int tbl_hi, int v_floor, int v_er, int v_o1)
+{
+    int d = diag + (int)__builtin_amdgcn_perm(tbl_hi, tbl, qc[0]);
+    int h_prev = 0;
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        int d_next = d;
+        if (i + 1 < R) d_next = Hq[i] + (int)__builtin_amdgcn_perm(tbl_hi, tbl, qc[i + 1]);
+        const int ein = pmaxi(E[i] - v_er, Hq[i]);
+        const int h = pmax3(d, ein, F);
+        if (i & 1) M = pmax3(M, h_prev, h);
+        else if (i == R - 1) M = pmaxi(M, h);
+        else h_prev = h;
+        E[i] = ein;
+        const int hq = h - v_o1;
+        Hq[i] = hq;
+        F = pmax3(F - v_er, hq, v_floor);
         d = d_next;
     }
 }

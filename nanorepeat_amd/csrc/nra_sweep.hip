@@ -514,7 +514,35 @@ __device__ __forceinline__ SweepCounters sweep_counters_at(int s, int jfirst, in
     return c;
 }
 
-template <int R, bool HAS_N, int DIR, bool COMB, bool QUANTA>
+// The taint scheme (TAINT): cells hold 4 * score + 2 * taint + origin.  Steps [0, s_relax) of a sweep run
+// the relaxed cell (nra_pk16.h), whose every value is a tainted upper bound; from step s_relax on the exact cell runs,
+// seeded from the relaxed states.  s_relax is a multiple of 64 at or below flank - c (c: the host's margin, >= 64), the
+// same for every lane: lane l is exact from column s_relax - skew * l on.  0: no relaxed step (the anchor is too short).
+__device__ __forceinline__ int sweep_relax_steps(int flank, int c)
+{
+    if (c <= 0) return 0;
+    const int t = flank - (c < 64 ? 64 : c);
+    return t >= 64 ? t / 64 * 64 : 0;
+}
+// the switch to the exact cell: E2 := E (E_r >= E1, E2), Hq2 := Hq - (o2 - o1) (H_r - o2 >= H - o2); F2 arrives as F on the ring
+template <int R>
+__device__ __forceinline__ void sweep_relax_switch(const int (&Hq)[R], int (&Hq2)[R], const int (&E)[R], int (&E2)[R], int v_do)
+{
+#pragma unroll
+    for (int i = 0; i < R; ++i) { E2[i] = E[i]; Hq2[i] = Hq[i] - v_do; }
+}
+// the reverse sweep's junction rows: any tainted one sends the task to the exact re-sweep (the combine adds two
+// biased states, and two taint bits would carry into the score)
+template <int R>
+__device__ __forceinline__ void sweep_rside_taint(const int (&Hq)[R], const int (&E)[R], const int (&E2)[R], int T2, int32_t* flag)
+{
+    int t = 0;
+#pragma unroll
+    for (int i = 0; i < R; ++i) t |= Hq[i] | E[i] | E2[i];
+    if (t & T2) *flag = 1;
+}
+
+template <int R, bool HAS_N, int DIR, bool COMB, bool QUANTA, bool TAINT = false>
 __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, int4* ring, int2* racc,
                                                 const NraSweepTask* __restrict__ tasks,
                                                 const NraDevRead* __restrict__ reads,
@@ -531,10 +559,11 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
                                                 int32_t* __restrict__ cand_score,
                                                 uint8_t* __restrict__ cand_flag,
                                                 int32_t* __restrict__ qs, const int s_begin, const int s_end,
-                                                const bool load, const bool store)
+                                                const bool load, const bool store, const int relax_c = 0,
+                                                int32_t* __restrict__ redo = nullptr)
 {
     static_assert(DIR == 1 || !COMB, "only a forward sweep meets unit boundaries");
-    constexpr int SC = 2;                 // origin-bit scheme: doubled scores
+    constexpr int SC = TAINT ? 4 : 2;     // origin-bit scheme: doubled scores; TAINT: 4 * score + 2 * taint + origin
     const NraSweepTask tk = tasks[task];
     const bool has_b = tk.read_b >= 0;
     const int ra = tk.read_a, rb = has_b ? tk.read_b : tk.read_a;
@@ -559,6 +588,10 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
     const int s_match = SC * sp.match + o1, s_mis = o1 - SC * sp.mismatch, s_ambi = o1 - SC * sp.ambi;
     const int tbl_hi = s_mis | (s_ambi << 8);
     const int tbl_mis4 = s_mis * 0x01010101, tbl_ambi4 = s_ambi * 0x01010101;
+    // the taint scheme: the steps [0, s_relax) run the relaxed cell; T2 = the taint bit of both halves
+    const int s_relax = TAINT ? sweep_relax_steps(flank, relax_c) : 0;
+    const int T2 = 2 * P1;
+    constexpr int SH = TAINT ? 2 : 1;     // score = state >> SH
 
     // the substitution table (+ flags) of template column `col`; padding outside the template
     auto column_table = [&](int col) {
@@ -624,7 +657,7 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
     }
     int Hq[R], Hq2[R], E[R], E2[R];
 #pragma unroll
-    for (int i = 0; i < R; ++i) { Hq[i] = v_floor; Hq2[i] = NEG1; E[i] = NEG1; E2[i] = NEG1; }
+    for (int i = 0; i < R; ++i) { Hq[i] = s_relax > 0 ? v_floor | T2 : v_floor; Hq2[i] = NEG1; E[i] = NEG1; E2[i] = NEG1; }
 
     // ring: padding columns everywhere, then lane 0's first `skew` columns
 #pragma unroll
@@ -633,7 +666,7 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
     if (lane < skew) ring[lane * 64] = make_int4(v_floor, NEG1, NEG1, column_table(lane));
     ring_order();
 
-    int Hup_prev = v_floor, M = BIAS * P1;
+    int Hup_prev = s_relax > 0 ? v_floor | T2 : v_floor, M = BIAS * P1;      // (tainted, as Hq: the diagonal into row 0)
     int feed = tbl_mis4;
     const int nsteps = ncols + 63 * skew;                   // lane 63 finishes the last column at step ncols - 1 + 63*skew
     const int wr = (lane + 1) & 63;
@@ -650,8 +683,30 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
     int phase = jfirst % m;                                 // boundary steps: step mod m == phase, step >= jfirst
     int pcnt = QUANTA ? s0 % m : 0;                         // step mod m
     int bidx = QUANTA ? sweep_counters_at(s0, jfirst, m, tk.kmin, tk.kmax, 63, 64).bidx : 0;      // boundary steps so far
+    int sx = s0;                                            // the first step of the exact cell
+    if (TAINT && s0 < s_relax) {
+        // the relaxed steps: columns of the anchor far from the junction (no boundary, snapshot or table flag among
+        // them: s_relax <= flank - 64); one gap state per direction, F in both places of the hand-off
+        sx = s1 < s_relax ? s1 : s_relax;
+        const int flr = BIAS * P1 | T2, hfl = flr - v_o1, v_er = SC * imin(sp.ext1, sp.ext2) * P1;
 #pragma unroll 1
-    for (int step = s0; step < s1; ++step) {
+        for (int step = s0; step < sx; ++step) {
+            if ((step & 63) == 0) feed = column_table(step + skew + wr);
+            const int4 in = ring[slot * 64 + lane];
+            int F = pmaxi(in.y, flr);
+            sweep_cell_relaxed<R>(Hq, E, qc, Hup_prev, F, M, in.w, tbl_hi, flr, v_er, v_o1);
+            Hup_prev = pmaxi(in.x, hfl);
+            ring[slot * 64 + wr] = make_int4(Hq[R - 1], F, F, in.w);
+            if (lane == 63) ring[slot * 64] = make_int4(v_floor, NEG1, NEG1, feed);
+            ring_order();
+            feed = dpp_rol1(feed);
+            if (++slot == skew) slot = 0;
+        }
+        pcnt = sx % m;
+    }
+    if (TAINT && sx == s_relax && sx < s1) sweep_relax_switch<R>(Hq, Hq2, E, E2, v_o2 - v_o1);
+#pragma unroll 1
+    for (int step = sx; step < s1; ++step) {
         if ((step & 63) == 0) feed = column_table(step + skew + wr);      // lane 63 hands out column step + skew
         const int4 in = ring[slot * 64 + lane];
         const int tt = in.w;
@@ -668,7 +723,10 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
         if (++slot == skew) slot = 0;
 
         if constexpr (DIR == 0) {
-            if (tt & FLAG_SNAPSHOT) sweep_snapshot<0, R, R>(Hq, E, E2, snap_task, lane);
+            if (tt & FLAG_SNAPSHOT) {
+                sweep_snapshot<0, R, R>(Hq, E, E2, snap_task, lane);
+                if (TAINT) sweep_rside_taint<R>(Hq, E, E2, T2, redo + task);
+            }
         } else if constexpr (COMB) {
             if (pcnt == phase && step >= jfirst) {          // every lane is on a unit boundary: wave-uniform
                 const int tS = sweep_combine<0, R, R, false, PARK>(Hq, E, E2, Hbo, Ebo, E2bo, NEG2);
@@ -687,10 +745,11 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
                             const int lo = sp.min_score > 1 ? sp.min_score : 1;
                             // packed 2*score + origin bit; an alignment inside R starts at a column >= |L|
                             const int V = imax(imax(S, B), (s2 ? a_of_b : a_of_a) + 1);
-                            const int best = V >> 1;
+                            const int best = V >> SH;
                             int flag = 1;
                             if (V & 1) flag = 0;                                  // an optimal alignment starts at >= |L|
-                            else if ((B >> 1) >= best) flag = ((S >> 1) >= best) ? 2 : 0;
+                            else if ((B >> SH) >= best) flag = ((S >> SH) >= best) ? 2 : 0;
+                            if (TAINT && (V & 2)) redo[task] = 1;                 // a relaxed cell is on a winning path
                             const int v = ((best >= lo ? best : -1) << 2) | flag;
                             if (s2) vb = v; else va = v;
                         }
@@ -721,7 +780,9 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
     }
 }
 
-template <int R, bool HAS_N, int DIR>
+// relax_c, redo: TAINT -- the margin c of the relaxed steps, and the per-task flags the sweep sets where a relaxed cell
+// may have reached an output; otherwise, redo non-null: the exact re-sweep of the flagged tasks only (the others leave)
+template <int R, bool HAS_N, int DIR, bool TAINT>
 __global__ __launch_bounds__(WAVE * SWEEP_RING_WPB) void k_sweep_ring(int n_tasks, const NraSweepTask* __restrict__ tasks,
                                                      const NraDevRead* __restrict__ reads,
                                                      const NraDevRegion* __restrict__ regions,
@@ -735,7 +796,7 @@ __global__ __launch_bounds__(WAVE * SWEEP_RING_WPB) void k_sweep_ring(int n_task
                                                      int32_t* __restrict__ snap,
                                                      int32_t* __restrict__ read_a,
                                                      int32_t* __restrict__ cand_score,
-                                                     uint8_t* __restrict__ cand_flag)
+                                                     uint8_t* __restrict__ cand_flag, int relax_c, int32_t* __restrict__ redo)
 {
     __shared__ int4 ring_all[SWEEP_RING_WPB * SWEEP_RING_D * 64];
     __shared__ int2 racc_all[SWEEP_RING_WPB * 64];
@@ -745,9 +806,11 @@ __global__ __launch_bounds__(WAVE * SWEEP_RING_WPB) void k_sweep_ring(int n_task
     int2* racc = racc_all + wave_in_block * 64;
     const int task = blockIdx.x * SWEEP_RING_WPB + wave_in_block;
     if (task >= n_tasks) return;
+    if (!TAINT && redo && redo[task] == 0) return;
     const int lane = SWEEP_RING_WPB > 1 ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
-    sweep_ring_body<R, HAS_N, DIR, DIR == 1, false>(task, lane, ring, racc, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin_arr, kmax_arr,
-                                                    coff, snap, read_a, cand_score, cand_flag, nullptr, 0, 0, false, false);
+    sweep_ring_body<R, HAS_N, DIR, DIR == 1, false, TAINT>(task, lane, ring, racc, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin_arr,
+                                                           kmax_arr, coff, snap, read_a, cand_score, cand_flag, nullptr, 0, 0, false, false,
+                                                           relax_c, redo);
 }
 
 // ------------------------------------------------------------------------------------
@@ -759,7 +822,7 @@ __global__ __launch_bounds__(WAVE * SWEEP_RING_WPB) void k_sweep_ring(int n_task
 // template (same region, the union of the four reads' windows) in lock step, each with its own ring
 // (lane 31 hands out what enters lane 0, lane 63 what enters lane 32), so the overhead is paid once for four
 // reads and the pipeline is 32*skew columns deep.
-template <int R, bool HAS_N, int DIR, bool COMB, bool QUANTA>          // COMB, QUANTA and the last four arguments as in sweep_ring_body
+template <int R, bool HAS_N, int DIR, bool COMB, bool QUANTA, bool TAINT = false>   // COMB, QUANTA, TAINT and the arguments after cand_flag as in sweep_ring_body
 __device__ __forceinline__ void sweep_ring32_body(const int task, const int lane, int4* ring, int2* racc,
                                                   const NraSweepTask* __restrict__ tasks,
                                                   const NraDevRead* __restrict__ reads,
@@ -776,10 +839,11 @@ __device__ __forceinline__ void sweep_ring32_body(const int task, const int lane
                                                   int32_t* __restrict__ cand_score,
                                                   uint8_t* __restrict__ cand_flag,
                                                   int32_t* __restrict__ qs, const int s_begin, const int s_end,
-                                                  const bool load, const bool store)
+                                                  const bool load, const bool store, const int relax_c = 0,
+                                                  int32_t* __restrict__ redo = nullptr)
 {
     static_assert(DIR == 1 || !COMB, "only a forward sweep meets unit boundaries");
-    constexpr int SC = 2;
+    constexpr int SC = TAINT ? 4 : 2;
     const int hoff = lane & 32;                           // first lane of this lane's half
     const int hl = lane & 31;                             // lane within the half
     const NraSweepTask tk = tasks[task];
@@ -810,6 +874,9 @@ __device__ __forceinline__ void sweep_ring32_body(const int task, const int lane
     const int s_match = SC * sp.match + o1, s_mis = o1 - SC * sp.mismatch, s_ambi = o1 - SC * sp.ambi;
     const int tbl_hi = s_mis | (s_ambi << 8);
     const int tbl_mis4 = s_mis * 0x01010101, tbl_ambi4 = s_ambi * 0x01010101;
+    const int s_relax = TAINT ? sweep_relax_steps(flank, relax_c) : 0;      // as in sweep_ring_body
+    const int T2 = 2 * P1;
+    constexpr int SH = TAINT ? 2 : 1;
 
     auto column_table = [&](int col) {
         int t = tbl_mis4;
@@ -876,7 +943,7 @@ __device__ __forceinline__ void sweep_ring32_body(const int task, const int lane
     }
     int Hq[R], Hq2[R], E[R], E2[R];
 #pragma unroll
-    for (int i = 0; i < R; ++i) { Hq[i] = v_floor; Hq2[i] = NEG1; E[i] = NEG1; E2[i] = NEG1; }
+    for (int i = 0; i < R; ++i) { Hq[i] = s_relax > 0 ? v_floor | T2 : v_floor; Hq2[i] = NEG1; E[i] = NEG1; E2[i] = NEG1; }
 
 #pragma unroll
     for (int s = 0; s < SWEEP_RING_D; ++s) ring[s * 64 + lane] = make_int4(v_floor, NEG1, NEG1, tbl_mis4);
@@ -884,7 +951,7 @@ __device__ __forceinline__ void sweep_ring32_body(const int task, const int lane
     if (hl < skew) ring[hl * 64 + hoff] = make_int4(v_floor, NEG1, NEG1, column_table(hl));
     ring_order();
 
-    int Hup_prev = v_floor, M = BIAS * P1;
+    int Hup_prev = s_relax > 0 ? v_floor | T2 : v_floor, M = BIAS * P1;
     int feed = tbl_mis4;
     const int nsteps = ncols + 31 * skew;                   // lanes 31 / 63 finish the last column at step ncols - 1 + 31*skew
     const int wr = hoff | ((hl + 1) & 31);
@@ -900,8 +967,28 @@ __device__ __forceinline__ void sweep_ring32_body(const int task, const int lane
     int phase = jfirst % m;
     int pcnt = QUANTA ? s0 % m : 0;
     int bidx = QUANTA ? sweep_counters_at(s0, jfirst, m, tk.kmin, tk.kmax, 31, 32).bidx : 0;
+    int sx = s0;                                            // the relaxed steps as in sweep_ring_body
+    if (TAINT && s0 < s_relax) {
+        sx = s1 < s_relax ? s1 : s_relax;
+        const int flr = BIAS * P1 | T2, hfl = flr - v_o1, v_er = SC * imin(sp.ext1, sp.ext2) * P1;
 #pragma unroll 1
-    for (int step = s0; step < s1; ++step) {
+        for (int step = s0; step < sx; ++step) {
+            if ((step & 31) == 0) feed = column_table(step + skew + ((hl + 1) & 31));
+            const int4 in = ring[slot * 64 + lane];
+            int F = pmaxi(in.y, flr);
+            sweep_cell_relaxed<R>(Hq, E, qc, Hup_prev, F, M, in.w, tbl_hi, flr, v_er, v_o1);
+            Hup_prev = pmaxi(in.x, hfl);
+            ring[slot * 64 + wr] = make_int4(Hq[R - 1], F, F, in.w);
+            if (hl == 31) ring[slot * 64 + hoff] = make_int4(v_floor, NEG1, NEG1, feed);
+            ring_order();
+            feed = dpp_rol1(feed);
+            if (++slot == skew) slot = 0;
+        }
+        pcnt = sx % m;
+    }
+    if (TAINT && sx == s_relax && sx < s1) sweep_relax_switch<R>(Hq, Hq2, E, E2, v_o2 - v_o1);
+#pragma unroll 1
+    for (int step = sx; step < s1; ++step) {
         // both halves sweep the same template: the column tables repeat with period 32 across the wave, and a
         // full-wave rotation keeps them so
         if ((step & 31) == 0) feed = column_table(step + skew + ((hl + 1) & 31));
@@ -918,7 +1005,10 @@ __device__ __forceinline__ void sweep_ring32_body(const int task, const int lane
         if (++slot == skew) slot = 0;
 
         if constexpr (DIR == 0) {
-            if (tt & FLAG_SNAPSHOT) sweep_snapshot_lane<R>(Hq, E, E2, snap_task + (size_t)lane * NRA_SNAP_LANE_STRIDE(R));
+            if (tt & FLAG_SNAPSHOT) {
+                sweep_snapshot_lane<R>(Hq, E, E2, snap_task + (size_t)lane * NRA_SNAP_LANE_STRIDE(R));
+                if (TAINT) sweep_rside_taint<R>(Hq, E, E2, T2, redo + task);
+            }
         } else if constexpr (COMB) {
             if (pcnt == phase && step >= jfirst) {          // every lane is on a unit boundary: wave-uniform
                 const int tS = sweep_combine<0, R, R>(Hq, E, E2, Hbo, Ebo, E2bo, NEG2);
@@ -936,10 +1026,11 @@ __device__ __forceinline__ void sweep_ring32_body(const int task, const int lane
                             const int S = (s2 ? half_hi(accS) : half_lo(accS)) - 2 * BIAS;
                             const int lo = sp.min_score > 1 ? sp.min_score : 1;
                             const int V = imax(imax(S, B), (s2 ? a_of_b : a_of_a) + 1);
-                            const int best = V >> 1;
+                            const int best = V >> SH;
                             int flag = 1;
                             if (V & 1) flag = 0;
-                            else if ((B >> 1) >= best) flag = ((S >> 1) >= best) ? 2 : 0;
+                            else if ((B >> SH) >= best) flag = ((S >> SH) >= best) ? 2 : 0;
+                            if (TAINT && (V & 2)) redo[task] = 1;
                             const int v = ((best >= lo ? best : -1) << 2) | flag;
                             if (s2) vb = v; else va = v;
                         }
@@ -970,7 +1061,7 @@ __device__ __forceinline__ void sweep_ring32_body(const int task, const int lane
     }
 }
 
-template <int R, bool HAS_N, int DIR>
+template <int R, bool HAS_N, int DIR, bool TAINT>                     // relax_c, redo as in k_sweep_ring
 __global__ __launch_bounds__(WAVE) void k_sweep_ring32(int n_tasks, const NraSweepTask* __restrict__ tasks,
                                                        const NraDevRead* __restrict__ reads,
                                                        const NraDevRegion* __restrict__ regions,
@@ -984,14 +1075,16 @@ __global__ __launch_bounds__(WAVE) void k_sweep_ring32(int n_tasks, const NraSwe
                                                        int32_t* __restrict__ snap,
                                                        int32_t* __restrict__ read_a,
                                                        int32_t* __restrict__ cand_score,
-                                                       uint8_t* __restrict__ cand_flag)
+                                                       uint8_t* __restrict__ cand_flag, int relax_c, int32_t* __restrict__ redo)
 {
     __shared__ int4 ring[SWEEP_RING_D * 64];
     __shared__ int2 racc[64];
     const int task = blockIdx.x;
     if (task >= n_tasks) return;
-    sweep_ring32_body<R, HAS_N, DIR, DIR == 1, false>(task, (int)threadIdx.x, ring, racc, tasks, reads, regions, pool, q2bit, qnmask, sp,
-                                                      kmin_arr, kmax_arr, coff, snap, read_a, cand_score, cand_flag, nullptr, 0, 0, false, false);
+    if (!TAINT && redo && redo[task] == 0) return;
+    sweep_ring32_body<R, HAS_N, DIR, DIR == 1, false, TAINT>(task, (int)threadIdx.x, ring, racc, tasks, reads, regions, pool, q2bit, qnmask,
+                                                             sp, kmin_arr, kmax_arr, coff, snap, read_a, cand_score, cand_flag, nullptr, 0,
+                                                             0, false, false, relax_c, redo);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1014,7 +1107,7 @@ __global__ __launch_bounds__(WAVE) void k_sweep_ring32(int n_tasks, const NraSwe
 //   * a cut costs no step: the dumped state is the skewed wave state, the pipeline is not drained.
 // A forward part that ends before the first boundary step (the columns of L) runs the plain body: no junction input, no combine.
 // (as real function calls -- noinline -- the bodies cost the calling convention's register reserve: 248 at R = 15)
-template <int R, bool HAS_N, bool HALF, int DIR, bool COMB>
+template <int R, bool HAS_N, bool HALF, int DIR, bool COMB, bool TAINT>
 __device__ __forceinline__ void sweep_quantum(const int task, const int lane, int4* ring, int2* racc,
                                                         const NraSweepTask* __restrict__ tasks,
                                                         const NraDevRead* __restrict__ reads,
@@ -1031,12 +1124,14 @@ __device__ __forceinline__ void sweep_quantum(const int task, const int lane, in
                                                         int32_t* __restrict__ cand_score,
                                                         uint8_t* __restrict__ cand_flag,
                                                         int32_t* __restrict__ qs, const int s_begin, const int s_end,
-                                                        const bool load, const bool store)
+                                                        const bool load, const bool store, const int relax_c, int32_t* __restrict__ redo)
 {
-    if (HALF) sweep_ring32_body<R, HAS_N, DIR, COMB, true>(task, lane, ring, racc, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin_arr,
-                                                           kmax_arr, coff, snap, read_a, cand_score, cand_flag, qs, s_begin, s_end, load, store);
-    else sweep_ring_body<R, HAS_N, DIR, COMB, true>(task, lane, ring, racc, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin_arr, kmax_arr,
-                                                    coff, snap, read_a, cand_score, cand_flag, qs, s_begin, s_end, load, store);
+    if (HALF) sweep_ring32_body<R, HAS_N, DIR, COMB, true, TAINT>(task, lane, ring, racc, tasks, reads, regions, pool, q2bit, qnmask, sp,
+                                                                  kmin_arr, kmax_arr, coff, snap, read_a, cand_score, cand_flag, qs,
+                                                                  s_begin, s_end, load, store, relax_c, redo);
+    else sweep_ring_body<R, HAS_N, DIR, COMB, true, TAINT>(task, lane, ring, racc, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin_arr,
+                                                           kmax_arr, coff, snap, read_a, cand_score, cand_flag, qs, s_begin, s_end, load,
+                                                           store, relax_c, redo);
 }
 
 // (waves per SIMD as the forward sweep alone: without the hint the merged body takes 226 registers at R = 15 where
@@ -1048,7 +1143,7 @@ constexpr int ringq_waves(int R)
     return w < 1 ? 1 : (w > 8 ? 8 : w);
 }
 
-template <int R, bool HAS_N, bool HALF>
+template <int R, bool HAS_N, bool HALF, bool TAINT>                  // relax_c, redo: TAINT as in k_sweep_ring
 __global__ __launch_bounds__(WAVE, ringq_waves(R)) void k_sweep_ringq(int n_quanta, const uint32_t* __restrict__ qlist, int qsteps, int n_tasks,
                                                       int32_t* ticket, int32_t* arrivals, int32_t* giveup,
                                                       int32_t* __restrict__ qstate,
@@ -1065,7 +1160,7 @@ __global__ __launch_bounds__(WAVE, ringq_waves(R)) void k_sweep_ringq(int n_quan
                                                       int32_t* __restrict__ snap,
                                                       int32_t* __restrict__ read_a,
                                                       int32_t* __restrict__ cand_score,
-                                                      uint8_t* __restrict__ cand_flag)
+                                                      uint8_t* __restrict__ cand_flag, int relax_c, int32_t* __restrict__ redo)
 {
     __shared__ int4 ring[SWEEP_RING_D * 64];
     __shared__ int2 racc[64];
@@ -1115,10 +1210,10 @@ __global__ __launch_bounds__(WAVE, ringq_waves(R)) void k_sweep_ringq(int n_quan
     }
     // a slot per forward sweep, then -- where a reverse sweep has more than one part -- one per reverse sweep
     int32_t* __restrict__ qs = qstate + ((size_t)(dir ? 0 : n_tasks) + (size_t)task) * (NRA_QSTATE_INTS(R) * 64);
-#define NRA_Q_ARGS task, lane, ring, racc, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin_arr, kmax_arr, coff, snap, read_a, cand_score, cand_flag, qs, s_begin, s_end, load, store
-    if (!dir) sweep_quantum<R, HAS_N, HALF, 0, false>(NRA_Q_ARGS);
-    else if (!comb) sweep_quantum<R, HAS_N, HALF, 1, false>(NRA_Q_ARGS);
-    else sweep_quantum<R, HAS_N, HALF, 1, true>(NRA_Q_ARGS);
+#define NRA_Q_ARGS task, lane, ring, racc, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin_arr, kmax_arr, coff, snap, read_a, cand_score, cand_flag, qs, s_begin, s_end, load, store, relax_c, redo
+    if (!dir) sweep_quantum<R, HAS_N, HALF, 0, false, TAINT>(NRA_Q_ARGS);
+    else if (!comb) sweep_quantum<R, HAS_N, HALF, 1, false, TAINT>(NRA_Q_ARGS);
+    else sweep_quantum<R, HAS_N, HALF, 1, true, TAINT>(NRA_Q_ARGS);
 #undef NRA_Q_ARGS
     // everything this wave stored -- the wave state at the cut, or the R side's snapshot and A -- before the arrival
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -1708,14 +1803,17 @@ static int launch_sweep_ring(int R, int has_n, hipStream_t st, int n_tasks, cons
                              const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
                              const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
                              const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                             int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag)
+                             int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo)
 {
     if (n_tasks <= 0) return 0;
-#define ARGS n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag
-#define CASE(r)                                                                          \
-    case r:                                                                              \
-        if (has_n) k_sweep_ring<r, true, DIR><<<(n_tasks + SWEEP_RING_WPB - 1) / SWEEP_RING_WPB, WAVE * SWEEP_RING_WPB, 0, st>>>(ARGS); \
-        else k_sweep_ring<r, false, DIR><<<(n_tasks + SWEEP_RING_WPB - 1) / SWEEP_RING_WPB, WAVE * SWEEP_RING_WPB, 0, st>>>(ARGS);      \
+    const int grid = (n_tasks + SWEEP_RING_WPB - 1) / SWEEP_RING_WPB;
+#define ARGS n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag, relax_c, redo
+#define CASE(r)                                                                                          \
+    case r:                                                                                              \
+        if (relax_c > 0) { if (has_n) k_sweep_ring<r, true, DIR, true><<<grid, WAVE * SWEEP_RING_WPB, 0, st>>>(ARGS);      \
+                           else k_sweep_ring<r, false, DIR, true><<<grid, WAVE * SWEEP_RING_WPB, 0, st>>>(ARGS); }          \
+        else { if (has_n) k_sweep_ring<r, true, DIR, false><<<grid, WAVE * SWEEP_RING_WPB, 0, st>>>(ARGS);                  \
+               else k_sweep_ring<r, false, DIR, false><<<grid, WAVE * SWEEP_RING_WPB, 0, st>>>(ARGS); }                     \
         break;
     switch (R) {
         NRA_R_LIST(CASE)
@@ -1731,10 +1829,10 @@ extern "C" int nra_launch_sweep_ring_bwd(int R, int has_n, hipStream_t st, int n
                                          const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
                                          const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
                                          const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                         int32_t* snap, int32_t* read_a)
+                                         int32_t* snap, int32_t* read_a, int relax_c, int32_t* redo)
 {
     return launch_sweep_ring<0>(R, has_n, st, n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax,
-                                coff, snap, read_a, nullptr, nullptr);
+                                coff, snap, read_a, nullptr, nullptr, relax_c, redo);
 }
 #endif
 #if NRA_HAS_PART(12)
@@ -1742,10 +1840,11 @@ extern "C" int nra_launch_sweep_ring_fwd(int R, int has_n, hipStream_t st, int n
                                          const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
                                          const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
                                          const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                         int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag)
+                                         int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag,
+                                         int relax_c, int32_t* redo)
 {
     return launch_sweep_ring<1>(R, has_n, st, n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax,
-                                coff, snap, read_a, cand_score, cand_flag);
+                                coff, snap, read_a, cand_score, cand_flag, relax_c, redo);
 }
 #endif
 
@@ -1780,14 +1879,16 @@ static int launch_sweep_ring32(int R, int has_n, hipStream_t st, int n_tasks, co
                                const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
                                const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
                                const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                               int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag)
+                               int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo)
 {
     if (n_tasks <= 0) return 0;
-#define ARGS n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag
-#define CASE(r)                                                                          \
-    case r:                                                                              \
-        if (has_n) k_sweep_ring32<r, true, DIR><<<n_tasks, WAVE, 0, st>>>(ARGS);         \
-        else k_sweep_ring32<r, false, DIR><<<n_tasks, WAVE, 0, st>>>(ARGS);              \
+#define ARGS n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag, relax_c, redo
+#define CASE(r)                                                                                                  \
+    case r:                                                                                                      \
+        if (relax_c > 0) { if (has_n) k_sweep_ring32<r, true, DIR, true><<<n_tasks, WAVE, 0, st>>>(ARGS);       \
+                           else k_sweep_ring32<r, false, DIR, true><<<n_tasks, WAVE, 0, st>>>(ARGS); }           \
+        else { if (has_n) k_sweep_ring32<r, true, DIR, false><<<n_tasks, WAVE, 0, st>>>(ARGS);                   \
+               else k_sweep_ring32<r, false, DIR, false><<<n_tasks, WAVE, 0, st>>>(ARGS); }                      \
         break;
     switch (R) {
         CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13)
@@ -1800,20 +1901,22 @@ static int launch_sweep_ring32(int R, int has_n, hipStream_t st, int n_tasks, co
 }
 
 // k_sweep_ringq launchers: `half` = the half-wave kernel's buckets (two read pairs per wave, R <= NRA_RING32_MAX_R)
-#define NRA_Q_LAUNCH_ARGS n_quanta, qlist, qsteps, n_tasks, ticket, arrivals, giveup, qstate, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag
+#define NRA_Q_LAUNCH_ARGS n_quanta, qlist, qsteps, n_tasks, ticket, arrivals, giveup, qstate, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag, relax_c, redo
 #if NRA_HAS_PART(25)
 extern "C" int nra_launch_sweep_ringq(int R, int has_n, hipStream_t st, int n_quanta, const uint32_t* qlist, int qsteps, int n_tasks, int32_t* ticket,
                                       int32_t* arrivals, int32_t* giveup, int32_t* qstate, const NraSweepTask* tasks,
                                       const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
                                       const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
                                       const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                      int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag)
+                                      int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo)
 {
     if (n_quanta <= 0) return 0;
-#define CASE(r)                                                                                          \
-    case r:                                                                                              \
-        if (has_n) k_sweep_ringq<r, true, false><<<n_quanta, WAVE, 0, st>>>(NRA_Q_LAUNCH_ARGS);          \
-        else k_sweep_ringq<r, false, false><<<n_quanta, WAVE, 0, st>>>(NRA_Q_LAUNCH_ARGS);               \
+#define CASE(r)                                                                                                          \
+    case r:                                                                                                              \
+        if (relax_c > 0) { if (has_n) k_sweep_ringq<r, true, false, true><<<n_quanta, WAVE, 0, st>>>(NRA_Q_LAUNCH_ARGS); \
+                           else k_sweep_ringq<r, false, false, true><<<n_quanta, WAVE, 0, st>>>(NRA_Q_LAUNCH_ARGS); }    \
+        else { if (has_n) k_sweep_ringq<r, true, false, false><<<n_quanta, WAVE, 0, st>>>(NRA_Q_LAUNCH_ARGS);            \
+               else k_sweep_ringq<r, false, false, false><<<n_quanta, WAVE, 0, st>>>(NRA_Q_LAUNCH_ARGS); }               \
         break;
     switch (R) {
         NRA_R_LIST(CASE)
@@ -1829,13 +1932,15 @@ extern "C" int nra_launch_sweep_ringq32(int R, int has_n, hipStream_t st, int n_
                                         const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
                                         const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
                                         const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                        int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag)
+                                        int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo)
 {
     if (n_quanta <= 0) return 0;
-#define CASE(r)                                                                                          \
-    case r:                                                                                              \
-        if (has_n) k_sweep_ringq<r, true, true><<<n_quanta, WAVE, 0, st>>>(NRA_Q_LAUNCH_ARGS);           \
-        else k_sweep_ringq<r, false, true><<<n_quanta, WAVE, 0, st>>>(NRA_Q_LAUNCH_ARGS);                \
+#define CASE(r)                                                                                                          \
+    case r:                                                                                                              \
+        if (relax_c > 0) { if (has_n) k_sweep_ringq<r, true, true, true><<<n_quanta, WAVE, 0, st>>>(NRA_Q_LAUNCH_ARGS);  \
+                           else k_sweep_ringq<r, false, true, true><<<n_quanta, WAVE, 0, st>>>(NRA_Q_LAUNCH_ARGS); }     \
+        else { if (has_n) k_sweep_ringq<r, true, true, false><<<n_quanta, WAVE, 0, st>>>(NRA_Q_LAUNCH_ARGS);             \
+               else k_sweep_ringq<r, false, true, false><<<n_quanta, WAVE, 0, st>>>(NRA_Q_LAUNCH_ARGS); }                \
         break;
     switch (R) {
         CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13)
@@ -1853,10 +1958,10 @@ extern "C" int nra_launch_sweep_ring32_bwd(int R, int has_n, hipStream_t st, int
                                            const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
                                            const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
                                            const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                           int32_t* snap, int32_t* read_a)
+                                           int32_t* snap, int32_t* read_a, int relax_c, int32_t* redo)
 {
     return launch_sweep_ring32<0>(R, has_n, st, n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax,
-                                  coff, snap, read_a, nullptr, nullptr);
+                                  coff, snap, read_a, nullptr, nullptr, relax_c, redo);
 }
 #endif
 #if NRA_HAS_PART(16)
@@ -1864,10 +1969,11 @@ extern "C" int nra_launch_sweep_ring32_fwd(int R, int has_n, hipStream_t st, int
                                            const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
                                            const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
                                            const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                           int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag)
+                                           int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag,
+                                           int relax_c, int32_t* redo)
 {
     return launch_sweep_ring32<1>(R, has_n, st, n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax,
-                                  coff, snap, read_a, cand_score, cand_flag);
+                                  coff, snap, read_a, cand_score, cand_flag, relax_c, redo);
 }
 #endif
 
