@@ -18,24 +18,28 @@ kernel, the per-read selection (best score, flank test, tie mean) on the device,
 per-read results to the host and -- N > 1 -- the one all_gather that leaves them on every rank.
 The same product class runs at every N; there is no data-path collective.
 
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line; nothing else.  --full also
+measures and checks what the headline does not need (the fields marked --full below, and the counters of this very build).
+
 ONE JSON line (< 8 KB), flat where the driver keeps scalars:
   value / ms_per_step                      the resident-input rate the benchmark contract asks for
-  value_scorer_call / ms_per_scorer_call   SURVEY.md 8(d): ONE scorer call from host buffers to host results (median; N = 1)
+  value_scorer_call / ms_per_scorer_call   --full: SURVEY.md 8(d): ONE scorer call from host buffers to host results (median; N = 1)
   roofline.frac                            COUNTED: SQ_INSTS_VALU of the scoring kernels x 64 lanes / scoring-phase time / peak;
                                            frac_priced (executed cells x 10 lane-ops), frac_useful (unpadded cells x 7.25 / 15.5),
-                                           traffic (FETCH_SIZE + WRITE_SIZE), frac_over_issue_ceiling -- DESIGN.md 5
-  cpu_baseline                             the oracle on a bounded sample of the same workload, the box's host cores
-  configs.config3 / 4 / 5                  the default run (N = 1, config 2): the same record for the other BASELINE workloads,
+                                           traffic (FETCH_SIZE + WRITE_SIZE), frac_over_issue_ceiling -- DESIGN.md 5.  The
+                                           counters come from rocprofv3 --pmc child runs with --full, else from the tracked summary
+  cpu_baseline                             --full: the oracle on a bounded sample of the same workload, the box's host cores
+  configs.config3 / 4 / 5                  --full, N = 1, config 2: the same record for the other BASELINE workloads,
                                            each with its own rocprofv3 --pmc child passes (--sub-configs none: skip them)
-  multi_gpu, configs.config4               N > 1: per-rank kernel ms, imbalance of executed cells, the exposed all_gather of one
-                                           pass; and BASELINE config 4 (1 M reads x 1000 regions) dealt over the N ranks:
+  multi_gpu, configs.config4               --full, N > 1: per-rank kernel ms, imbalance of executed cells, the exposed all_gather
+                                           of one pass; and BASELINE config 4 (1 M reads x 1000 regions) dealt over the N ranks:
                                            the strong-scaling workload north_star names
 
 --dump-outputs DIR writes what the headline's last timed step handed its caller as DIR/<name>.npy (float64): configs 2, 4,
 5 the per-read best_score, sum_k, n_ties, status; config 3 the per-read repeat1_count / repeat2_count (NaN where a read has
 none) and the grid steps step_size1 / step_size2.  The inputs are seeded, so two builds can be compared file by file.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--sub-configs 3,4,5|none] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--dump-outputs DIR] [--full [--sub-configs 3,4,5|none]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -109,19 +113,31 @@ def parse():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL)")
     ap.add_argument("--same-device", action="store_true",
                     help="rehearsal only: every rank uses GPU 0 (with --backend gloo on a one-GPU box)")
-    ap.add_argument("--cpu-sample", type=int, default=-1,
-                    help="reads in the CPU-baseline sample (-1: sized for ~15 s, ~6 s in a sub-record; 0: skip)")
-    ap.add_argument("--one-shot-calls", type=int, default=5, help="host-buffers-in/out scorer calls timed at N = 1 (0: skip)")
-    ap.add_argument("--live-pmc", default="auto", choices=("auto", "on", "off"),
-                    help="count the VALU instructions of this very build with a short rocprofv3 --pmc child run (auto: the "
-                         "default N = 1 run only; falls back to the tracked summary when rocprofv3 is not there)")
-    ap.add_argument("--sub-configs", default="3,4,5",
-                    help="default run (N = 1, config 2) only: the other configs measured into `configs` (none: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: CPU baselines, scorer calls, live counters, "
+                         "the other configs, the multi_gpu record (a plain run does none of them)")
+    ap.add_argument("--cpu-sample", type=int, default=None,
+                    help="--full: reads in the CPU-baseline sample (-1, the default: sized for ~15 s, ~6 s in a sub-record; 0: skip)")
+    ap.add_argument("--one-shot-calls", type=int, default=None,
+                    help="--full: host-buffers-in/out scorer calls timed at N = 1 (default 5; 0: skip)")
+    ap.add_argument("--live-pmc", default=None, choices=("auto", "on", "off"),
+                    help="--full: count the VALU instructions of this very build with a short rocprofv3 --pmc child run (auto, the "
+                         "default: the N = 1 config-2 run only; falls back to the tracked summary when rocprofv3 is not there)")
+    ap.add_argument("--sub-configs", default=None,
+                    help="--full, N = 1, config 2 only: the other configs measured into `configs` (default 3,4,5; none: skip)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the results of the last timed step as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    # the options of --full: their --full defaults, or off in a plain run, where asking for the work is an error
+    for name, full, off in (("cpu_sample", -1, 0), ("one_shot_calls", 5, 0), ("live_pmc", "auto", "off"),
+                            ("sub_configs", "3,4,5", "none")):
+        value = getattr(args, name)
+        if value is None:
+            setattr(args, name, full if args.full else off)
+        elif not args.full and value not in (off, ""):
+            ap.error(f"--{name.replace('_', '-')} {value} needs --full")
     return args
 
 
@@ -234,8 +250,8 @@ def cpu_baseline_1d(data, n_sample, seconds):
 
 
 def live_pmc(config, kernel_substr, steps=2, timeout_s=180, extra=()):
-    """Counters of the scoring kernels of THIS build, counted by short child runs `rocprofv3 --pmc <group> --kernel-trace --
-    python3 bench.py --config N --steps S` (counters only, one group per pass, as MI355X_MICROARCH.md prescribes):
+    """Counters of the scoring kernels of THIS build, counted by short plain child runs `rocprofv3 --pmc <group> --kernel-trace
+    -- python3 bench.py --config N --steps S` (counters only, one group per pass, as MI355X_MICROARCH.md prescribes):
     SQ_INSTS_VALU / SQ_ACTIVE_INST_VALU / GRBM_GUI_ACTIVE, then FETCH_SIZE, then WRITE_SIZE.  Returns the keys of a
     tracked summary (tools/pmc_summary.py), or None when the first pass fails (no rocprofv3, a refusal, a timeout)."""
     import csv
@@ -250,8 +266,7 @@ def live_pmc(config, kernel_substr, steps=2, timeout_s=180, extra=()):
     def one_pass(counters):
         out = tempfile.mkdtemp(prefix="nra_pmc_", dir=tmp)
         cmd = [exe, "--pmc"] + counters + ["--kernel-trace", "--output-format", "csv", "-d", out, "--", sys.executable,
-               os.path.abspath(__file__), "--config", str(config), "--steps", str(steps), "--warmup", "0", "--cpu-sample", "0",
-               "--one-shot-calls", "0", "--sub-configs", "none", "--live-pmc", "off"] + list(extra)
+               os.path.abspath(__file__), "--config", str(config), "--steps", str(steps), "--warmup", "0"] + list(extra)
         try:
             env = dict(os.environ, TMPDIR=tmp)
             for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
@@ -488,23 +503,26 @@ def bench_1d(args):
     multi = None
     job_share = 1.0
     if dist is not None:
-        # one more pass with NOTHING behind it: the exchange (one all_gather of 32 B per read, padded to the largest shard)
-        # exposed, timed between barriers; then every rank's kernel time and executed cells
+        # --full: one more pass with NOTHING behind it: the exchange (one all_gather of 32 B per read, padded to the largest
+        # shard) exposed, timed between barriers; then every rank's kernel time and executed cells
         import torch
         dev = torch.device("cuda", torch.cuda.current_device()) if args.backend == "nccl" else torch.device("cpu")
-        sb.run()
-        local = sb.fetch_local()
-        dist.barrier(); torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        sb.exchange(local)
-        dist.barrier()
-        t_gather = time.perf_counter() - t0
+        t_gather = float("nan")
+        if args.full:
+            sb.run()
+            local = sb.fetch_local()
+            dist.barrier(); torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            sb.exchange(local)
+            dist.barrier()
+            t_gather = time.perf_counter() - t0
         mine_t = torch.tensor([dl["phase_ms"], float(st["executed_cells"]), t_gather * 1e3, float(n_align_local)], dtype=torch.float64, device=dev)
         allr = [torch.empty_like(mine_t) for _ in range(world)]
         dist.all_gather(allr, mine_t)
         allr = np.array([t.cpu().numpy() for t in allr])
         if scaling == "strong":        # the counters were counted on the whole job on one GPU: this rank ran its share of it
             job_share = float(st["executed_cells"]) / max(float(allr[:, 1].sum()), 1.0)
+    if dist is not None and args.full:
         multi = {"per_rank_kernel_ms": [round(float(x), 3) for x in allr[:, 0]],
                  "per_rank_alignments": [int(x) for x in allr[:, 3]],
                  "executed_cells_max_over_mean": float(allr[:, 1].max() / max(allr[:, 1].mean(), 1.0)),

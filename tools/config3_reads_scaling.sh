@@ -6,7 +6,7 @@ mkdir -p $OUT
 for n in 1000 2500 5000 20000 28000 40000 80000; do
   for keep in kept not_kept; do
     F=""; P="on"; if [ $keep = not_kept ]; then F="--joint-no-keep"; P="off"; fi
-    timeout -k 10 400 python3 bench.py --config 3 --reads $n --steps 8 --warmup 2 --cpu-sample 0 --one-shot-calls 0 --sub-configs none --live-pmc $P $F > $OUT/${keep}_$n.json 2> $OUT/${keep}_$n.err || exit 1
+    timeout -k 10 400 python3 bench.py --full --config 3 --reads $n --steps 8 --warmup 2 --cpu-sample 0 --one-shot-calls 0 --sub-configs none --live-pmc $P $F > $OUT/${keep}_$n.json 2> $OUT/${keep}_$n.err || exit 1
   done
 done
 python3 - $OUT <<'P'

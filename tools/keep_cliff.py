@@ -9,8 +9,7 @@ import csv, glob, json, os, shutil, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out_path = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/keep_cliff.json"
 sizes = [int(x) for x in sys.argv[2:]] or [20000, 30000, 40000]
-BENCH = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "3", "--warmup", "1", "--cpu-sample", "0", "--one-shot-calls", "0",
-         "--sub-configs", "none", "--live-pmc", "off"]
+BENCH = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "3", "--warmup", "1"]
 env = dict(os.environ, NRA_JOINT_KEEP_BUDGET_GB="64", TMPDIR="/tmp")
 res = {"what": "config 3 with reads x 4 / x 6 / x 8: 16 / 24 / 32 GB of kept column states (budget lifted to 64 GB)", "runs": {}}
 

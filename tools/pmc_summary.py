@@ -84,7 +84,7 @@ def main():
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from bench import kernel_source_sha16
     res = {"command": "rocprofv3 --pmc <group> --kernel-trace --output-format csv -- python3 bench.py --steps "
-                      f"{steps} --warmup 0 --cpu-sample 0 --one-shot-calls 0 --sub-configs none {opts.get('--flags', '')} "
+                      f"{steps} --warmup 0 {opts.get('--flags', '')} "
                       "(one pass per counter group)",
            "source_sha16": kernel_source_sha16(),       # bench.py quotes these counters only for the same kernel sources
            "kernel": kern, "steps": steps,

@@ -11,11 +11,11 @@ OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 ROOT=$(pwd)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --steps 10 --warmup 2 --sub-configs none "$@" > $OUT/bench_stats.json 2> $OUT/bench_stats.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --full --steps 10 --warmup 2 --sub-configs none "$@" > $OUT/bench_stats.json 2> $OUT/bench_stats.err || exit 1
 STEPS=3
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -- python3 bench.py --steps $STEPS --warmup 0 --cpu-sample 0 --one-shot-calls 0 --sub-configs none "$@" > $OUT/pmc_fetch.log 2>&1 || exit 2
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write -- python3 bench.py --steps $STEPS --warmup 0 --cpu-sample 0 --one-shot-calls 0 --sub-configs none "$@" > $OUT/pmc_write.log 2>&1 || exit 3
-rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/pmc_sq -- python3 bench.py --steps $STEPS --warmup 0 --cpu-sample 0 --one-shot-calls 0 --sub-configs none "$@" > $OUT/pmc_sq.log 2>&1 || exit 4
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -- python3 bench.py --steps $STEPS --warmup 0 "$@" > $OUT/pmc_fetch.log 2>&1 || exit 2
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write -- python3 bench.py --steps $STEPS --warmup 0 "$@" > $OUT/pmc_write.log 2>&1 || exit 3
+rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/pmc_sq -- python3 bench.py --steps $STEPS --warmup 0 "$@" > $OUT/pmc_sq.log 2>&1 || exit 4
 python3 tools/pmc_summary.py $TAG $OUT/stats $OUT/pmc_fetch $OUT/pmc_write $OUT/pmc_sq --steps=$STEPS --kernel=$KERN "--flags=$*" > $OUT/summary.json || exit 5
 mkdir -p gpurun_out/profiles_$TAG
 cp profiles/${TAG}_* gpurun_out/profiles_$TAG/
