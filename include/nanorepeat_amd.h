@@ -412,6 +412,22 @@ int nra_read_structure(int device, int32_t n_motifs, const char* motifs, const i
                        int32_t n_reads, const char* seqs, const int64_t* seq_off, const int32_t* read_motif,
                        int32_t* edits, int32_t* start_phase, uint8_t* path);
 
+/* ---- tandem motifs: which motifs a read's tract is made of (no counterpart in the reference) ----------------------
+ *
+ * For each tract s (n bases, upper-cased first) and each period p = 1..max_period, position i (i + 2p <= n) is a
+ * tandem position when s[i, i+p) == s[i+p, i+2p), all 2p bases are A, C, G or T (any other byte breaks the window)
+ * and the word w = s[i, i+p) is primitive (not x^m for a shorter x: AA never counts at p = 2, ATAT never at p = 4).
+ * The class of w is its smallest rotation in the order A < C < G < T; its code is that rotation in base 4, first base
+ * most significant.  There are 964 classes of 1..6 bases.  DESIGN.md section 15. */
+
+/* tract t = bytes [seq_off[t], seq_off[t+1]) of `seqs` (at most 200 000 bases, NRA_E_RANGE beyond).  Writes
+ * n_tandem[t * max_period + p - 1] = the tandem positions of period p, and the top_n classes by count as
+ * (top_p, top_code, top_count)[t * top_n + q], ordered by count descending, then p ascending, then code ascending;
+ * (0, -1, 0) in unused slots.  1 <= max_period <= 6 and 1 <= top_n <= 8, else NRA_E_ARG; arguments are checked
+ * before the device is touched. */
+int nra_tract_motifs(int device, int32_t n_tracts, const char* seqs, const int64_t* seq_off, int32_t max_period,
+                     int32_t top_n, int32_t* n_tandem, int8_t* top_p, int32_t* top_code, int32_t* top_count);
+
 #ifdef __cplusplus
 }
 #endif

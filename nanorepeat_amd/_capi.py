@@ -34,7 +34,7 @@ EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count
            "nra_batch2d_create", "nra_batch2d_create_reads", "nra_batch2d_set_cells", "nra_joint_grid_cells", "nra_batch2d_set_grid", "nra_batch2d_invalidate", "nra_batch2d_sweep_flanks", "nra_batch2d_refine", "nra_batch_run", "nra_batch_sync", "nra_batch_stats",
            "nra_batch1d_fetch", "nra_batch1d_resweeps", "nra_batch2d_fetch", "nra_batch_destroy",
            "nra_screen_create", "nra_screen_reads", "nra_screen_stats", "nra_screen_destroy",
-           "nra_read_structure")
+           "nra_read_structure", "nra_tract_motifs")
 
 
 E_RANGE = -3      # NRA_E_RANGE
@@ -173,6 +173,9 @@ def load():
     lib.nra_read_structure.restype = C.c_int
     lib.nra_read_structure.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, C.c_int32, C.c_char_p, pi64, pi32,
                                        pi32, pi32, p8]
+    lib.nra_tract_motifs.restype = C.c_int
+    lib.nra_tract_motifs.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, C.c_int32, C.c_int32, pi32,
+                                     C.POINTER(C.c_int8), pi32, pi32]
     _LIB = lib
     return lib
 
@@ -634,4 +637,19 @@ def read_structure(motifs, tracts, read_motif, device=0):
     _check(lib.nra_read_structure(device, len(motifs), mdata, _ptr(moff, C.c_int64), n, data, _ptr(off, C.c_int64),
                                   _ptr(rm, C.c_int32), _ptr(out["edits"], C.c_int32),
                                   _ptr(out["start_phase"], C.c_int32), _ptr(out["path"], C.c_uint8)))
+    return out
+
+
+def tract_motifs(tracts, max_period=6, top_n=4, device=0):
+    """nra_tract_motifs: the tandem positions of every tract per period 1..max_period and its top_n motif classes ->
+    dict(n_tandem [n, max_period], top_p [n, top_n] int8, top_code, top_count [n, top_n] int32); (0, -1, 0) in
+    unused slots."""
+    lib = load()
+    data, off = pack_reads(list(tracts))
+    n = len(off) - 1
+    out = dict(n_tandem=np.zeros((n, max(max_period, 0)), np.int32), top_p=np.zeros((n, max(top_n, 0)), np.int8),
+               top_code=np.zeros((n, max(top_n, 0)), np.int32), top_count=np.zeros((n, max(top_n, 0)), np.int32))
+    _check(lib.nra_tract_motifs(device, n, data, _ptr(off, C.c_int64), max_period, top_n,
+                                _ptr(out["n_tandem"], C.c_int32), _ptr(out["top_p"], C.c_int8),
+                                _ptr(out["top_code"], C.c_int32), _ptr(out["top_count"], C.c_int32)))
     return out

@@ -229,6 +229,25 @@ struct NraStructRead {
 // traceback pointer words per (row, lane): ins bits of the P phases, then del bits
 #define NRA_STRUCT_WORDS(P) ((P) <= 16 ? 1 : (P) <= 32 ? 2 : 4)
 
+// Tandem motifs (nra_motif.hip, nra_motif_host.cpp): per read tract, the tandem positions of each period 1..6 and
+// the counts of their motif classes.  A class is a Lyndon word of p <= 6 bases; its code is the
+// word in base 4, first base most significant; its dense id orders the 964 classes by (p, code).
+#define NRA_MOTIF_MAX_P 6
+#define NRA_MOTIF_MAX_TOP 8
+#define NRA_MOTIF_MAX_N 200000
+#define NRA_MOTIF_CODES 5460                  // sum of 4^p, p = 1..6: the code-to-dense-id table
+#define NRA_MOTIF_CLASSES 964                 // Lyndon words of 1..6 bases over ACGT
+#define NRA_MOTIF_BLOCK 16                    // positions per lane step; tracts start 16-byte aligned
+#define NRA_MOTIF_CODE_OTHER 4                // a tract byte other than ACGT (either case): breaks every window
+#define NRA_MOTIF_PAD 32                      // bytes after the last tract of a chunk: a block loads 32 bytes
+
+// one tract of a launch: its codes start at byte `off` of the chunk's buffer (a multiple of NRA_MOTIF_BLOCK)
+struct NraMotifTract {
+    uint64_t off;
+    int32_t n;
+    int32_t pad;
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -246,6 +265,12 @@ int nra_launch_screen_hits(hipStream_t st, int64_t n_tiles, const NraScreenTile*
 // res[2 i] = edits, res[2 i + 1] = start phase of read i
 int nra_launch_structure(hipStream_t st, int P, int n_reads, const NraStructRead* reads, const NraStructMotif* motifs,
                          const uint8_t* codes, uint32_t* ptrs, uint8_t* path, int32_t* res);
+
+// tandem motifs (nra_motif.hip): one wave per tract, n_grid workgroups of four waves.  n_tandem[t * 6 + p - 1] and
+// top_key[t * 8 + q] (count << 10 | (1023 - dense id), 0 for an unused slot) for q < top_n
+int nra_launch_tract_motifs(hipStream_t st, int n_grid, int n_tracts, const NraMotifTract* tracts,
+                            const uint8_t* codes, const int16_t* dense_of, int max_p, int top_n, int32_t* n_tandem,
+                            uint32_t* top_key);
 
 // launchers (nra_kernels.hip).  All asynchronous on `st`; return hipError_t as int.
 int nra_launch_score_pk16(int R, int has_n, hipStream_t st, int n_tasks,

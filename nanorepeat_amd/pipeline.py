@@ -145,14 +145,17 @@ def quantify_joint(in_fq, ref_fasta, repeat1_string, repeat2_string, out_prefix,
 def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, data_type="ont", anchor_len=1000,
                       fast_mode=False, ploidy=2, max_mutual_overlap=0.15, max_num_components=-1,
                       remove_noisy_reads=False, no_check_repeat_motif_in_ref=False, no_details=False,
-                      num_cpu=1, device=0, scoring=None, seed=None, read_structure=False, **engines):
+                      num_cpu=1, device=0, scoring=None, seed=None, read_structure=False, discover_motifs=False,
+                      min_motif_count=4, min_motif_share=0.1, **engines):
     """The BAM command from files to files (nanoRepeat_bam.py:614-751): for every region of the BED
     file, reads from the alignment file -> `<out_prefix>.details/<chr>/<region>.*` ->
     `<out_prefix>.NanoRepeat_output.tsv`.  The reference forks up to 16 workers, one region each;
     here steps 1-2 run region by region and step 3 for all regions in one GPU batch.  Regions
     without reads, or whose reference sequence fails the motif check, get their row with 0
     alleles like in the reference.  read_structure=True adds the repeat structure files
-    (structure.py); `engines` may carry aligner / scorer / structure_engine stand-ins.  Returns the regions."""
+    (structure.py); discover_motifs=True adds the tandem motif files (motifs.py; min_motif_count and
+    min_motif_share set the per-read call).  `engines` may carry aligner / scorer / structure_engine /
+    motif_engine stand-ins.  Returns the regions."""
     from . import bam as nr_bam
     regions = nr_io.read_repeat_region_file(repeat_region_bed, no_details)
     ref_fasta_dict = nr_io.fasta_file2dict(ref_fasta)
@@ -169,7 +172,7 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
         reads_of.append(nr_io.read_fastq(region.region_fq_file))
     _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
-                        read_structure)
+                        read_structure, _motif_options(discover_motifs, min_motif_count, min_motif_share))
     return regions
 
 
@@ -184,11 +187,16 @@ def _set_region_paths(region, index, out_prefix):
     region.region_fq_file = f"{region.out_prefix}.reads.fastq"
 
 
+def _motif_options(discover_motifs, min_motif_count, min_motif_share):
+    return dict(min_motif_count=min_motif_count, min_motif_share=min_motif_share) if discover_motifs else None
+
+
 def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
-                        read_structure=False):
+                        read_structure=False, motif_options=None):
     """The commands' common tail: steps 1-4 for the regions with reads, then one TSV row per BED region; with
-    read_structure, the structure of every read with a size and the two structure files."""
+    read_structure, the structure of every read with a size and the two structure files; with motif_options (a dict
+    of motifs.motif_regions keywords), the tandem motifs of every read with a core and the two motif files."""
     quantify_regions(live, reads_of, data_type, fast_mode, num_cpu, device, scoring,
                      engines.get("aligner"), engines.get("scorer"))
     phase_regions(live, data_type, ploidy, max_mutual_overlap, max_num_components, remove_noisy_reads, seed)
@@ -201,6 +209,13 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
         for region in live:
             structure.write_read_structure(region)
         structure.write_structure_summary(regions, out_prefix)
+    if motif_options is not None:
+        from . import motifs
+        motifs.motif_regions(live, fast_mode, device=device, engine=engines.get("motif_engine"),
+                             scorer=engines.get("scorer"), scoring=scoring, **motif_options)
+        for region in live:
+            motifs.write_read_motifs(region)
+        motifs.write_motif_summary(regions, out_prefix)
     if no_details:
         import shutil
         shutil.rmtree(f"{out_prefix}.details", ignore_errors=True)
@@ -210,15 +225,17 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         fast_mode=False, ploidy=2, max_mutual_overlap=0.15, max_num_components=-1,
                         remove_noisy_reads=False, no_check_repeat_motif_in_ref=False, no_details=False,
                         num_cpu=1, device=0, scoring=None, seed=None, screen=True, k=15, min_hits=4, max_occ=16,
-                        chunk_bases=1 << 28, read_structure=False, **engines):
+                        chunk_bases=1 << 28, read_structure=False, discover_motifs=False, min_motif_count=4,
+                        min_motif_share=0.1, **engines):
     """The FASTQ / FASTA command (nanoRepeat.py:109, `-t fastq|fasta`) from files to files, without a genome mapper:
     the reads each region sees are chosen by the anchor k-mer screen (screen.reads_by_region) instead of a
     genome-wide mapping and a BAM window, then the BAM command's steps run unchanged.  Every region's reference
     must extract (else the command fails, as the BAM command does); regions that fail the motif check are not
     screened and get their 0-allele row.  Each region's reads go to `<out_prefix>.details/<chr>/<region>.reads.fastq`
     (qualities `.` for FASTA input).  screen=False offers every read to every region: exact, and slow beyond small
-    panels.  read_structure=True adds the repeat structure files (structure.py).  `engines` may carry aligner /
-    scorer / screener / structure_engine stand-ins.  Returns the regions."""
+    panels.  read_structure=True adds the repeat structure files (structure.py); discover_motifs=True adds the
+    tandem motif files (motifs.py).  `engines` may carry aligner / scorer / screener / structure_engine / motif_engine
+    stand-ins.  Returns the regions."""
     from . import screen as nr_screen
     regions = nr_io.read_repeat_region_file(repeat_region_bed, no_details)
     ref_fasta_dict = nr_io.fasta_file2dict(ref_fasta)
@@ -243,7 +260,7 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
             reads_of.append({name: seq for name, (seq, _) in reads.items()})
     _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
-                        read_structure)
+                        read_structure, _motif_options(discover_motifs, min_motif_count, min_motif_share))
     return regions
 
 

@@ -383,3 +383,45 @@ def structure_panel(reads_per_allele=8, anchor_len=1000, model="hifi", seed=SEED
     reads = [reads[i] for i in order]
     return dict(ref={"chr1": chrom}, bed=[f"{c}\t{st}\t{en}\t{u}\n" for c, st, en, u in regions], regions=regions,
                 reads=reads, truth=truth, planted=[[inter for _, inter in alleles] for _, alleles, _ in loci])
+
+
+def motif_panel(reads_per_allele=8, anchor_len=1000, model="hifi", seed=SEED):
+    """A small panel whose alleles carry planted motif changes, for the tandem motifs (motifs.py): an RFC1-like locus
+    (BED AAAAG; alleles (AAAAG)11 and (AAGGG)200), a period change (BED CAG; (CAG)20 and (CCTG)120), a DAB1-like
+    insertion (BED ATTTT; (ATTTT)15 and (ATTTT)60 (ATTTC)40 (ATTTT)20) and a pure TATTG control (12 and 30 units).
+    The reference holds the BED motif.  Reads span both anchors, half reverse-complemented, through the `model` error
+    channel.  Its own random stream.
+
+    Returns dict(ref, bed, regions, reads, truth) like panel(), plus planted = [per region, per allele in the order
+    above: (dominant class, units of it)].
+    """
+    rng = np.random.default_rng(seed)
+    loci = [("AAAAG", "AAAAG" * 11, [("AAAAG" * 11, ("AAAAG", 11)), ("AAGGG" * 200, ("AAGGG", 200))]),
+            ("CAG", "CAG" * 20, [("CAG" * 20, ("AGC", 20)), ("CCTG" * 120, ("CCTG", 120))]),
+            ("ATTTT", "ATTTT" * 15, [("ATTTT" * 15, ("ATTTT", 15)),
+                                     ("ATTTT" * 60 + "ATTTC" * 40 + "ATTTT" * 20, ("ATTTT", 80))]),
+            ("TATTG", "TATTG" * 16, [("TATTG" * 12, ("ATTGT", 12)), ("TATTG" * 30, ("ATTGT", 30))])]
+    gap, extra = 3000, 800
+    parts, regions, at = [], [], 0
+    for unit, ref_tract, _ in loci:
+        left, right = rand_seq(rng, anchor_len + extra), rand_seq(rng, anchor_len + extra)
+        start = at + gap + len(left)
+        regions.append(("chr1", start, start + len(ref_tract), unit))
+        parts += [rand_seq(rng, gap), left, ref_tract, right]
+        at += gap + len(left) + len(ref_tract) + len(right)
+    parts.append(rand_seq(rng, gap))
+    chrom = "".join(parts)
+    raw, truth = [], {}
+    for g, ((_, _, alleles), (_, st, en, _)) in enumerate(zip(loci, regions)):
+        for a, (tract, _) in enumerate(alleles):
+            for i in range(reads_per_allele):
+                lo, ro = anchor_len + int(rng.integers(0, 301)), anchor_len + int(rng.integers(0, 301))
+                name = f"m{g}_{a}_{i:02d}"
+                raw.append((name, chrom[st - lo:st] + tract + chrom[en:en + ro]))
+                truth[name] = (g, a)
+    seqs = apply_errors_batch(rng, [s for _, s in raw], model)
+    reads = [(name, revcomp(s) if rng.random() < 0.5 else s) for (name, _), s in zip(raw, seqs)]
+    order = rng.permutation(len(reads))
+    reads = [reads[i] for i in order]
+    return dict(ref={"chr1": chrom}, bed=[f"{c}\t{st}\t{en}\t{u}\n" for c, st, en, u in regions], regions=regions,
+                reads=reads, truth=truth, planted=[[want for _, want in alleles] for _, _, alleles in loci])
