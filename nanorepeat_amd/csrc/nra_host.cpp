@@ -401,7 +401,7 @@ struct Bucket {
     int R = 0;
     bool chain = false;        // reads longer than one register block: chained row blocks
     bool wide = false;         // chained: int32 cells, one read per wave (else packed int16, two reads per wave)
-    bool half = false;         // k_sweep_ring32: two read pairs per wave, 32 lanes each (R = rows per lane of a half)
+    bool half = false;         // k_sweep_ring32: two read pairs per wave, 32 lanes each (R = rows per lane of a half; a ring bucket)
     int payload_R = 0;         // chained: row block of the extents kernel (NRA_CHAIN_R / NRA_CHAIN_R_TEST)
     size_t strip_off = 0;      // chained: this bucket's scratch strips in chain_sweep (int32 index)
     int n_strips = 0;
@@ -1597,21 +1597,13 @@ static int run_1d(nra_batch* b)
         // The exact re-sweep of a tainted bucket's flagged tasks: today's two launches, behind the tainted
         // sweeps on the bucket's stream; every other wave leaves at once.  It rewrites the tasks' R side, A and outputs.
         auto resweep = [&](const Bucket& bk, hipStream_t q, int32_t* redo) {
-            int rc2 = bk.half ? nra_launch_sweep_ring32_bwd(bk.R, b->has_n, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off, b->reads.p,
-                                                            b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p,
-                                                            b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p, 0, redo)
-                              : nra_launch_sweep_ring_bwd(bk.R, b->has_n, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off, b->reads.p,
-                                                          b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p,
-                                                          b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p, 0, redo);
+            int rc2 = nra_launch_sweep_ring_bwd(bk.R, b->has_n, bk.half, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off, b->reads.p,
+                                                b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p, b->kmax.p,
+                                                b->coff.p, b->snap.p, b->read_a1d.p, 0, redo);
             if (rc2) return rc2;
-            return bk.half ? nra_launch_sweep_ring32_fwd(bk.R, b->has_n, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off, b->reads.p,
-                                                         b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p,
-                                                         b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p, b->cand_score.p,
-                                                         b->cand_flag.p, 0, redo)
-                           : nra_launch_sweep_ring_fwd(bk.R, b->has_n, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off, b->reads.p,
-                                                       b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p,
-                                                       b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p, b->cand_score.p,
-                                                       b->cand_flag.p, 0, redo);
+            return nra_launch_sweep_ring_fwd(bk.R, b->has_n, bk.half, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off, b->reads.p,
+                                             b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p, b->kmax.p,
+                                             b->coff.p, b->snap.p, b->read_a1d.p, b->cand_score.p, b->cand_flag.p, 0, redo);
         };
         // (the order the buckets' chains are launched in makes no difference: 5.50 - 5.61 ms either way on config 2;
         // a bucket's tasks as 2 / 3 / 4 groups with chains of their own are slower: 5.65 -> 6.0 / 5.9 / 7.6 ms)
@@ -1640,12 +1632,12 @@ static int run_1d(nra_batch* b)
             if (bk.quanta) {
                 // one launch: the sweeps' parts, taken by ticket (two timing pairs like the two launches it replaces: the
                 // second one is empty)
-                auto launch = bk.half ? nra_launch_sweep_ringq32 : nra_launch_sweep_ringq;
-                LAUNCH_TRY(launch(bk.R, b->has_n, q, bk.n_quanta, b->q_list.p + bk.q_off, bk.q_steps, bk.n_sweep, b->q_words.p + 1 + i,
-                                  b->q_words.p + b->q_arrivals_off + bk.q_task_off, b->q_words.p, b->q_state.p + bk.q_state_off,
-                                  b->sweep_tasks.p + bk.sweep_off, b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p,
-                                  b->sp, b->kmin.p, b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p, b->cand_score.p,
-                                  b->cand_flag.p, bk.taint ? b->relax_c : 0, redo));
+                LAUNCH_TRY(nra_launch_sweep_ringq(bk.R, b->has_n, bk.half, q, bk.n_quanta, b->q_list.p + bk.q_off, bk.q_steps, bk.n_sweep,
+                                                  b->q_words.p + 1 + i, b->q_words.p + b->q_arrivals_off + bk.q_task_off, b->q_words.p,
+                                                  b->q_state.p + bk.q_state_off, b->sweep_tasks.p + bk.sweep_off, b->reads.p,
+                                                  b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p, b->kmax.p,
+                                                  b->coff.p, b->snap.p, b->read_a1d.p, b->cand_score.p, b->cand_flag.p,
+                                                  bk.taint ? b->relax_c : 0, redo));
                 if (bk.taint) LAUNCH_TRY(resweep(bk, q, redo));
                 HIP_TRY(hipEventRecord(b->ev[ev++], q));
                 HIP_TRY(hipEventRecord(b->ev[ev++], q));
@@ -1668,12 +1660,8 @@ static int run_1d(nra_batch* b)
                                                           b->sweep_tasks.p + bk.sweep_off, b->reads.p, b->regions.p, b->pool.p,
                                                           b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p, b->kmax.p, b->coff.p,
                                                           b->snap.p, b->read_a1d.p, strips, b->chain_cap, bk.n_strips));
-            else if (bk.half)
-                LAUNCH_TRY(nra_launch_sweep_ring32_bwd(bk.R, b->has_n, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off,
-                                                       b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp,
-                                                       b->kmin.p, b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p, relax_c, redo));
             else if (bk.ring)
-                LAUNCH_TRY(nra_launch_sweep_ring_bwd(bk.R, b->has_n, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off,
+                LAUNCH_TRY(nra_launch_sweep_ring_bwd(bk.R, b->has_n, bk.half, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off,
                                                      b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp,
                                                      b->kmin.p, b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p, relax_c, redo));
             else
@@ -1703,13 +1691,8 @@ static int run_1d(nra_batch* b)
                                                           b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p, b->kmax.p, b->coff.p,
                                                           b->snap.p, b->read_a1d.p, b->cand_score.p, b->cand_flag.p,
                                                           strips, b->chain_cap, bk.n_strips));
-            else if (bk.half)
-                LAUNCH_TRY(nra_launch_sweep_ring32_fwd(bk.R, b->has_n, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off,
-                                                       b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp,
-                                                       b->kmin.p, b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p,
-                                                       b->cand_score.p, b->cand_flag.p, relax_c, redo));
             else if (bk.ring)
-                LAUNCH_TRY(nra_launch_sweep_ring_fwd(bk.R, b->has_n, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off,
+                LAUNCH_TRY(nra_launch_sweep_ring_fwd(bk.R, b->has_n, bk.half, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off,
                                                      b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp,
                                                      b->kmin.p, b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p,
                                                      b->cand_score.p, b->cand_flag.p, relax_c, redo));

@@ -316,37 +316,26 @@ int nra_launch_sweep_fwd(int R, int has_n, int chain, hipStream_t st, int n_task
 
 // the same sweeps with the lane-to-lane hand-off through an LDS ring (k_sweep_ring: one read block per wave,
 // forward sweep skewed by the unit length so that the junction combine runs on every m-th step only);
-// unchained reads, unit length <= NRA_SWEEP_RING_MAX_M
+// unchained reads, unit length <= NRA_SWEEP_RING_MAX_M.  half: the half-wave kernel (k_sweep_ring32), reads of up to
+// 32 * NRA_RING32_MAX_R bases, two read pairs of one region per wave (32 lanes each); R from NRA_R_LIST up to
+// NRA_RING32_MAX_R (16: 301.8, 20: 299.7, 24: 297.4 ms on config 4; 32, which would take config 2's 950-base reads too:
+// 5.65 -> 7.1 ms there, 281 -> 288 ms on config 4)
 #define NRA_SWEEP_RING_MAX_M 8
-int nra_launch_sweep_ring_bwd(int R, int has_n, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
+#define NRA_RING32_MAX_R 24
+int nra_launch_sweep_ring_bwd(int R, int has_n, int half, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
                               const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
                               const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
                               const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
                               int32_t* snap, int32_t* read_a, int relax_c, int32_t* redo);
-int nra_launch_sweep_ring_fwd(int R, int has_n, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
+int nra_launch_sweep_ring_fwd(int R, int has_n, int half, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
                               const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
                               const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
                               const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
                               int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo);
-// relax_c > 0 (these, the half-wave and the quanta launchers): the taint scheme -- the anchor columns up to
+// relax_c > 0 (these and the quanta launcher): the taint scheme -- the anchor columns up to
 // relax_c bases from the junction run the relaxed cell, and redo[task] is set where that may have reached an output;
 // relax_c <= 0 and redo non-null: the exact sweeps of the flagged tasks only (the re-sweep); both 0 / null: the exact sweeps
 #define NRA_RELAX_C_DEFAULT 256
-
-// half-wave LDS-ring sweeps (k_sweep_ring32): reads of up to 32 * NRA_RING32_MAX_R bases, two read pairs of one
-// region per wave (32 lanes each); R from NRA_R_LIST up to NRA_RING32_MAX_R (16: 301.8, 20: 299.7, 24: 297.4 ms on config 4;
-// 32, which would take config 2's 950-base reads too: 5.65 -> 7.1 ms there, 281 -> 288 ms on config 4)
-#define NRA_RING32_MAX_R 24
-int nra_launch_sweep_ring32_bwd(int R, int has_n, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
-                                const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                int32_t* snap, int32_t* read_a, int relax_c, int32_t* redo);
-int nra_launch_sweep_ring32_fwd(int R, int has_n, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
-                                const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo);
 
 // a bucket's reverse and forward sweeps as one launch of quanta taken by ticket (k_sweep_ringq).  A sweep is cut every
 // `qsteps` steps (a multiple of 64; a forward sweep also at NRA_Q_CUT of its first boundary step) into parts; qlist holds one entry per part, direction << 31 | part << NRA_Q_PART_SHIFT |
@@ -354,7 +343,7 @@ int nra_launch_sweep_ring32_fwd(int R, int has_n, hipStream_t st, int n_tasks, c
 // count a sweep's steps with the same macros.  `arrivals`: two counters per task (finished reverse / forward parts) and
 // `ticket`, zeroed before the launch; `giveup` the launch-wide give-up word; qstate: slots of NRA_QSTATE_INTS(R) x 64 int32
 // (the registers, the ring's places, then the pending outputs and boundary accumulators), one per forward sweep and then,
-// where a reverse sweep has more than one part, one per reverse sweep
+// where a reverse sweep has more than one part, one per reverse sweep; half: the half-wave buckets, as above
 #define NRA_QSTATE_INTS(R) (((4 * (R) + 2 + 3) / 4 + NRA_SWEEP_RING_MAX_M + 1) * 4)
 #define NRA_Q_PART_SHIFT 27
 #define NRA_Q_PART_MASK 15u
@@ -366,18 +355,12 @@ int nra_launch_sweep_ring32_fwd(int R, int has_n, hipStream_t st, int n_tasks, c
                                 // its first cut, the rest
 #define NRA_Q_STEPS_REV(l3, half) ((l3) + ((half) ? 31 : 63))
 #define NRA_Q_STEPS_FWD(l1, m, kmax, half) ((l1) + (m) * (kmax) + ((half) ? 31 : 63) * (m))
-int nra_launch_sweep_ringq(int R, int has_n, hipStream_t st, int n_quanta, const uint32_t* qlist, int qsteps, int n_tasks, int32_t* ticket,
+int nra_launch_sweep_ringq(int R, int has_n, int half, hipStream_t st, int n_quanta, const uint32_t* qlist, int qsteps, int n_tasks, int32_t* ticket,
                            int32_t* arrivals, int32_t* giveup, int32_t* qstate, const NraSweepTask* tasks,
                            const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
                            const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
                            const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
                            int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo);
-int nra_launch_sweep_ringq32(int R, int has_n, hipStream_t st, int n_quanta, const uint32_t* qlist, int qsteps, int n_tasks, int32_t* ticket,
-                             int32_t* arrivals, int32_t* giveup, int32_t* qstate, const NraSweepTask* tasks,
-                             const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                             const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                             const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                             int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo);
 
 // chained LDS-ring sweeps (k_sweep_ringchain): reads of more than NRA_RING_CHAIN_MIN_ROWS rows as row blocks of
 // 64 * NRA_RING_CHAIN_R; wide = 0: two reads per wave in packed int16, 1: one read per wave in int32 cells.

@@ -542,7 +542,10 @@ __device__ __forceinline__ void sweep_rside_taint(const int (&Hq)[R], const int 
     if (t & T2) *flag = 1;
 }
 
-template <int R, bool HAS_N, int DIR, bool COMB, bool QUANTA, bool TAINT = false>
+// HALF: the two 32-lane halves of the wave sweep a read pair each (k_sweep_ring32).  W lanes hold a pair, hl is a lane's
+// place among them and hoff the pair's first lane.  Rows, ring places and boundary accumulators are a pair's own: the
+// pair's last lane hands out what enters its first.
+template <int R, bool HAS_N, bool HALF, int DIR, bool COMB, bool QUANTA, bool TAINT>
 __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, int4* ring, int2* racc,
                                                 const NraSweepTask* __restrict__ tasks,
                                                 const NraDevRead* __restrict__ reads,
@@ -559,16 +562,23 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
                                                 int32_t* __restrict__ cand_score,
                                                 uint8_t* __restrict__ cand_flag,
                                                 int32_t* __restrict__ qs, const int s_begin, const int s_end,
-                                                const bool load, const bool store, const int relax_c = 0,
-                                                int32_t* __restrict__ redo = nullptr)
+                                                const bool load, const bool store, const int relax_c,
+                                                int32_t* __restrict__ redo)
 {
     static_assert(DIR == 1 || !COMB, "only a forward sweep meets unit boundaries");
     constexpr int SC = TAINT ? 4 : 2;     // origin-bit scheme: doubled scores; TAINT: 4 * score + 2 * taint + origin
+    constexpr int W = HALF ? 32 : 64;
+    const int hoff = HALF ? lane & 32 : 0;
+    const int hl = HALF ? lane & 31 : lane;
     const NraSweepTask tk = tasks[task];
-    const bool has_b = tk.read_b >= 0;
-    const int ra = tk.read_a, rb = has_b ? tk.read_b : tk.read_a;
+    // the upper half's own pair (a half without reads repeats pair a/b and stores nothing)
+    const bool half_on = hoff == 0 || tk.read_c >= 0;
+    const int r0 = (hoff && tk.read_c >= 0) ? tk.read_c : tk.read_a;
+    const int r1 = (hoff && tk.read_c >= 0) ? tk.read_d : tk.read_b;
+    const bool has_b = r1 >= 0;
+    const int ra = r0, rb = has_b ? r1 : r0;
     const NraDevRead rda = reads[ra], rdb = reads[rb];
-    const NraDevRegion rg = regions[rda.region];
+    const NraDevRegion rg = regions[HALF ? reads[tk.read_a].region : rda.region];
     const int m = rg.m1;
     const int flank = DIR ? rg.l1 : rg.l3;
     const uint8_t* __restrict__ piece = pool + (DIR ? rg.p1_off : rg.pr_off);
@@ -605,11 +615,14 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
         return t;
     };
 
+    // outputs: lane W - 1 of a pair produces one value per boundary; the pair keeps its last W in a lane-indexed register
+    // (rotated within the pair) and writes them W candidates at a time
     int out_a = 0, out_b = 0;
     int n_out = 0, kcur = tk.kmin;                          // wave-uniform
+    const int rot_src = HALF ? (hoff | ((hl + 1) & 31)) << 2 : 0;      // ds_bpermute address: the next lane of the half
     auto flush = [&](int n_valid) {
-        const int k = kcur - 64 + lane;
-        if (lane < 64 - n_valid) return;
+        const int k = kcur - W + hl;
+        if (hl < W - n_valid || !half_on) return;
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
             if (s2 == 1 && !has_b) break;
@@ -625,7 +638,7 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
     int qc[R];
 #pragma unroll
     for (int i = 0; i < R; ++i) {
-        const int gi = lane * R + i;
+        const int gi = hl * R + i;
         const int ca = sweep_query_sel<HAS_N>(rda, q2bit, qnmask, gi, DIR == 0);
         const int cb = sweep_query_sel<HAS_N>(rdb, q2bit, qnmask, gi, DIR == 0);
         qc[i] = ca | (0x0c << 8) | (cb << 16) | (0x0c << 24);
@@ -634,17 +647,20 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
     int Hbo[COMB ? R : 1], Ebo[COMB ? R : 1], E2bo[COMB ? R : 1];
     if (COMB) {
         const int q1 = SC * (sp.open1 - sp.ext1), q2 = SC * (sp.open2 - sp.ext2);
+        // the R side as the reverse sweep stored it: [row][lane] planes (sweep_snapshot) or lane-major (sweep_snapshot_lane)
+        constexpr int PL = HALF ? R : R * 64;               // from H to E to E2
 #pragma unroll
         for (int i = 0; i < R; ++i) {
-            const int r = lane * R + i;
+            const int r = hl * R + i;
             int h[2], e[2], e2[2];
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 const int a = (s ? rdb.qlen : rda.qlen) - 2 - r;
                 if (a >= 0) {
-                    const int al = a / R, ai = a - al * R;
-                    const int32_t* __restrict__ p = snap_task + (size_t)ai * 64 + al;
-                    const int vh = p[0], ve = p[R * 64], ve2 = p[2 * R * 64];
+                    const int al = a / R, ai = a - al * R;      // reverse-sweep row a sits in lane al of the pair
+                    const int32_t* __restrict__ p = HALF ? snap_task + (size_t)(hoff + al) * NRA_SNAP_LANE_STRIDE(R) + ai
+                                                         : snap_task + (size_t)ai * 64 + al;
+                    const int vh = p[0], ve = p[PL], ve2 = p[2 * PL];
                     h[s] = (s ? half_hi(vh) : half_lo(vh)) + 2 * o1;
                     e[s] = (s ? half_hi(ve) : half_lo(ve)) + q1;
                     e2[s] = (s ? half_hi(ve2) : half_lo(ve2)) + q2;
@@ -659,22 +675,23 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
 #pragma unroll
     for (int i = 0; i < R; ++i) { Hq[i] = s_relax > 0 ? v_floor | T2 : v_floor; Hq2[i] = NEG1; E[i] = NEG1; E2[i] = NEG1; }
 
-    // ring: padding columns everywhere, then lane 0's first `skew` columns
+    // ring: padding columns everywhere, then the first lane's first `skew` columns
 #pragma unroll
     for (int s = 0; s < SWEEP_RING_D; ++s) ring[s * 64 + lane] = make_int4(v_floor, NEG1, NEG1, tbl_mis4);
     racc[lane] = make_int2(NEG2, NEG1);
-    if (lane < skew) ring[lane * 64] = make_int4(v_floor, NEG1, NEG1, column_table(lane));
+    if (hl < skew) ring[hl * 64 + hoff] = make_int4(v_floor, NEG1, NEG1, column_table(hl));
     ring_order();
 
     int Hup_prev = s_relax > 0 ? v_floor | T2 : v_floor, M = BIAS * P1;      // (tainted, as Hq: the diagonal into row 0)
     int feed = tbl_mis4;
-    const int nsteps = ncols + 63 * skew;                   // lane 63 finishes the last column at step ncols - 1 + 63*skew
-    const int wr = (lane + 1) & 63;
+    const int nsteps = ncols + (W - 1) * skew;              // lane W - 1 finishes the last column at step ncols - 1 + (W - 1)*skew
+    const int nx = (hl + 1) & (W - 1);
+    const int wr = hoff | nx;
     const int s0 = QUANTA ? s_begin : 0, s1 = QUANTA ? (s_end < nsteps ? s_end : nsteps) : nsteps;
     if (QUANTA && load) {
         qstate_load<R>(qs, Hq, Hq2, E, E2, Hup_prev, M, ring, racc, out_a, out_b, lane);
         ring_order();
-        const SweepCounters c = sweep_counters_at(s0, jfirst, m, tk.kmin, tk.kmax, 63, 64);
+        const SweepCounters c = sweep_counters_at(s0, jfirst, m, tk.kmin, tk.kmax, W - 1, W);
         kcur = c.kcur; n_out = c.n_out;
     }
     int slot = QUANTA ? s0 % skew : 0;                      // step mod skew
@@ -682,7 +699,7 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
     const int a_of_a = COMB ? read_a[ra] : 0, a_of_b = COMB ? read_a[rb] : 0;
     int phase = jfirst % m;                                 // boundary steps: step mod m == phase, step >= jfirst
     int pcnt = QUANTA ? s0 % m : 0;                         // step mod m
-    int bidx = QUANTA ? sweep_counters_at(s0, jfirst, m, tk.kmin, tk.kmax, 63, 64).bidx : 0;      // boundary steps so far
+    int bidx = QUANTA ? sweep_counters_at(s0, jfirst, m, tk.kmin, tk.kmax, W - 1, W).bidx : 0;      // boundary steps so far
     int sx = s0;                                            // the first step of the exact cell
     if (TAINT && s0 < s_relax) {
         // the relaxed steps: columns of the anchor far from the junction (no boundary, snapshot or table flag among
@@ -691,13 +708,13 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
         const int flr = BIAS * P1 | T2, hfl = flr - v_o1, v_er = SC * imin(sp.ext1, sp.ext2) * P1;
 #pragma unroll 1
         for (int step = s0; step < sx; ++step) {
-            if ((step & 63) == 0) feed = column_table(step + skew + wr);
+            if ((step & (W - 1)) == 0) feed = column_table(step + skew + nx);
             const int4 in = ring[slot * 64 + lane];
             int F = pmaxi(in.y, flr);
             sweep_cell_relaxed<R>(Hq, E, qc, Hup_prev, F, M, in.w, tbl_hi, flr, v_er, v_o1);
             Hup_prev = pmaxi(in.x, hfl);
             ring[slot * 64 + wr] = make_int4(Hq[R - 1], F, F, in.w);
-            if (lane == 63) ring[slot * 64] = make_int4(v_floor, NEG1, NEG1, feed);
+            if (hl == W - 1) ring[slot * 64 + hoff] = make_int4(v_floor, NEG1, NEG1, feed);
             ring_order();
             feed = dpp_rol1(feed);
             if (++slot == skew) slot = 0;
@@ -707,24 +724,27 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
     if (TAINT && sx == s_relax && sx < s1) sweep_relax_switch<R>(Hq, Hq2, E, E2, v_o2 - v_o1);
 #pragma unroll 1
     for (int step = sx; step < s1; ++step) {
-        if ((step & 63) == 0) feed = column_table(step + skew + wr);      // lane 63 hands out column step + skew
+        // lane W - 1 hands out column step + skew.  (Both halves sweep the same template: the column tables repeat
+        // with period 32 across the wave, and a full-wave rotation keeps them so.)
+        if ((step & (W - 1)) == 0) feed = column_table(step + skew + nx);
         const int4 in = ring[slot * 64 + lane];
         const int tt = in.w;
         // the floor lives in F (sweep_cell, FF): score 0 with the origin bit of the next column.  What enters a
-        // lane's first row is at the floor already, but for lane 0, which takes constants: one max each
+        // lane's first row is at the floor already, but for a pair's first lane, which takes constants: one max each
         const int fl = DIR == 1 ? (int)((((unsigned)tt >> 15) & (unsigned)P1) | (unsigned)(BIAS * P1)) : BIAS * P1;
         int F = pmaxi(in.y, fl), F2 = in.z;
         sweep_cell<0, R, R, false, true>(Hq, Hq2, E, E2, qc, Hup_prev, F, F2, M, tt & 0x7f7f7f7f, tbl_hi, fl, v_e1, v_e2, v_o1, v_o2);
         Hup_prev = pmaxi(in.x, fl - v_o1);
         ring[slot * 64 + wr] = make_int4(Hq[R - 1], F, F2, tt);
-        if (lane == 63) ring[slot * 64] = make_int4(v_floor, NEG1, NEG1, feed);
+        if (hl == W - 1) ring[slot * 64 + hoff] = make_int4(v_floor, NEG1, NEG1, feed);
         ring_order();                                       // the next steps' loads stay behind these stores
         feed = dpp_rol1(feed);
         if (++slot == skew) slot = 0;
 
         if constexpr (DIR == 0) {
             if (tt & FLAG_SNAPSHOT) {
-                sweep_snapshot<0, R, R>(Hq, E, E2, snap_task, lane);
+                if constexpr (HALF) sweep_snapshot_lane<R>(Hq, E, E2, snap_task + (size_t)lane * NRA_SNAP_LANE_STRIDE(R));
+                else sweep_snapshot<0, R, R>(Hq, E, E2, snap_task, lane);
                 if (TAINT) sweep_rside_taint<R>(Hq, E, E2, T2, redo + task);
             }
         } else if constexpr (COMB) {
@@ -733,11 +753,11 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
                 const int2 acc = racc[lane];
                 const int accS = pmaxi(acc.x, tS), accB = pmaxi(acc.y, M);
                 racc[wr] = make_int2(accS, accB);
-                if (lane == 63) racc[0] = make_int2(NEG2, NEG1);
+                if (hl == W - 1) racc[hoff] = make_int2(NEG2, NEG1);
                 ring_order();
-                if (bidx >= 63 && kcur <= tk.kmax) {        // lane 63 is on the boundary of k = kcur
+                if (bidx >= W - 1 && kcur <= tk.kmax) {     // lane W - 1 of each pair is on the boundary of k = kcur
                     int va = 0, vb = 0;
-                    if (lane == 63) {
+                    if (hl == W - 1) {
 #pragma unroll
                         for (int s2 = 0; s2 < 2; ++s2) {
                             const int B = (s2 ? half_hi(accB) : half_lo(accB)) - BIAS;
@@ -754,10 +774,15 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
                             if (s2) vb = v; else va = v;
                         }
                     }
-                    out_a = dpp_rol1(out_a); out_b = dpp_rol1(out_b);
-                    if (lane == 63) { out_a = va; out_b = vb; }
+                    if constexpr (HALF) {                   // within the half: through the LDS crossbar
+                        out_a = __builtin_amdgcn_ds_bpermute(rot_src, out_a);
+                        out_b = __builtin_amdgcn_ds_bpermute(rot_src, out_b);
+                    } else {
+                        out_a = dpp_rol1(out_a); out_b = dpp_rol1(out_b);
+                    }
+                    if (hl == W - 1) { out_a = va; out_b = vb; }
                     ++kcur; ++n_out;
-                    if (n_out == 64) { flush(64); n_out = 0; }
+                    if (n_out == W) { flush(W); n_out = 0; }
                 }
                 ++bidx;
             }
@@ -768,10 +793,10 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
         qstate_store<R>(qs, Hq, Hq2, E, E2, Hup_prev, M, ring, racc, out_a, out_b, lane);
     } else if (DIR == 0) {
         // the short reverse sweep ends on its one boundary, R[0]: A = best alignment inside R (doubled)
-        // = the maximum over every cell of the sweep
+        // = the maximum over every cell of the pair's sweep
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) M = pmaxi(M, __shfl_xor(M, off, 64));
-        if (lane == 0) {
+        for (int off = W / 2; off > 0; off >>= 1) M = pmaxi(M, __shfl_xor(M, off, 64));
+        if (hl == 0 && half_on) {
             read_a[ra] = half_lo(M) - BIAS;
             if (has_b) read_a[rb] = half_hi(M) - BIAS;
         }
@@ -808,9 +833,9 @@ __global__ __launch_bounds__(WAVE * SWEEP_RING_WPB) void k_sweep_ring(int n_task
     if (task >= n_tasks) return;
     if (!TAINT && redo && redo[task] == 0) return;
     const int lane = SWEEP_RING_WPB > 1 ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
-    sweep_ring_body<R, HAS_N, DIR, DIR == 1, false, TAINT>(task, lane, ring, racc, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin_arr,
-                                                           kmax_arr, coff, snap, read_a, cand_score, cand_flag, nullptr, 0, 0, false, false,
-                                                           relax_c, redo);
+    sweep_ring_body<R, HAS_N, false, DIR, DIR == 1, false, TAINT>(task, lane, ring, racc, tasks, reads, regions, pool, q2bit, qnmask, sp,
+                                                                  kmin_arr, kmax_arr, coff, snap, read_a, cand_score, cand_flag, nullptr, 0,
+                                                                  0, false, false, relax_c, redo);
 }
 
 // ------------------------------------------------------------------------------------
@@ -822,245 +847,6 @@ __global__ __launch_bounds__(WAVE * SWEEP_RING_WPB) void k_sweep_ring(int n_task
 // template (same region, the union of the four reads' windows) in lock step, each with its own ring
 // (lane 31 hands out what enters lane 0, lane 63 what enters lane 32), so the overhead is paid once for four
 // reads and the pipeline is 32*skew columns deep.
-template <int R, bool HAS_N, int DIR, bool COMB, bool QUANTA, bool TAINT = false>   // COMB, QUANTA, TAINT and the arguments after cand_flag as in sweep_ring_body
-__device__ __forceinline__ void sweep_ring32_body(const int task, const int lane, int4* ring, int2* racc,
-                                                  const NraSweepTask* __restrict__ tasks,
-                                                  const NraDevRead* __restrict__ reads,
-                                                  const NraDevRegion* __restrict__ regions,
-                                                  const uint8_t* __restrict__ pool,
-                                                  const uint32_t* __restrict__ q2bit,
-                                                  const uint32_t* __restrict__ qnmask,
-                                                  NraScoreParams sp,
-                                                  const int32_t* __restrict__ kmin_arr,
-                                                  const int32_t* __restrict__ kmax_arr,
-                                                  const uint32_t* __restrict__ coff,
-                                                  int32_t* __restrict__ snap,
-                                                  int32_t* __restrict__ read_a,
-                                                  int32_t* __restrict__ cand_score,
-                                                  uint8_t* __restrict__ cand_flag,
-                                                  int32_t* __restrict__ qs, const int s_begin, const int s_end,
-                                                  const bool load, const bool store, const int relax_c = 0,
-                                                  int32_t* __restrict__ redo = nullptr)
-{
-    static_assert(DIR == 1 || !COMB, "only a forward sweep meets unit boundaries");
-    constexpr int SC = TAINT ? 4 : 2;
-    const int hoff = lane & 32;                           // first lane of this lane's half
-    const int hl = lane & 31;                             // lane within the half
-    const NraSweepTask tk = tasks[task];
-    // the half's own pair (a half without reads repeats pair a/b and stores nothing)
-    const bool half_on = hoff == 0 || tk.read_c >= 0;
-    const int r0 = (hoff && tk.read_c >= 0) ? tk.read_c : tk.read_a;
-    const int r1x = (hoff && tk.read_c >= 0) ? tk.read_d : tk.read_b;
-    const bool has_b = r1x >= 0;
-    const int ra = r0, rb = has_b ? r1x : r0;
-    const NraDevRead rda = reads[ra], rdb = reads[rb];
-    const NraDevRegion rg = regions[reads[tk.read_a].region];
-    const int m = rg.m1;
-    const int flank = DIR ? rg.l1 : rg.l3;
-    const uint8_t* __restrict__ piece = pool + (DIR ? rg.p1_off : rg.pr_off);
-    const int ncols = DIR ? flank + m * tk.kmax : flank;
-    const int jfirst = DIR ? flank + m * tk.kmin - 1 : flank - 1;
-    const int skew = DIR ? m : 1;
-    const int kmin_a = kmin_arr[ra], kmax_a = kmax_arr[ra];
-    const int kmin_b = kmin_arr[rb], kmax_b = kmax_arr[rb];
-    const uint32_t coff_a = coff[ra], coff_b = coff[rb];
-    int32_t* __restrict__ snap_task = snap + tk.snap_off;
-
-    const int o1 = SC * sp.open1, o2 = SC * sp.open2;
-    const int P1 = 0x00010001;
-    const int v_floor = (BIAS - o1) * P1;
-    const int v_o1 = o1 * P1, v_e1 = SC * sp.ext1 * P1, v_o2 = o2 * P1, v_e2 = SC * sp.ext2 * P1;
-    const int NEG1 = NEGB * P1, NEG2 = 2 * NEGB * P1;
-    const int s_match = SC * sp.match + o1, s_mis = o1 - SC * sp.mismatch, s_ambi = o1 - SC * sp.ambi;
-    const int tbl_hi = s_mis | (s_ambi << 8);
-    const int tbl_mis4 = s_mis * 0x01010101, tbl_ambi4 = s_ambi * 0x01010101;
-    const int s_relax = TAINT ? sweep_relax_steps(flank, relax_c) : 0;      // as in sweep_ring_body
-    const int T2 = 2 * P1;
-    constexpr int SH = TAINT ? 2 : 1;
-
-    auto column_table = [&](int col) {
-        int t = tbl_mis4;
-        if (col >= 0 && col < ncols) {
-            const int code = piece[col];
-            t = code < 4 ? tbl_mis4 + ((s_match - s_mis) << (8 * code)) : tbl_ambi4;
-            if (DIR == 0 && col == flank - 1) t |= FLAG_SNAPSHOT;
-            if (DIR == 1 && col + 1 >= flank) t |= FLAG_INREP;     // origin bit of an alignment starting at the NEXT column
-        }
-        return t;
-    };
-
-    // outputs: lane 31 / 63 produce one value per boundary; each half keeps its last 32 in a lane-indexed
-    // register (rotated within the half through the LDS crossbar) and writes them 32 candidates at a time
-    int out_a = 0, out_b = 0;
-    int n_out = 0, kcur = tk.kmin;                          // wave-uniform
-    const int rot_src = (hoff | ((hl + 1) & 31)) << 2;      // ds_bpermute address: the next lane of the half
-    auto flush = [&](int n_valid) {
-        const int k = kcur - 32 + hl;
-        if (hl < 32 - n_valid || !half_on) return;
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            if (s2 == 1 && !has_b) break;
-            const int lo_k = s2 ? kmin_b : kmin_a, hi_k = s2 ? kmax_b : kmax_a;
-            if (k < lo_k || k > hi_k) continue;
-            const uint32_t idx = (s2 ? coff_b : coff_a) + (uint32_t)(k - lo_k);
-            const int v = s2 ? out_b : out_a;
-            cand_score[idx] = v >> 2;
-            cand_flag[idx] = (uint8_t)(v & 3);
-        }
-    };
-
-    int qc[R];
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-        const int gi = hl * R + i;
-        const int ca = sweep_query_sel<HAS_N>(rda, q2bit, qnmask, gi, DIR == 0);
-        const int cb = sweep_query_sel<HAS_N>(rdb, q2bit, qnmask, gi, DIR == 0);
-        qc[i] = ca | (0x0c << 8) | (cb << 16) | (0x0c << 24);
-    }
-    int Hbo[COMB ? R : 1], Ebo[COMB ? R : 1], E2bo[COMB ? R : 1];
-    if (COMB) {
-        const int q1 = SC * (sp.open1 - sp.ext1), q2 = SC * (sp.open2 - sp.ext2);
-#pragma unroll
-        for (int i = 0; i < R; ++i) {
-            const int r = hl * R + i;
-            int h[2], e[2], e2[2];
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const int a = (s ? rdb.qlen : rda.qlen) - 2 - r;
-                if (a >= 0) {
-                    const int al = a / R, ai = a - al * R;      // reverse-sweep row a sits in lane al of this half
-                    const int32_t* __restrict__ p = snap_task + (size_t)(hoff + al) * NRA_SNAP_LANE_STRIDE(R) + ai;
-                    const int vh = p[0], ve = p[R], ve2 = p[2 * R];
-                    h[s] = (s ? half_hi(vh) : half_lo(vh)) + 2 * o1;
-                    e[s] = (s ? half_hi(ve) : half_lo(ve)) + q1;
-                    e2[s] = (s ? half_hi(ve2) : half_lo(ve2)) + q2;
-                } else { h[s] = BIAS + o1 - SC; e[s] = BIAS - SC; e2[s] = BIAS - SC; }
-            }
-            Hbo[i] = pack2(h[0], h[1]);
-            Ebo[i] = pack2(e[0], e[1]);
-            E2bo[i] = pack2(e2[0], e2[1]);
-        }
-    }
-    int Hq[R], Hq2[R], E[R], E2[R];
-#pragma unroll
-    for (int i = 0; i < R; ++i) { Hq[i] = s_relax > 0 ? v_floor | T2 : v_floor; Hq2[i] = NEG1; E[i] = NEG1; E2[i] = NEG1; }
-
-#pragma unroll
-    for (int s = 0; s < SWEEP_RING_D; ++s) ring[s * 64 + lane] = make_int4(v_floor, NEG1, NEG1, tbl_mis4);
-    racc[lane] = make_int2(NEG2, NEG1);
-    if (hl < skew) ring[hl * 64 + hoff] = make_int4(v_floor, NEG1, NEG1, column_table(hl));
-    ring_order();
-
-    int Hup_prev = s_relax > 0 ? v_floor | T2 : v_floor, M = BIAS * P1;
-    int feed = tbl_mis4;
-    const int nsteps = ncols + 31 * skew;                   // lanes 31 / 63 finish the last column at step ncols - 1 + 31*skew
-    const int wr = hoff | ((hl + 1) & 31);
-    const int s0 = QUANTA ? s_begin : 0, s1 = QUANTA ? (s_end < nsteps ? s_end : nsteps) : nsteps;
-    if (QUANTA && load) {
-        qstate_load<R>(qs, Hq, Hq2, E, E2, Hup_prev, M, ring, racc, out_a, out_b, lane);
-        ring_order();
-        const SweepCounters c = sweep_counters_at(s0, jfirst, m, tk.kmin, tk.kmax, 31, 32);
-        kcur = c.kcur; n_out = c.n_out;
-    }
-    int slot = QUANTA ? s0 % skew : 0;
-    const int a_of_a = COMB ? read_a[ra] : 0, a_of_b = COMB ? read_a[rb] : 0;
-    int phase = jfirst % m;
-    int pcnt = QUANTA ? s0 % m : 0;
-    int bidx = QUANTA ? sweep_counters_at(s0, jfirst, m, tk.kmin, tk.kmax, 31, 32).bidx : 0;
-    int sx = s0;                                            // the relaxed steps as in sweep_ring_body
-    if (TAINT && s0 < s_relax) {
-        sx = s1 < s_relax ? s1 : s_relax;
-        const int flr = BIAS * P1 | T2, hfl = flr - v_o1, v_er = SC * imin(sp.ext1, sp.ext2) * P1;
-#pragma unroll 1
-        for (int step = s0; step < sx; ++step) {
-            if ((step & 31) == 0) feed = column_table(step + skew + ((hl + 1) & 31));
-            const int4 in = ring[slot * 64 + lane];
-            int F = pmaxi(in.y, flr);
-            sweep_cell_relaxed<R>(Hq, E, qc, Hup_prev, F, M, in.w, tbl_hi, flr, v_er, v_o1);
-            Hup_prev = pmaxi(in.x, hfl);
-            ring[slot * 64 + wr] = make_int4(Hq[R - 1], F, F, in.w);
-            if (hl == 31) ring[slot * 64 + hoff] = make_int4(v_floor, NEG1, NEG1, feed);
-            ring_order();
-            feed = dpp_rol1(feed);
-            if (++slot == skew) slot = 0;
-        }
-        pcnt = sx % m;
-    }
-    if (TAINT && sx == s_relax && sx < s1) sweep_relax_switch<R>(Hq, Hq2, E, E2, v_o2 - v_o1);
-#pragma unroll 1
-    for (int step = sx; step < s1; ++step) {
-        // both halves sweep the same template: the column tables repeat with period 32 across the wave, and a
-        // full-wave rotation keeps them so
-        if ((step & 31) == 0) feed = column_table(step + skew + ((hl + 1) & 31));
-        const int4 in = ring[slot * 64 + lane];
-        const int tt = in.w;
-        const int fl = DIR == 1 ? (int)((((unsigned)tt >> 15) & (unsigned)P1) | (unsigned)(BIAS * P1)) : BIAS * P1;   // as in k_sweep_ring
-        int F = pmaxi(in.y, fl), F2 = in.z;
-        sweep_cell<0, R, R, false, true>(Hq, Hq2, E, E2, qc, Hup_prev, F, F2, M, tt & 0x7f7f7f7f, tbl_hi, fl, v_e1, v_e2, v_o1, v_o2);
-        Hup_prev = pmaxi(in.x, fl - v_o1);
-        ring[slot * 64 + wr] = make_int4(Hq[R - 1], F, F2, tt);
-        if (hl == 31) ring[slot * 64 + hoff] = make_int4(v_floor, NEG1, NEG1, feed);
-        ring_order();                                       // the next steps' loads stay behind these stores
-        feed = dpp_rol1(feed);
-        if (++slot == skew) slot = 0;
-
-        if constexpr (DIR == 0) {
-            if (tt & FLAG_SNAPSHOT) {
-                sweep_snapshot_lane<R>(Hq, E, E2, snap_task + (size_t)lane * NRA_SNAP_LANE_STRIDE(R));
-                if (TAINT) sweep_rside_taint<R>(Hq, E, E2, T2, redo + task);
-            }
-        } else if constexpr (COMB) {
-            if (pcnt == phase && step >= jfirst) {          // every lane is on a unit boundary: wave-uniform
-                const int tS = sweep_combine<0, R, R>(Hq, E, E2, Hbo, Ebo, E2bo, NEG2);
-                const int2 acc = racc[lane];
-                const int accS = pmaxi(acc.x, tS), accB = pmaxi(acc.y, M);
-                racc[wr] = make_int2(accS, accB);
-                if (hl == 31) racc[hoff] = make_int2(NEG2, NEG1);
-                ring_order();
-                if (bidx >= 31 && kcur <= tk.kmax) {        // lanes 31 and 63 are on the boundary of k = kcur
-                    int va = 0, vb = 0;
-                    if (hl == 31) {
-#pragma unroll
-                        for (int s2 = 0; s2 < 2; ++s2) {
-                            const int B = (s2 ? half_hi(accB) : half_lo(accB)) - BIAS;
-                            const int S = (s2 ? half_hi(accS) : half_lo(accS)) - 2 * BIAS;
-                            const int lo = sp.min_score > 1 ? sp.min_score : 1;
-                            const int V = imax(imax(S, B), (s2 ? a_of_b : a_of_a) + 1);
-                            const int best = V >> SH;
-                            int flag = 1;
-                            if (V & 1) flag = 0;
-                            else if ((B >> SH) >= best) flag = ((S >> SH) >= best) ? 2 : 0;
-                            if (TAINT && (V & 2)) redo[task] = 1;
-                            const int v = ((best >= lo ? best : -1) << 2) | flag;
-                            if (s2) vb = v; else va = v;
-                        }
-                    }
-                    out_a = __builtin_amdgcn_ds_bpermute(rot_src, out_a);
-                    out_b = __builtin_amdgcn_ds_bpermute(rot_src, out_b);
-                    if (hl == 31) { out_a = va; out_b = vb; }
-                    ++kcur; ++n_out;
-                    if (n_out == 32) { flush(32); n_out = 0; }
-                }
-                ++bidx;
-            }
-            if (++pcnt == m) pcnt = 0;
-        }
-    }
-    if (QUANTA && store) {
-        qstate_store<R>(qs, Hq, Hq2, E, E2, Hup_prev, M, ring, racc, out_a, out_b, lane);
-    } else if (DIR == 0) {
-        // A = best alignment inside R (doubled) = the maximum over every cell of the half's sweep
-#pragma unroll
-        for (int off = 16; off > 0; off >>= 1) M = pmaxi(M, __shfl_xor(M, off, 64));
-        if (hl == 0 && half_on) {
-            read_a[ra] = half_lo(M) - BIAS;
-            if (has_b) read_a[rb] = half_hi(M) - BIAS;
-        }
-    } else if (COMB && n_out > 0) {
-        flush(n_out);
-    }
-}
-
 template <int R, bool HAS_N, int DIR, bool TAINT>                     // relax_c, redo as in k_sweep_ring
 __global__ __launch_bounds__(WAVE) void k_sweep_ring32(int n_tasks, const NraSweepTask* __restrict__ tasks,
                                                        const NraDevRead* __restrict__ reads,
@@ -1082,9 +868,9 @@ __global__ __launch_bounds__(WAVE) void k_sweep_ring32(int n_tasks, const NraSwe
     const int task = blockIdx.x;
     if (task >= n_tasks) return;
     if (!TAINT && redo && redo[task] == 0) return;
-    sweep_ring32_body<R, HAS_N, DIR, DIR == 1, false, TAINT>(task, (int)threadIdx.x, ring, racc, tasks, reads, regions, pool, q2bit, qnmask,
-                                                             sp, kmin_arr, kmax_arr, coff, snap, read_a, cand_score, cand_flag, nullptr, 0,
-                                                             0, false, false, relax_c, redo);
+    sweep_ring_body<R, HAS_N, true, DIR, DIR == 1, false, TAINT>(task, (int)threadIdx.x, ring, racc, tasks, reads, regions, pool, q2bit,
+                                                                 qnmask, sp, kmin_arr, kmax_arr, coff, snap, read_a, cand_score, cand_flag,
+                                                                 nullptr, 0, 0, false, false, relax_c, redo);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1106,33 +892,7 @@ __global__ __launch_bounds__(WAVE) void k_sweep_ring32(int n_tasks, const NraSwe
 //     (cdna_hip_programming.md Guideline 16: plain payload, atomic flag, fences on both sides);
 //   * a cut costs no step: the dumped state is the skewed wave state, the pipeline is not drained.
 // A forward part that ends before the first boundary step (the columns of L) runs the plain body: no junction input, no combine.
-// (as real function calls -- noinline -- the bodies cost the calling convention's register reserve: 248 at R = 15)
-template <int R, bool HAS_N, bool HALF, int DIR, bool COMB, bool TAINT>
-__device__ __forceinline__ void sweep_quantum(const int task, const int lane, int4* ring, int2* racc,
-                                                        const NraSweepTask* __restrict__ tasks,
-                                                        const NraDevRead* __restrict__ reads,
-                                                        const NraDevRegion* __restrict__ regions,
-                                                        const uint8_t* __restrict__ pool,
-                                                        const uint32_t* __restrict__ q2bit,
-                                                        const uint32_t* __restrict__ qnmask,
-                                                        NraScoreParams sp,
-                                                        const int32_t* __restrict__ kmin_arr,
-                                                        const int32_t* __restrict__ kmax_arr,
-                                                        const uint32_t* __restrict__ coff,
-                                                        int32_t* __restrict__ snap,
-                                                        int32_t* __restrict__ read_a,
-                                                        int32_t* __restrict__ cand_score,
-                                                        uint8_t* __restrict__ cand_flag,
-                                                        int32_t* __restrict__ qs, const int s_begin, const int s_end,
-                                                        const bool load, const bool store, const int relax_c, int32_t* __restrict__ redo)
-{
-    if (HALF) sweep_ring32_body<R, HAS_N, DIR, COMB, true, TAINT>(task, lane, ring, racc, tasks, reads, regions, pool, q2bit, qnmask, sp,
-                                                                  kmin_arr, kmax_arr, coff, snap, read_a, cand_score, cand_flag, qs,
-                                                                  s_begin, s_end, load, store, relax_c, redo);
-    else sweep_ring_body<R, HAS_N, DIR, COMB, true, TAINT>(task, lane, ring, racc, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin_arr,
-                                                           kmax_arr, coff, snap, read_a, cand_score, cand_flag, qs, s_begin, s_end, load,
-                                                           store, relax_c, redo);
-}
+// (the body inlined: as a real function call -- noinline -- it costs the calling convention's register reserve: 248 at R = 15)
 
 // (waves per SIMD as the forward sweep alone: without the hint the merged body takes 226 registers at R = 15 where
 // k_sweep_ring's forward sweep takes 156; with it 168 and a few spilled values in the prologues -- the R side's
@@ -1211,9 +971,9 @@ __global__ __launch_bounds__(WAVE, ringq_waves(R)) void k_sweep_ringq(int n_quan
     // a slot per forward sweep, then -- where a reverse sweep has more than one part -- one per reverse sweep
     int32_t* __restrict__ qs = qstate + ((size_t)(dir ? 0 : n_tasks) + (size_t)task) * (NRA_QSTATE_INTS(R) * 64);
 #define NRA_Q_ARGS task, lane, ring, racc, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin_arr, kmax_arr, coff, snap, read_a, cand_score, cand_flag, qs, s_begin, s_end, load, store, relax_c, redo
-    if (!dir) sweep_quantum<R, HAS_N, HALF, 0, false, TAINT>(NRA_Q_ARGS);
-    else if (!comb) sweep_quantum<R, HAS_N, HALF, 1, false, TAINT>(NRA_Q_ARGS);
-    else sweep_quantum<R, HAS_N, HALF, 1, true, TAINT>(NRA_Q_ARGS);
+    if (!dir) sweep_ring_body<R, HAS_N, HALF, 0, false, true, TAINT>(NRA_Q_ARGS);
+    else if (!comb) sweep_ring_body<R, HAS_N, HALF, 1, false, true, TAINT>(NRA_Q_ARGS);
+    else sweep_ring_body<R, HAS_N, HALF, 1, true, true, TAINT>(NRA_Q_ARGS);
 #undef NRA_Q_ARGS
     // everything this wave stored -- the wave state at the cut, or the R side's snapshot and A -- before the arrival
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -1798,22 +1558,55 @@ static int launch_sweep(int R, int has_n, int chain, hipStream_t st, int n_tasks
     return (int)hipGetLastError();
 }
 
-template <int DIR>
-static int launch_sweep_ring(int R, int has_n, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
-                             const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                             const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                             const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                             int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo)
+// the LDS-ring sweeps; HALF: the half-wave kernels, two read pairs per wave (R <= NRA_RING32_MAX_R)
+template <int DIR, bool HALF>
+int launch_sweep_ring(int R, int has_n, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
+                      const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
+                      const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
+                      const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
+                      int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo)
 {
     if (n_tasks <= 0) return 0;
-    const int grid = (n_tasks + SWEEP_RING_WPB - 1) / SWEEP_RING_WPB;
+    const int grid = HALF ? n_tasks : (n_tasks + SWEEP_RING_WPB - 1) / SWEEP_RING_WPB;
 #define ARGS n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag, relax_c, redo
-#define CASE(r)                                                                                          \
-    case r:                                                                                              \
-        if (relax_c > 0) { if (has_n) k_sweep_ring<r, true, DIR, true><<<grid, WAVE * SWEEP_RING_WPB, 0, st>>>(ARGS);      \
-                           else k_sweep_ring<r, false, DIR, true><<<grid, WAVE * SWEEP_RING_WPB, 0, st>>>(ARGS); }          \
-        else { if (has_n) k_sweep_ring<r, true, DIR, false><<<grid, WAVE * SWEEP_RING_WPB, 0, st>>>(ARGS);                  \
-               else k_sweep_ring<r, false, DIR, false><<<grid, WAVE * SWEEP_RING_WPB, 0, st>>>(ARGS); }                     \
+#define LAUNCH(r, n, t)                                                                         \
+    {                                                                                           \
+        if constexpr (HALF) k_sweep_ring32<r, n, DIR, t><<<grid, WAVE, 0, st>>>(ARGS);         \
+        else k_sweep_ring<r, n, DIR, t><<<grid, WAVE * SWEEP_RING_WPB, 0, st>>>(ARGS);         \
+    }
+#define CASE(r)                                                                                 \
+    case r:                                                                                     \
+        if constexpr (HALF && r > NRA_RING32_MAX_R) return (int)hipErrorInvalidValue;           \
+        else if (relax_c > 0) { if (has_n) LAUNCH(r, true, true) else LAUNCH(r, false, true) }  \
+        else { if (has_n) LAUNCH(r, true, false) else LAUNCH(r, false, false) }                 \
+        break;
+    switch (R) {
+        NRA_R_LIST(CASE)
+    default: return (int)hipErrorInvalidValue;
+    }
+#undef CASE
+#undef LAUNCH
+#undef ARGS
+    return (int)hipGetLastError();
+}
+
+template <bool HALF>
+int launch_sweep_ringq(int R, int has_n, hipStream_t st, int n_quanta, const uint32_t* qlist, int qsteps, int n_tasks, int32_t* ticket,
+                       int32_t* arrivals, int32_t* giveup, int32_t* qstate, const NraSweepTask* tasks,
+                       const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
+                       const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
+                       const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
+                       int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo)
+{
+    if (n_quanta <= 0) return 0;
+#define ARGS n_quanta, qlist, qsteps, n_tasks, ticket, arrivals, giveup, qstate, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag, relax_c, redo
+#define CASE(r)                                                                                                          \
+    case r:                                                                                                              \
+        if constexpr (HALF && r > NRA_RING32_MAX_R) return (int)hipErrorInvalidValue;                                   \
+        else if (relax_c > 0) { if (has_n) k_sweep_ringq<r, true, HALF, true><<<n_quanta, WAVE, 0, st>>>(ARGS);          \
+                                else k_sweep_ringq<r, false, HALF, true><<<n_quanta, WAVE, 0, st>>>(ARGS); }             \
+        else { if (has_n) k_sweep_ringq<r, true, HALF, false><<<n_quanta, WAVE, 0, st>>>(ARGS);                          \
+               else k_sweep_ringq<r, false, HALF, false><<<n_quanta, WAVE, 0, st>>>(ARGS); }                             \
         break;
     switch (R) {
         NRA_R_LIST(CASE)
@@ -1824,27 +1617,63 @@ static int launch_sweep_ring(int R, int has_n, hipStream_t st, int n_tasks, cons
     return (int)hipGetLastError();
 }
 
+// The half-wave kernels compile in parts of their own (build.py): each of those parts instantiates its launcher, and the
+// extern "C" launchers of parts 11, 12 and 25 call it.
+#define NRA_SPEC(...) decltype(__VA_ARGS__) __VA_ARGS__
+#if NRA_HAS_PART(15)
+template NRA_SPEC(launch_sweep_ring<0, true>);
+#else
+extern template NRA_SPEC(launch_sweep_ring<0, true>);
+#endif
+#if NRA_HAS_PART(16)
+template NRA_SPEC(launch_sweep_ring<1, true>);
+#else
+extern template NRA_SPEC(launch_sweep_ring<1, true>);
+#endif
+#if NRA_HAS_PART(26)
+template NRA_SPEC(launch_sweep_ringq<true>);
+#else
+extern template NRA_SPEC(launch_sweep_ringq<true>);
+#endif
+#undef NRA_SPEC
+
 #if NRA_HAS_PART(11)
-extern "C" int nra_launch_sweep_ring_bwd(int R, int has_n, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
+extern "C" int nra_launch_sweep_ring_bwd(int R, int has_n, int half, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
                                          const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
                                          const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
                                          const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
                                          int32_t* snap, int32_t* read_a, int relax_c, int32_t* redo)
 {
-    return launch_sweep_ring<0>(R, has_n, st, n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax,
-                                coff, snap, read_a, nullptr, nullptr, relax_c, redo);
+    return (half ? launch_sweep_ring<0, true> : launch_sweep_ring<0, false>)(R, has_n, st, n_tasks, tasks, reads, regions, pool, q2bit,
+                                                                              qnmask, sp, kmin, kmax, coff, snap, read_a, nullptr,
+                                                                              nullptr, relax_c, redo);
 }
 #endif
 #if NRA_HAS_PART(12)
-extern "C" int nra_launch_sweep_ring_fwd(int R, int has_n, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
+extern "C" int nra_launch_sweep_ring_fwd(int R, int has_n, int half, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
                                          const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
                                          const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
                                          const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
                                          int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag,
                                          int relax_c, int32_t* redo)
 {
-    return launch_sweep_ring<1>(R, has_n, st, n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax,
-                                coff, snap, read_a, cand_score, cand_flag, relax_c, redo);
+    return (half ? launch_sweep_ring<1, true> : launch_sweep_ring<1, false>)(R, has_n, st, n_tasks, tasks, reads, regions, pool, q2bit,
+                                                                              qnmask, sp, kmin, kmax, coff, snap, read_a, cand_score,
+                                                                              cand_flag, relax_c, redo);
+}
+#endif
+#if NRA_HAS_PART(25)
+extern "C" int nra_launch_sweep_ringq(int R, int has_n, int half, hipStream_t st, int n_quanta, const uint32_t* qlist, int qsteps,
+                                      int n_tasks, int32_t* ticket, int32_t* arrivals, int32_t* giveup, int32_t* qstate,
+                                      const NraSweepTask* tasks, const NraDevRead* reads, const NraDevRegion* regions,
+                                      const uint8_t* pool, const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
+                                      const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
+                                      int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo)
+{
+    return (half ? launch_sweep_ringq<true> : launch_sweep_ringq<false>)(R, has_n, st, n_quanta, qlist, qsteps, n_tasks, ticket, arrivals,
+                                                                          giveup, qstate, tasks, reads, regions, pool, q2bit, qnmask,
+                                                                          sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag,
+                                                                          relax_c, redo);
 }
 #endif
 
@@ -1873,109 +1702,6 @@ static int launch_sweep_ringchain(int R, int has_n, int wide, hipStream_t st, in
 #undef ARGS
     return (int)hipGetLastError();
 }
-
-template <int DIR>
-static int launch_sweep_ring32(int R, int has_n, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
-                               const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                               const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                               const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                               int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo)
-{
-    if (n_tasks <= 0) return 0;
-#define ARGS n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag, relax_c, redo
-#define CASE(r)                                                                                                  \
-    case r:                                                                                                      \
-        if (relax_c > 0) { if (has_n) k_sweep_ring32<r, true, DIR, true><<<n_tasks, WAVE, 0, st>>>(ARGS);       \
-                           else k_sweep_ring32<r, false, DIR, true><<<n_tasks, WAVE, 0, st>>>(ARGS); }           \
-        else { if (has_n) k_sweep_ring32<r, true, DIR, false><<<n_tasks, WAVE, 0, st>>>(ARGS);                   \
-               else k_sweep_ring32<r, false, DIR, false><<<n_tasks, WAVE, 0, st>>>(ARGS); }                      \
-        break;
-    switch (R) {
-        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13)
-        CASE(14) CASE(15) CASE(16) CASE(18) CASE(20) CASE(22) CASE(24)
-    default: return (int)hipErrorInvalidValue;
-    }
-#undef CASE
-#undef ARGS
-    return (int)hipGetLastError();
-}
-
-// k_sweep_ringq launchers: `half` = the half-wave kernel's buckets (two read pairs per wave, R <= NRA_RING32_MAX_R)
-#define NRA_Q_LAUNCH_ARGS n_quanta, qlist, qsteps, n_tasks, ticket, arrivals, giveup, qstate, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag, relax_c, redo
-#if NRA_HAS_PART(25)
-extern "C" int nra_launch_sweep_ringq(int R, int has_n, hipStream_t st, int n_quanta, const uint32_t* qlist, int qsteps, int n_tasks, int32_t* ticket,
-                                      int32_t* arrivals, int32_t* giveup, int32_t* qstate, const NraSweepTask* tasks,
-                                      const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                      const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                      const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                      int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo)
-{
-    if (n_quanta <= 0) return 0;
-#define CASE(r)                                                                                                          \
-    case r:                                                                                                              \
-        if (relax_c > 0) { if (has_n) k_sweep_ringq<r, true, false, true><<<n_quanta, WAVE, 0, st>>>(NRA_Q_LAUNCH_ARGS); \
-                           else k_sweep_ringq<r, false, false, true><<<n_quanta, WAVE, 0, st>>>(NRA_Q_LAUNCH_ARGS); }    \
-        else { if (has_n) k_sweep_ringq<r, true, false, false><<<n_quanta, WAVE, 0, st>>>(NRA_Q_LAUNCH_ARGS);            \
-               else k_sweep_ringq<r, false, false, false><<<n_quanta, WAVE, 0, st>>>(NRA_Q_LAUNCH_ARGS); }               \
-        break;
-    switch (R) {
-        NRA_R_LIST(CASE)
-    default: return (int)hipErrorInvalidValue;
-    }
-#undef CASE
-    return (int)hipGetLastError();
-}
-#endif
-#if NRA_HAS_PART(26)
-extern "C" int nra_launch_sweep_ringq32(int R, int has_n, hipStream_t st, int n_quanta, const uint32_t* qlist, int qsteps, int n_tasks, int32_t* ticket,
-                                        int32_t* arrivals, int32_t* giveup, int32_t* qstate, const NraSweepTask* tasks,
-                                        const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                        const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                        const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                        int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo)
-{
-    if (n_quanta <= 0) return 0;
-#define CASE(r)                                                                                                          \
-    case r:                                                                                                              \
-        if (relax_c > 0) { if (has_n) k_sweep_ringq<r, true, true, true><<<n_quanta, WAVE, 0, st>>>(NRA_Q_LAUNCH_ARGS);  \
-                           else k_sweep_ringq<r, false, true, true><<<n_quanta, WAVE, 0, st>>>(NRA_Q_LAUNCH_ARGS); }     \
-        else { if (has_n) k_sweep_ringq<r, true, true, false><<<n_quanta, WAVE, 0, st>>>(NRA_Q_LAUNCH_ARGS);             \
-               else k_sweep_ringq<r, false, true, false><<<n_quanta, WAVE, 0, st>>>(NRA_Q_LAUNCH_ARGS); }                \
-        break;
-    switch (R) {
-        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13)
-        CASE(14) CASE(15) CASE(16) CASE(18) CASE(20) CASE(22) CASE(24)
-    default: return (int)hipErrorInvalidValue;
-    }
-#undef CASE
-    return (int)hipGetLastError();
-}
-#endif
-#undef NRA_Q_LAUNCH_ARGS
-
-#if NRA_HAS_PART(15)
-extern "C" int nra_launch_sweep_ring32_bwd(int R, int has_n, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
-                                           const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                           const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                           const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                           int32_t* snap, int32_t* read_a, int relax_c, int32_t* redo)
-{
-    return launch_sweep_ring32<0>(R, has_n, st, n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax,
-                                  coff, snap, read_a, nullptr, nullptr, relax_c, redo);
-}
-#endif
-#if NRA_HAS_PART(16)
-extern "C" int nra_launch_sweep_ring32_fwd(int R, int has_n, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
-                                           const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                           const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                           const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                           int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag,
-                                           int relax_c, int32_t* redo)
-{
-    return launch_sweep_ring32<1>(R, has_n, st, n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax,
-                                  coff, snap, read_a, cand_score, cand_flag, relax_c, redo);
-}
-#endif
 
 #if NRA_HAS_PART(13)
 extern "C" int nra_launch_sweep_ringchain_bwd(int R, int has_n, int wide, hipStream_t st, int n_tasks,
