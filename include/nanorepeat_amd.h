@@ -428,6 +428,34 @@ int nra_read_structure(int device, int32_t n_motifs, const char* motifs, const i
 int nra_tract_motifs(int device, int32_t n_tracts, const char* seqs, const int64_t* seq_off, int32_t max_period,
                      int32_t top_n, int32_t* n_tandem, int8_t* top_p, int32_t* top_code, int32_t* top_count);
 
+/* ---- anchored extension: how many repeat units a tract shows from one anchored end (no counterpart in the reference)
+ *
+ * For a read with one anchor only: the sequence s that follows the anchor (n bases, upper-cased first; a byte other
+ * than ACGT mismatches every motif base) is extended along its motif u (p bases, 1 <= p <= 64, uppercase ACGT) repeated
+ * without end, anchored at its first base, free at its far end.  Scores match = a, mismatch = b, gap = g
+ * (1 <= a <= 127, 0 <= b <= 127, 1 <= g <= 127).  Each cell holds a score H and a count M of motif bases consumed;
+ * phase j = motif bases consumed mod p.
+ *   H[0][j] = 0, M[0][j] = 0                        anchored at row 0, any start phase; no zero floor later
+ *   for i >= 1, c = s[i-1], k = (j-1) mod p:
+ *     diagonal  H[i-1][k] + (c == u[k] ? a : -b),   count M[i-1][k] + 1
+ *     insertion H[i-1][j] - g,                      count M[i-1][j]
+ *     T[j] = the larger; a tie takes the diagonal
+ *     H[i][j] = max over d = 0..p-1 of T[(j-d) mod p] - g*d, count + d    (d motif bases deleted);
+ *               among equal values the smallest d wins
+ *   best = the largest H[i][j] over i >= 0; among equals the smallest i, then the smallest j.
+ * Outputs per sequence: score = best H (0 with end = 0 when nothing is positive), end = that i, end_phase = that j,
+ * motif_bases = that M.  motif_bases / p is the number of repeat units the sequence shows next to its anchor: a lower
+ * bound from one read, not an allele size.  DESIGN.md section 16. */
+
+/* Motifs and reads as for nra_read_structure (read r: at most 200 000 bases, NRA_E_RANGE beyond; a motif of 0 bases
+ * or with a byte other than A, C, G, T is NRA_E_ARG, one of more than 64 bases NRA_E_RANGE); a score outside its range
+ * is NRA_E_ARG.  Writes score[r], end[r], end_phase[r], motif_bases[r].  Arguments are checked before the device is
+ * touched. */
+int nra_extend_tracts(int device, int32_t n_motifs, const char* motifs, const int64_t* motif_off,
+                      int32_t n_reads, const char* seqs, const int64_t* seq_off, const int32_t* read_motif,
+                      int32_t match, int32_t mismatch, int32_t gap,
+                      int32_t* score, int32_t* end, int32_t* end_phase, int32_t* motif_bases);
+
 #ifdef __cplusplus
 }
 #endif

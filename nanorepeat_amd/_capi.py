@@ -34,7 +34,7 @@ EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count
            "nra_batch2d_create", "nra_batch2d_create_reads", "nra_batch2d_set_cells", "nra_joint_grid_cells", "nra_batch2d_set_grid", "nra_batch2d_invalidate", "nra_batch2d_sweep_flanks", "nra_batch2d_refine", "nra_batch_run", "nra_batch_sync", "nra_batch_stats",
            "nra_batch1d_fetch", "nra_batch1d_resweeps", "nra_batch2d_fetch", "nra_batch_destroy",
            "nra_screen_create", "nra_screen_reads", "nra_screen_stats", "nra_screen_destroy",
-           "nra_read_structure", "nra_tract_motifs")
+           "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts")
 
 
 E_RANGE = -3      # NRA_E_RANGE
@@ -176,6 +176,9 @@ def load():
     lib.nra_tract_motifs.restype = C.c_int
     lib.nra_tract_motifs.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, C.c_int32, C.c_int32, pi32,
                                      C.POINTER(C.c_int8), pi32, pi32]
+    lib.nra_extend_tracts.restype = C.c_int
+    lib.nra_extend_tracts.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, C.c_int32, C.c_char_p, pi64, pi32,
+                                      C.c_int32, C.c_int32, C.c_int32, pi32, pi32, pi32, pi32]
     _LIB = lib
     return lib
 
@@ -652,4 +655,21 @@ def tract_motifs(tracts, max_period=6, top_n=4, device=0):
     _check(lib.nra_tract_motifs(device, n, data, _ptr(off, C.c_int64), max_period, top_n,
                                 _ptr(out["n_tandem"], C.c_int32), _ptr(out["top_p"], C.c_int8),
                                 _ptr(out["top_code"], C.c_int32), _ptr(out["top_count"], C.c_int32)))
+    return out
+
+
+def extend_tracts(motifs, tracts, read_motif, match=2, mismatch=4, gap=6, device=0):
+    """nra_extend_tracts: the anchored wraparound extension of every tract along its motif (motifs[read_motif[i]]) ->
+    dict(score, end, end_phase, motif_bases), int32 per tract."""
+    lib = load()
+    mdata, moff = pack_reads(list(motifs))
+    data, off = pack_reads(tracts)
+    rm = np.ascontiguousarray(read_motif, np.int32)
+    n = len(tracts)
+    if len(rm) != n:
+        raise ValueError("one motif index per tract")
+    out = {key: np.zeros(n, np.int32) for key in ("score", "end", "end_phase", "motif_bases")}
+    _check(lib.nra_extend_tracts(device, len(motifs), mdata, _ptr(moff, C.c_int64), n, data, _ptr(off, C.c_int64),
+                                 _ptr(rm, C.c_int32), match, mismatch, gap,
+                                 *(_ptr(out[key], C.c_int32) for key in ("score", "end", "end_phase", "motif_bases"))))
     return out

@@ -266,6 +266,11 @@ int nra_launch_screen_hits(hipStream_t st, int64_t n_tiles, const NraScreenTile*
 int nra_launch_structure(hipStream_t st, int P, int n_reads, const NraStructRead* reads, const NraStructMotif* motifs,
                          const uint8_t* codes, uint32_t* ptrs, uint8_t* path, int32_t* res);
 
+// anchored extension (nra_extend.hip): one lane per read, forward only, reads and motifs as for nra_launch_structure
+// (NraStructRead.ptr unused).  P in {1..6, 8, 16, 32, 64}; res[4 i ..] = score, end row, end phase, motif bases of read i
+int nra_launch_extend(hipStream_t st, int P, int n_reads, const NraStructRead* reads, const NraStructMotif* motifs,
+                      const uint8_t* codes, int match, int mismatch, int gap, int32_t* res);
+
 // tandem motifs (nra_motif.hip): one wave per tract, n_grid workgroups of four waves.  n_tandem[t * 6 + p - 1] and
 // top_key[t * 8 + q] (count << 10 | (1023 - dense id), 0 for an unused slot) for q < top_n
 int nra_launch_tract_motifs(hipStream_t st, int n_grid, int n_tracts, const NraMotifTract* tracts,

@@ -146,7 +146,7 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
                       fast_mode=False, ploidy=2, max_mutual_overlap=0.15, max_num_components=-1,
                       remove_noisy_reads=False, no_check_repeat_motif_in_ref=False, no_details=False,
                       num_cpu=1, device=0, scoring=None, seed=None, read_structure=False, discover_motifs=False,
-                      min_motif_count=4, min_motif_share=0.1, **engines):
+                      min_motif_count=4, min_motif_share=0.1, partial_reads=False, **engines):
     """The BAM command from files to files (nanoRepeat_bam.py:614-751): for every region of the BED
     file, reads from the alignment file -> `<out_prefix>.details/<chr>/<region>.*` ->
     `<out_prefix>.NanoRepeat_output.tsv`.  The reference forks up to 16 workers, one region each;
@@ -154,8 +154,10 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
     without reads, or whose reference sequence fails the motif check, get their row with 0
     alleles like in the reference.  read_structure=True adds the repeat structure files
     (structure.py); discover_motifs=True adds the tandem motif files (motifs.py; min_motif_count and
-    min_motif_share set the per-read call).  `engines` may carry aligner / scorer / structure_engine /
-    motif_engine stand-ins.  Returns the regions."""
+    min_motif_share set the per-read call); partial_reads=True adds the one-anchor read files (partial.py): for
+    every read with one anchor only, the repeat units it shows next to that anchor, and per region whether any such
+    read shows more than the largest spanning read.  `engines` may carry aligner / scorer / structure_engine /
+    motif_engine / extension_engine stand-ins.  Returns the regions."""
     from . import bam as nr_bam
     regions = nr_io.read_repeat_region_file(repeat_region_bed, no_details)
     ref_fasta_dict = nr_io.fasta_file2dict(ref_fasta)
@@ -172,7 +174,8 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
         reads_of.append(nr_io.read_fastq(region.region_fq_file))
     _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
-                        read_structure, _motif_options(discover_motifs, min_motif_count, min_motif_share))
+                        read_structure, _motif_options(discover_motifs, min_motif_count, min_motif_share),
+                        partial_reads)
     return regions
 
 
@@ -193,10 +196,12 @@ def _motif_options(discover_motifs, min_motif_count, min_motif_share):
 
 def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
-                        read_structure=False, motif_options=None):
+                        read_structure=False, motif_options=None, partial_reads=False):
     """The commands' common tail: steps 1-4 for the regions with reads, then one TSV row per BED region; with
     read_structure, the structure of every read with a size and the two structure files; with motif_options (a dict
-    of motifs.motif_regions keywords), the tandem motifs of every read with a core and the two motif files."""
+    of motifs.motif_regions keywords), the tandem motifs of every read with a core and the two motif files; with
+    partial_reads, the extension of every one-anchor read, the two partial-read files and a NOTICE per region where
+    such reads show more repeat units than any spanning read."""
     quantify_regions(live, reads_of, data_type, fast_mode, num_cpu, device, scoring,
                      engines.get("aligner"), engines.get("scorer"))
     phase_regions(live, data_type, ploidy, max_mutual_overlap, max_num_components, remove_noisy_reads, seed)
@@ -216,6 +221,13 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
         for region in live:
             motifs.write_read_motifs(region)
         motifs.write_motif_summary(regions, out_prefix)
+    if partial_reads:
+        from . import partial
+        partial.partial_regions(live, reads_of, device=device, scoring=scoring, engine=engines.get("extension_engine"))
+        for region in live:
+            partial.write_partial_reads(region)
+        partial.write_partial_summary(regions, out_prefix)
+        partial.report_exceeding_reads(live)
     if no_details:
         import shutil
         shutil.rmtree(f"{out_prefix}.details", ignore_errors=True)

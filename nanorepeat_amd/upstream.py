@@ -71,6 +71,7 @@ def find_anchor_locations_for1read(read_paf_list, repeat_region):
     ranked = {side: sorted((p for p in read_paf_list if p.tname.startswith(side + "_anchor")),
                            key=lambda p: -p.align_score) for side in ("left", "right")}
     if not (check_anchor_mapping(ranked["left"]) and check_anchor_mapping(ranked["right"])):
+        _record_one_anchor_read(ranked, repeat_region)
         return
     left, right = ranked["left"][0], ranked["right"][0]
     # anchors on opposite strands keep a gap of 0 and pass, as upstream (:207-212)
@@ -89,6 +90,19 @@ def find_anchor_locations_for1read(read_paf_list, repeat_region):
     read.right_buffer_len = read.core_seq_end_pos - right.qstart
     repeat_region.buffer_len = CORE_BUFFER
     repeat_region.read_dict[read.read_name] = read
+
+
+def _record_one_anchor_read(ranked, repeat_region):
+    """A read that is not placed, with one side's hits passing check_anchor_mapping and no hit at all on the other
+    side, starts in one flank and ends inside the repeat (or the other way round): it is kept as
+    `repeat_region.one_anchor_reads[name] = (side, best hit)` for partial.py.  The reference drops it without a
+    word.  A read whose other side has hits that fail the check is ambiguous and is not kept; nothing else changes."""
+    for side, other in (("left", "right"), ("right", "left")):
+        if check_anchor_mapping(ranked[side]) and not ranked[other]:
+            kept = getattr(repeat_region, "one_anchor_reads", None)
+            if kept is None:
+                kept = repeat_region.one_anchor_reads = {}
+            kept[ranked[side][0].qname] = (side, ranked[side][0])
 
 
 def find_anchor_locations_in_reads(data_type, repeat_region, num_cpu=1, region_reads=None, device=0,
