@@ -456,6 +456,37 @@ int nra_extend_tracts(int device, int32_t n_motifs, const char* motifs, const in
                       int32_t match, int32_t mismatch, int32_t gap,
                       int32_t* score, int32_t* end, int32_t* end_phase, int32_t* motif_bases);
 
+/* ---- mixture fits: the diagonal Gaussian mixtures of the phasing step, many fits in one call
+ *
+ * One fit of n components to the N x d sample X (float64, d = 1 or 2) from n start rows, everything in float64:
+ *   1. means = the start rows.  labels = nearest mean (squared distance summed over the axes; a tie goes to the lowest
+ *      component).  Up to 10 Lloyd steps: the mean of a component with points becomes the mean of its points, one
+ *      without keeps its mean, relabel; stop early when no label changes.
+ *   2. responsibilities r = one-hot labels, then the M-step of a diagonal mixture:
+ *      nk = sum r + 10 eps (eps = 2^-52), mu = sum r x / nk, var = sum r x^2 / nk - mu^2 + 1e-6, w = nk / N.
+ *   3. E-step: log p(x, c) = log w_c - (d log 2 pi + sum log var_c) / 2 - sum (x - mu_c)^2 / var_c / 2 (sums over the
+ *      axes), log p(x) by log-sum-exp over c, r = exp(log p(x, c) - log p(x)), lb = mean of log p(x) over the points;
+ *      then the M-step on r.  Stop after the M-step of the first E-step whose |lb - lb of the E-step before| < 1e-3
+ *      (converged = 1), or after 100 E-steps (converged = 0).
+ * Outputs per fit: lb of its last E-step, n_iter = E-steps, converged, and w, mu, var of its last M-step.  A fit is
+ * a function of its sample and its start rows alone: not of the other fits of the call, their order, or the run.
+ * DESIGN.md section 17. */
+
+/* flags of nra_mixture_fit, for tests and comparisons: the results do not depend on them */
+#define NRA_MIX_STREAM     1   /* every problem streams its points from memory, also one that fits in registers */
+#define NRA_MIX_ONE_CLASS  2   /* no separate kernel for problems of up to 1024 points */
+
+/* Problem p = prob_n[p] rows of prob_d[p] doubles from samples[prob_off[p]] (of n_samples doubles in all; problems may
+ * share rows).  Fit f = fit_n[f] components on problem fit_problem[f]; its start rows are the next fit_n[f] entries of
+ * `starts`, fits in order.  Writes lb[f], n_iter[f], converged[f], and with o = fit_n[0] + ... + fit_n[f-1]:
+ * w[o + c], mu[2 (o + c) + axis], var[2 (o + c) + axis] (axis 1 is 0 where d = 1).  d other than 1 or 2, a problem
+ * without points or outside the samples, a value that is not finite, n < 1, n > N or a start row >= N is NRA_E_ARG;
+ * n > 32 or N > 4 194 304 is NRA_E_RANGE.  Arguments are checked before the device is touched. */
+int nra_mixture_fit(int device, int64_t n_samples, const double* samples, int32_t n_problems, const int64_t* prob_off,
+                    const int32_t* prob_n, const int32_t* prob_d, int32_t n_fits, const int32_t* fit_problem,
+                    const int32_t* fit_n, const int32_t* starts, int32_t flags,
+                    double* lb, double* w, double* mu, double* var, int32_t* n_iter, int32_t* converged);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,8 @@ F_JOINT_NO_CHAIN = 512  # testing / comparison, 2D routed grids: the MID part as
 F_NO_QUANTA = 2048    # testing / comparison, 1D: reverse and forward sweeps as two launches instead of one launch of quanta taken by ticket
 F_QUANTA_2L = 4096    # accepted and ignored (round 4's first form of the quanta as two launches)
 F_SERIAL_CHAIN = 128  # testing / comparison, 1D: a long read's row blocks one after the other in one wave
+MIX_STREAM = 1        # testing / comparison, nra_mixture_fit: every problem streams its points from memory
+MIX_ONE_CLASS = 2     # testing / comparison, nra_mixture_fit: no separate kernel for problems of up to 1024 points
 F_FULL_ANCHORS = 8192  # testing / comparison, 1D: the exact cell over every anchor column (no relaxed cells, no re-sweep)
 
 # every symbol include/nanorepeat_amd.h declares
@@ -34,7 +36,7 @@ EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count
            "nra_batch2d_create", "nra_batch2d_create_reads", "nra_batch2d_set_cells", "nra_joint_grid_cells", "nra_batch2d_set_grid", "nra_batch2d_invalidate", "nra_batch2d_sweep_flanks", "nra_batch2d_refine", "nra_batch_run", "nra_batch_sync", "nra_batch_stats",
            "nra_batch1d_fetch", "nra_batch1d_resweeps", "nra_batch2d_fetch", "nra_batch_destroy",
            "nra_screen_create", "nra_screen_reads", "nra_screen_stats", "nra_screen_destroy",
-           "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts")
+           "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts", "nra_mixture_fit")
 
 
 E_RANGE = -3      # NRA_E_RANGE
@@ -179,6 +181,9 @@ def load():
     lib.nra_extend_tracts.restype = C.c_int
     lib.nra_extend_tracts.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, C.c_int32, C.c_char_p, pi64, pi32,
                                       C.c_int32, C.c_int32, C.c_int32, pi32, pi32, pi32, pi32]
+    lib.nra_mixture_fit.restype = C.c_int
+    lib.nra_mixture_fit.argtypes = [C.c_int, C.c_int64, pf64, C.c_int32, pi64, pi32, pi32, C.c_int32, pi32, pi32, pi32,
+                                    C.c_int32, pf64, pf64, pf64, pf64, pi32, pi32]
     _LIB = lib
     return lib
 
@@ -672,4 +677,34 @@ def extend_tracts(motifs, tracts, read_motif, match=2, mismatch=4, gap=6, device
     _check(lib.nra_extend_tracts(device, len(motifs), mdata, _ptr(moff, C.c_int64), n, data, _ptr(off, C.c_int64),
                                  _ptr(rm, C.c_int32), match, mismatch, gap,
                                  *(_ptr(out[key], C.c_int32) for key in ("score", "end", "end_phase", "motif_bases"))))
+    return out
+
+
+def mixture_fit(samples, prob_off, prob_n, prob_d, fit_problem, fit_n, starts, flags=0, device=0):
+    """nra_mixture_fit: fit f = fit_n[f] components on problem fit_problem[f] (prob_n[p] rows of prob_d[p] float64 from
+    samples[prob_off[p]]) from the next fit_n[f] rows of `starts` -> dict(lb, n_iter, converged per fit; off = where a
+    fit's components begin; w [components], mu and var [components, 2])."""
+    lib = load()
+    x = np.ascontiguousarray(samples, np.float64).ravel()
+    po = np.ascontiguousarray(prob_off, np.int64)
+    pn = np.ascontiguousarray(prob_n, np.int32)
+    pd = np.ascontiguousarray(prob_d, np.int32)
+    fp = np.ascontiguousarray(fit_problem, np.int32)
+    fn = np.ascontiguousarray(fit_n, np.int32)
+    st = np.ascontiguousarray(starts, np.int32)
+    if not (len(po) == len(pn) == len(pd)) or len(fp) != len(fn):
+        raise ValueError("one offset, row count and axis count per problem; one problem and order per fit")
+    if len(st) != int(np.maximum(fn, 0).sum()):
+        raise ValueError("one start row per component of every fit")
+    nf = len(fn)
+    off = np.zeros(nf + 1, np.int64)
+    np.cumsum(np.maximum(fn, 0), out=off[1:])
+    t = int(off[-1])
+    out = dict(lb=np.zeros(nf), n_iter=np.zeros(nf, np.int32), converged=np.zeros(nf, np.int32), off=off,
+               w=np.zeros(t), mu=np.zeros((t, 2)), var=np.zeros((t, 2)))
+    _check(lib.nra_mixture_fit(device, len(x), _ptr(x, C.c_double), len(po), _ptr(po, C.c_int64), _ptr(pn, C.c_int32),
+                               _ptr(pd, C.c_int32), nf, _ptr(fp, C.c_int32), _ptr(fn, C.c_int32), _ptr(st, C.c_int32),
+                               flags, _ptr(out["lb"], C.c_double), _ptr(out["w"], C.c_double),
+                               _ptr(out["mu"], C.c_double), _ptr(out["var"], C.c_double),
+                               _ptr(out["n_iter"], C.c_int32), _ptr(out["converged"], C.c_int32)))
     return out

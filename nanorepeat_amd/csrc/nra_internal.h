@@ -248,12 +248,44 @@ struct NraMotifTract {
     int32_t pad;
 };
 
+// Mixture fits (nra_mixture.hip, nra_mixture_host.cpp): one workgroup of 256 threads per fit.
+// A problem of up to 256 * KREG_SMALL or 256 * KREG points keeps its points in registers, a larger one streams them.
+#define NRA_MIX_THREADS 256
+#define NRA_MIX_MAX_COMPONENTS 32
+#define NRA_MIX_MAX_N (1 << 22)
+#define NRA_MIX_KREG_SMALL 4
+#define NRA_MIX_KREG 20
+#define NRA_MIX_LLOYD_STEPS 10
+#define NRA_MIX_MAX_ITER 100
+#define NRA_MIX_TOL 1e-3
+
+// one problem: n rows of d doubles from double `off` of the sample buffer (even, so a row of two is 16-byte aligned)
+struct NraMixProblem {
+    uint64_t off;
+    int32_t n;
+    int32_t d;
+};
+
+// one fit: n components on `problem`; its start rows and its per-component results begin at entry `off`
+struct NraMixFit {
+    int64_t off;
+    int32_t problem;
+    int32_t n;
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
 
 // the error message nra_last_error() returns; returns `code` (nra_host.cpp)
 int nra_set_error(int code, const char* msg);
+
+// mixture fits (nra_mixture.hip): workgroup b fits fits[fit_ids[b]].  d in {1, 2}; kreg in {NRA_MIX_KREG_SMALL,
+// NRA_MIX_KREG, 0 = streaming} and every problem of the launch has n <= 256 * kreg unless kreg is 0.  Writes lb[f],
+// iter[2 f] = E-steps, iter[2 f + 1] = converged, and w[off + c], mu / var[2 (off + c) + axis]
+int nra_launch_mixture(hipStream_t st, int d, int kreg, int n, const int32_t* fit_ids, const NraMixFit* fits,
+                       const NraMixProblem* probs, const double* samples, const int32_t* starts, double* lb, double* w,
+                       double* mu, double* var, int32_t* iter);
 
 // anchor screen (nra_screen.hip): one workgroup per tile.  Entries go to entries[0, cap); *count ends as the number of
 // entries wanted, which may exceed cap (the host then grows the list and runs again)

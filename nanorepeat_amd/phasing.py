@@ -1,7 +1,9 @@
 """Step 4 of the reference pipeline: phasing reads into alleles with a Gaussian mixture and the
 result files (split_alleles.py:82-534, nanoRepeat_bam.py:502-574,
-nanoRepeat_joint.py:675-747).  Host-side statistics on a few hundred numbers per region --
-there is no GPU work here; scikit-learn does the fitting exactly as in the reference.
+nanoRepeat_joint.py:675-747).  Host-side statistics on a few hundred numbers per region.  By default
+scikit-learn does the fitting exactly as in the reference and there is no GPU work here; with
+`mixture="gpu"` (pipeline.py) the fits of all regions run on the GPU instead (mixture.py hands `phase` a
+`fitter`), and everything around the fit stays the code below.
 
 One implementation serves both the 1D and the joint (2D) mode: the reference's pairs of
 `*_1d` / `*_2d` functions differ only in the number of columns.  What is mirrored:
@@ -307,16 +309,22 @@ def _generators(seed):
 
 
 def phase(count_dict, dimension, ploidy, error_rate, max_mutual_overlap, max_num_components,
-          remove_noisy_reads, seed=None, _gens=None):
+          remove_noisy_reads, seed=None, _gens=None, fitter=None, _restart=0):
     """The statistical core shared by both drivers.  Returns (allele_list, num_removed_reads,
-    final_gmm), or None when there are too few reads."""
+    final_gmm), or None when there are too few reads.  `fitter` replaces the simulated sample and the
+    scikit-learn fits: fitter(kept sizes [m, dimension], error_rate, max_mutual_overlap, max_num_components,
+    seed, restart) -> (number of components, fitted mixture); restart counts the joint mode's new starts."""
     if ploidy < 1:
         raise ValueError("ploidy must be >= 1")
-    py_rng, np_rng = _gens if _gens is not None else _generators(seed)
     names, flat = remove_outlier_reads(count_dict, dimension)
     real = np.array(flat).reshape(-1, dimension)
-    simulated = np.array(simulate_reads(flat, error_rate, py_rng)).reshape(-1, dimension)
-    n, gmm = auto_gmm(simulated, max_num_components, max_mutual_overlap, np_rng)
+    if fitter is None:
+        py_rng, np_rng = _gens if _gens is not None else _generators(seed)
+        simulated = np.array(simulate_reads(flat, error_rate, py_rng)).reshape(-1, dimension)
+        n, gmm = auto_gmm(simulated, max_num_components, max_mutual_overlap, np_rng)
+    else:
+        py_rng = np_rng = None
+        n, gmm = fitter(real, error_rate, max_mutual_overlap, max_num_components, seed, _restart)
     alleles = create_allele_list(n, gmm, names, real, count_dict)
     num_removed = 0
     if remove_noisy_reads and len(alleles) > ploidy:
@@ -328,8 +336,8 @@ def phase(count_dict, dimension, ploidy, error_rate, max_mutual_overlap, max_num
                     for a in alleles for i, name in enumerate(a.readname_list)}
             if len(kept) < ploidy or len(kept) == 1:
                 return None
-            return phase(kept, 2, ploidy, error_rate, max_mutual_overlap, max_num_components, False,
-                         _gens=(py_rng, np_rng))
+            return phase(kept, 2, ploidy, error_rate, max_mutual_overlap, max_num_components, False, seed,
+                         _gens=(py_rng, np_rng), fitter=fitter, _restart=_restart + 1)
     alleles.sort(key=lambda a: a.gmm_mean1)
     return alleles, num_removed, gmm
 
@@ -375,14 +383,15 @@ def region_count_dict(repeat_region):
             if r.round3_repeat_size is not None}
 
 
-def phase_1d_job(args):
+def phase_1d_job(args, fitter=None):
     """The mixture fit of one region without the region object (picklable in, picklable out): what
-    `pipeline.phase_regions` hands to its worker processes.  Returns (alleles, num_removed) or None."""
+    `pipeline.phase_regions` hands to its worker processes.  Returns (alleles, num_removed) or None.
+    `fitter`: see `phase`."""
     count_dict, ploidy, error_rate, max_mutual_overlap, max_num_components, remove_noisy_reads, seed = args
     if len(count_dict) < 2:
         return None
     alleles, num_removed, _ = phase(count_dict, 1, ploidy, error_rate, max_mutual_overlap,
-                                    max_num_components, remove_noisy_reads, seed)
+                                    max_num_components, remove_noisy_reads, seed, fitter=fitter)
     return alleles, num_removed
 
 
@@ -433,13 +442,14 @@ def split_allele_using_gmm_1d(repeat_region, ploidy, error_rate, max_mutual_over
     return alleles
 
 
-def phase_2d_job(args):
+def phase_2d_job(args, fitter=None):
     """The 2D mixture fit as a picklable job (see phase_1d_job): (alleles, components of the final
     mixture) or None."""
     count_dict, ploidy, error_rate, max_mutual_overlap, max_num_components, remove_noisy_reads, seed = args
     if len(count_dict) < ploidy or len(count_dict) == 1:
         return None
-    got = phase(count_dict, 2, ploidy, error_rate, max_mutual_overlap, max_num_components, remove_noisy_reads, seed)
+    got = phase(count_dict, 2, ploidy, error_rate, max_mutual_overlap, max_num_components, remove_noisy_reads, seed,
+                fitter=fitter)
     if got is None:
         return None
     return got[0], int(got[2].n_components)

@@ -69,24 +69,35 @@ def _fit_in_worker_processes(jobs, n_jobs):
 
 
 def phase_regions(repeat_regions, data_type="ont", ploidy=2, max_mutual_overlap=0.15, max_num_components=-1,
-                  remove_noisy_reads=False, seed=None, out_tsv_file=None, n_jobs=None):
+                  remove_noisy_reads=False, seed=None, out_tsv_file=None, n_jobs=None, mixture="sklearn", device=0,
+                  mixture_engine=None):
     """Step 4 for every region (nanoRepeat_bam.py:683-684) and the final table (:737-743); defaults
     are the CLI's (nanoRepeat.py:121-129,159-160).  With a seed, region i uses seed + i.  The mixture
     fits -- by far the longest step of the whole command -- run in up to 16 worker processes like
     the reference's region workers (nanoRepeat_bam.py:712-724); the workers are fresh interpreters
-    that get only the sizes and never touch the GPU.  n_jobs=1 keeps everything in this process."""
+    that get only the sizes and never touch the GPU.  n_jobs=1 keeps everything in this process.
+    mixture="gpu" fits every region's mixtures on the GPU instead, in this process, in one C-ABI call per
+    window of model orders (mixture.py): no worker processes, no scikit-learn, and a
+    run is a function of its seed (seed=None draws one).  `mixture_engine` stands in for that call (tests)."""
     import os
+    from . import mixture as nr_mixture
+    nr_mixture.check_engine_name(mixture)
+    if mixture == "gpu" and seed is None:
+        seed = nr_mixture.fresh_seed()
     if max_num_components == -1:
         max_num_components = ploidy + 20
     error_rate = phasing.data_type_error_rate(data_type)
     jobs = [(phasing.region_count_dict(region), ploidy, error_rate, max_mutual_overlap, max_num_components,
              remove_noisy_reads, None if seed is None else seed + i) for i, region in enumerate(repeat_regions)]
-    if n_jobs is None:
-        n_jobs = min(16, os.cpu_count() or 1, max(1, sum(len(j[0]) >= 2 for j in jobs)))
-    if n_jobs > 1:
-        fitted = _fit_in_worker_processes([("1d", j) for j in jobs], n_jobs)
+    if mixture == "gpu":
+        fitted = nr_mixture.phase_jobs([("1d", j) for j in jobs], device, mixture_engine)
     else:
-        fitted = [phasing.phase_1d_job(j) for j in jobs]
+        if n_jobs is None:
+            n_jobs = min(16, os.cpu_count() or 1, max(1, sum(len(j[0]) >= 2 for j in jobs)))
+        if n_jobs > 1:
+            fitted = _fit_in_worker_processes([("1d", j) for j in jobs], n_jobs)
+        else:
+            fitted = [phasing.phase_1d_job(j) for j in jobs]
     rows = []
     for region, job, fit in zip(repeat_regions, jobs, fitted):
         if fit is not None:
@@ -101,11 +112,15 @@ def phase_regions(repeat_regions, data_type="ont", ploidy=2, max_mutual_overlap=
 
 def quantify_joint(in_fq, ref_fasta, repeat1_string, repeat2_string, out_prefix, data_type="ont", num_threads=1,
                    ploidy=2, error_rate=0.1, max_mutual_overlap=0.1, remove_noisy_reads=False,
-                   max_num_components=-1, device=0, scoring=None, seed=None, phase_in_worker=True, **engines):
+                   max_num_components=-1, device=0, scoring=None, seed=None, phase_in_worker=True, mixture="sklearn",
+                   **engines):
     """The joint (2D) command from files to files (nanoRepeat_joint.py:160-232): round 1 ->
     grid rounds 2/3 -> `<out_prefix>.repeat_size.txt` -> 2D GMM phasing -> `.phased_reads.txt`,
-    `.summary.txt`, `.alleleN.fastq`.  `engines` may carry aligner / cigar_aligner / scorer
-    stand-ins (tests).  Returns (RepeatSize, allele list or None)."""
+    `.summary.txt`, `.alleleN.fastq`.  `engines` may carry aligner / cigar_aligner / scorer /
+    mixture_engine stand-ins (tests).  mixture="gpu": the 2D mixtures are fitted on the GPU in this process
+    (see phase_regions).  Returns (RepeatSize, allele list or None)."""
+    from . import mixture as nr_mixture
+    nr_mixture.check_engine_name(mixture)
     if max_num_components == -1:
         max_num_components = ploidy + 20
     fastq_dict = nr_io.fastq_file_to_dict(in_fq)
@@ -134,8 +149,15 @@ def quantify_joint(in_fq, ref_fasta, repeat1_string, repeat2_string, out_prefix,
                                                   final_estimation.repeat2_count_dict)
     # the fit runs in a fresh single-threaded interpreter: scikit-learn's small-matrix algebra is several
     # times slower with this process's BLAS/OpenMP thread pools (split_alleles.py:28-32 pins them to 1)
+    if mixture == "gpu" and seed is None:
+        seed = nr_mixture.fresh_seed()
     job = ("2d", (joint_counts, ploidy, error_rate, max_mutual_overlap, max_num_components, remove_noisy_reads, seed))
-    fitted = _fit_in_worker_processes([job], 1)[0] if phase_in_worker else None
+    if mixture == "gpu":
+        fitted = nr_mixture.phase_jobs([job], device, engines.get("mixture_engine"))[0]
+        if fitted is None:                  # too few reads: nothing to write, as when the default engine returns None
+            return final_estimation, None
+    else:
+        fitted = _fit_in_worker_processes([job], 1)[0] if phase_in_worker else None
     alleles = phasing.split_alleles_using_gmm_2d(ploidy, error_rate, max_mutual_overlap, remove_noisy_reads,
                                                  max_num_components, repeat1, repeat2, joint_counts, 0, in_fq,
                                                  out_prefix, seed=seed, fitted=fitted)
@@ -146,7 +168,7 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
                       fast_mode=False, ploidy=2, max_mutual_overlap=0.15, max_num_components=-1,
                       remove_noisy_reads=False, no_check_repeat_motif_in_ref=False, no_details=False,
                       num_cpu=1, device=0, scoring=None, seed=None, read_structure=False, discover_motifs=False,
-                      min_motif_count=4, min_motif_share=0.1, partial_reads=False, **engines):
+                      min_motif_count=4, min_motif_share=0.1, partial_reads=False, mixture="sklearn", **engines):
     """The BAM command from files to files (nanoRepeat_bam.py:614-751): for every region of the BED
     file, reads from the alignment file -> `<out_prefix>.details/<chr>/<region>.*` ->
     `<out_prefix>.NanoRepeat_output.tsv`.  The reference forks up to 16 workers, one region each;
@@ -156,9 +178,11 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
     (structure.py); discover_motifs=True adds the tandem motif files (motifs.py; min_motif_count and
     min_motif_share set the per-read call); partial_reads=True adds the one-anchor read files (partial.py): for
     every read with one anchor only, the repeat units it shows next to that anchor, and per region whether any such
-    read shows more than the largest spanning read.  `engines` may carry aligner / scorer / structure_engine /
-    motif_engine / extension_engine stand-ins.  Returns the regions."""
-    from . import bam as nr_bam
+    read shows more than the largest spanning read.  mixture="gpu" fits the phasing mixtures on the GPU (see
+    phase_regions).  `engines` may carry aligner / scorer / structure_engine / motif_engine / extension_engine /
+    mixture_engine stand-ins.  Returns the regions."""
+    from . import bam as nr_bam, mixture as nr_mixture
+    nr_mixture.check_engine_name(mixture)
     regions = nr_io.read_repeat_region_file(repeat_region_bed, no_details)
     ref_fasta_dict = nr_io.fasta_file2dict(ref_fasta)
     live, reads_of = [], []
@@ -175,7 +199,7 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
     _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
                         read_structure, _motif_options(discover_motifs, min_motif_count, min_motif_share),
-                        partial_reads)
+                        partial_reads, mixture)
     return regions
 
 
@@ -196,7 +220,7 @@ def _motif_options(discover_motifs, min_motif_count, min_motif_share):
 
 def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
-                        read_structure=False, motif_options=None, partial_reads=False):
+                        read_structure=False, motif_options=None, partial_reads=False, mixture="sklearn"):
     """The commands' common tail: steps 1-4 for the regions with reads, then one TSV row per BED region; with
     read_structure, the structure of every read with a size and the two structure files; with motif_options (a dict
     of motifs.motif_regions keywords), the tandem motifs of every read with a core and the two motif files; with
@@ -204,7 +228,8 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
     such reads show more repeat units than any spanning read."""
     quantify_regions(live, reads_of, data_type, fast_mode, num_cpu, device, scoring,
                      engines.get("aligner"), engines.get("scorer"))
-    phase_regions(live, data_type, ploidy, max_mutual_overlap, max_num_components, remove_noisy_reads, seed)
+    phase_regions(live, data_type, ploidy, max_mutual_overlap, max_num_components, remove_noisy_reads, seed,
+                  mixture=mixture, device=device, mixture_engine=engines.get("mixture_engine"))
     with open(f"{out_prefix}.NanoRepeat_output.tsv", "w") as f:
         for region in regions:
             f.write(phasing.final_output_row(region))
@@ -238,7 +263,7 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         remove_noisy_reads=False, no_check_repeat_motif_in_ref=False, no_details=False,
                         num_cpu=1, device=0, scoring=None, seed=None, screen=True, k=15, min_hits=4, max_occ=16,
                         chunk_bases=1 << 28, read_structure=False, discover_motifs=False, min_motif_count=4,
-                        min_motif_share=0.1, **engines):
+                        min_motif_share=0.1, mixture="sklearn", **engines):
     """The FASTQ / FASTA command (nanoRepeat.py:109, `-t fastq|fasta`) from files to files, without a genome mapper:
     the reads each region sees are chosen by the anchor k-mer screen (screen.reads_by_region) instead of a
     genome-wide mapping and a BAM window, then the BAM command's steps run unchanged.  Every region's reference
@@ -246,9 +271,11 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
     screened and get their 0-allele row.  Each region's reads go to `<out_prefix>.details/<chr>/<region>.reads.fastq`
     (qualities `.` for FASTA input).  screen=False offers every read to every region: exact, and slow beyond small
     panels.  read_structure=True adds the repeat structure files (structure.py); discover_motifs=True adds the
-    tandem motif files (motifs.py).  `engines` may carry aligner / scorer / screener / structure_engine / motif_engine
-    stand-ins.  Returns the regions."""
-    from . import screen as nr_screen
+    tandem motif files (motifs.py).  mixture="gpu" fits the phasing mixtures on the GPU (see phase_regions).
+    `engines` may carry aligner / scorer / screener / structure_engine / motif_engine / mixture_engine stand-ins.
+    Returns the regions."""
+    from . import screen as nr_screen, mixture as nr_mixture
+    nr_mixture.check_engine_name(mixture)
     regions = nr_io.read_repeat_region_file(repeat_region_bed, no_details)
     ref_fasta_dict = nr_io.fasta_file2dict(ref_fasta)
     screened = []
@@ -272,7 +299,8 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
             reads_of.append({name: seq for name, (seq, _) in reads.items()})
     _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
-                        read_structure, _motif_options(discover_motifs, min_motif_count, min_motif_share))
+                        read_structure, _motif_options(discover_motifs, min_motif_count, min_motif_share),
+                        mixture=mixture)
     return regions
 
 
