@@ -487,6 +487,58 @@ int nra_mixture_fit(int device, int64_t n_samples, const double* samples, int32_
                     const int32_t* fit_n, const int32_t* starts, int32_t flags,
                     double* lb, double* w, double* mu, double* var, int32_t* n_iter, int32_t* converged);
 
+/* ---- allele consensus: one sequence per group of tracts (no counterpart in the reference) ----------------------------
+ *
+ * Integer arithmetic throughout: the outputs are a function of the group alone, bit for bit.
+ * A group is a list of tracts (upper-cased; A C G T -> codes 0..3, any other byte -> code 4); empty tracts are dropped,
+ * m tracts remain, in the order given.
+ *   Backbone of round 0: sort the tracts by (length, position in the group), take element (m - 1) / 2 (integer
+ *   division), remove its code-4 bases.
+ *   Alignment of a tract s (n bases) to the backbone b (t bases), global, unit cost:
+ *     D[0][j] = j, D[i][0] = i,
+ *     D[i][j] = min(D[i-1][j-1] + (s[i-1] != b[j-1]), D[i-1][j] + 1, D[i][j-1] + 1)   (code 4 mismatches every base).
+ *   Traceback from (n, t) to (0, 0): at each cell the diagonal if it attains D[i][j], else the insertion (i-1, j), else
+ *   the deletion (i, j-1).  The path gives per backbone column j the tract base aligned to it or "deleted", and per
+ *   slot j in [0, t] (before column j; slot t is after the last column) the run of inserted tract bases.
+ *   Left out: a tract with D[n][t] > max_dist takes no part in that round's vote (it may vote in a later round).
+ *   Vote of the m_v tracts that take part: col[j][c], c in {A, C, G, T, deleted} (a code-4 base aligned to the column
+ *   abstains); ins[j][c], c in {A, C, G, T}: the first base, in tract order, of the tract's insertion run in slot j,
+ *   if the run is not empty and that base is A, C, G or T.
+ *   New backbone, slots and columns interleaved from the left: slot j emits argmax_c ins[j][c] (a tie: the smallest
+ *   code) when 2 * sum_c ins[j][c] > m_v; column j emits the symbol with the most votes -- on a tie the backbone's own
+ *   base if it is among the tied, else the smallest code, "deleted" last -- unless that symbol is "deleted".
+ *   Rounds: repeat with the new backbone until a round returns the backbone unchanged (converged = 1) or max_rounds
+ *   rounds have run.  A round with m_v = 0 ends the group with the backbone it has, converged = 0 (the round counts).
+ * Outputs per group: the consensus; n_rounds; converged; the tracts that voted in the last round and those left out
+ * of it; per consensus base its support: the votes for the emitted symbol in the round that emitted it (the ins votes
+ * for a base that entered through a slot; 0 everywhere when no round voted).  A group without tracts returns an empty
+ * consensus and four zeros.
+ * The device aligns inside a band of 64 c diagonals, c in {1, 2, 4, 8, 16}: with delta = t - n and
+ * h = (64 c - 1 - |delta|) / 2 >= 0 the band holds the diagonals j - i in [min(0, delta) - h, max(0, delta) + h].  A
+ * path from (0, 0) to (n, t) that leaves that range by x diagonals costs at least |delta| + 2 x, so every path of cost
+ * <= w = |delta| + 2 h lies in the band: a banded distance <= w is the distance, and every traceback decision is the
+ * full matrix's (a co-optimal predecessor lies on an optimal path, so in the band with its exact value; another one has
+ * a banded value >= its true value and still fails the equality); a banded distance > w means the distance is > w.
+ * A tract is aligned in a wider band until its banded distance is <= min(w, max_dist), or w >= max_dist says it is
+ * left out.  max_dist <= 1000 (the widest band proves 1022).  DESIGN.md section 18. */
+
+#define NRA_CONS_MAX_DIST     1000   /* largest (and default) max_dist */
+#define NRA_CONS_MAX_ROUNDS   64
+#define NRA_CONS_N_STATS      16     /* int64 counters: [c] alignments run and [5 + c] tract rows swept in band class c
+                                        (c = 0..4: 64, 128, 256, 512, 1024 diagonals), [10] rounds launched, [11]
+                                        alignment launches, [12] alignments repeated in a wider band, [13] tract-rounds
+                                        left out by |t - n| > max_dist alone, [14] pointer bytes of the largest launch */
+
+/* Group g = tracts [group_off[g], group_off[g+1]) (group_off[0] = 0, group_off[n_groups] = n_tracts); tract r = bytes
+ * [seq_off[r], seq_off[r+1]) of `seqs` (at most 200 000 bases, NRA_E_RANGE beyond).  0 <= max_dist <= 1000 and
+ * 1 <= max_rounds <= 64 (negative or zero: NRA_E_ARG, larger: NRA_E_RANGE).  Writes the consensus of group g as
+ * letters at consensus[cons_off[g] .. cons_off[g+1]) and its supports at the same indices of `support` (both hold
+ * cons_cap entries; NRA_E_RANGE when the consensuses need more), group_res[4 g ..] = n_rounds, converged, voted, left out, and stats[] if not
+ * NULL.  Arguments are checked before the device is touched. */
+int nra_tract_consensus(int device, int32_t n_groups, const int64_t* group_off, int32_t n_tracts, const char* seqs,
+                        const int64_t* seq_off, int32_t max_dist, int32_t max_rounds, int64_t cons_cap,
+                        char* consensus, int32_t* support, int64_t* cons_off, int32_t* group_res, int64_t* stats);
+
 #ifdef __cplusplus
 }
 #endif

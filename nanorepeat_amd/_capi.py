@@ -36,7 +36,8 @@ EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count
            "nra_batch2d_create", "nra_batch2d_create_reads", "nra_batch2d_set_cells", "nra_joint_grid_cells", "nra_batch2d_set_grid", "nra_batch2d_invalidate", "nra_batch2d_sweep_flanks", "nra_batch2d_refine", "nra_batch_run", "nra_batch_sync", "nra_batch_stats",
            "nra_batch1d_fetch", "nra_batch1d_resweeps", "nra_batch2d_fetch", "nra_batch_destroy",
            "nra_screen_create", "nra_screen_reads", "nra_screen_stats", "nra_screen_destroy",
-           "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts", "nra_mixture_fit")
+           "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts", "nra_mixture_fit",
+           "nra_tract_consensus")
 
 
 E_RANGE = -3      # NRA_E_RANGE
@@ -184,6 +185,9 @@ def load():
     lib.nra_mixture_fit.restype = C.c_int
     lib.nra_mixture_fit.argtypes = [C.c_int, C.c_int64, pf64, C.c_int32, pi64, pi32, pi32, C.c_int32, pi32, pi32, pi32,
                                     C.c_int32, pf64, pf64, pf64, pf64, pi32, pi32]
+    lib.nra_tract_consensus.restype = C.c_int
+    lib.nra_tract_consensus.argtypes = [C.c_int, C.c_int32, pi64, C.c_int32, C.c_char_p, pi64, C.c_int32, C.c_int32,
+                                        C.c_int64, C.c_char_p, pi32, pi64, pi32, pi64]
     _LIB = lib
     return lib
 
@@ -708,3 +712,36 @@ def mixture_fit(samples, prob_off, prob_n, prob_d, fit_problem, fit_n, starts, f
                                _ptr(out["mu"], C.c_double), _ptr(out["var"], C.c_double),
                                _ptr(out["n_iter"], C.c_int32), _ptr(out["converged"], C.c_int32)))
     return out
+
+
+CONS_MAX_DIST = 1000      # NRA_CONS_MAX_DIST: the largest, and the default, max_dist of nra_tract_consensus
+CONS_STATS = ("aligned_64", "aligned_128", "aligned_256", "aligned_512", "aligned_1024", "rows_64", "rows_128",
+              "rows_256", "rows_512", "rows_1024", "rounds", "launches", "widened", "left_out_by_length",
+              "max_pointer_bytes")
+
+
+def tract_consensus(groups, max_dist=CONS_MAX_DIST, max_rounds=8, device=0):
+    """nra_tract_consensus: the consensus of every group (a list of tracts) -> dict(consensus [str per group], support
+    [int32 array per group], n_rounds, converged, voted, left_out [int32 per group], stats {name: count})."""
+    lib = load()
+    groups = [list(g) for g in groups]
+    ng = len(groups)
+    goff = np.zeros(ng + 1, np.int64)
+    if ng:
+        np.cumsum([len(g) for g in groups], out=goff[1:])
+    tracts = [t for g in groups for t in g]
+    data, off = pack_reads(tracts)
+    cap = int(sum(2 * max((len(t) for t in g), default=0) + 64 for g in groups))
+    cons = C.create_string_buffer(max(cap, 1))
+    support = np.zeros(max(cap, 1), np.int32)
+    coff = np.zeros(ng + 1, np.int64)
+    res = np.zeros((ng, 4), np.int32)
+    stats = np.zeros(16, np.int64)
+    _check(lib.nra_tract_consensus(device, ng, _ptr(goff, C.c_int64), len(tracts), data, _ptr(off, C.c_int64),
+                                   max_dist, max_rounds, cap, cons, _ptr(support, C.c_int32), _ptr(coff, C.c_int64),
+                                   _ptr(res, C.c_int32), _ptr(stats, C.c_int64)))
+    raw = cons.raw
+    return dict(consensus=[raw[coff[g]:coff[g + 1]].decode("ascii") for g in range(ng)],
+                support=[support[coff[g]:coff[g + 1]].copy() for g in range(ng)],
+                n_rounds=res[:, 0].copy(), converged=res[:, 1].copy(), voted=res[:, 2].copy(),
+                left_out=res[:, 3].copy(), stats={k: int(v) for k, v in zip(CONS_STATS, stats)})

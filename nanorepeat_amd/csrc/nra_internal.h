@@ -273,9 +273,51 @@ struct NraMixFit {
     int32_t n;
 };
 
+// Allele consensus (nra_consensus.hip, nra_consensus_host.cpp): banded unit-cost alignment of every tract of a group to
+// the group's backbone, one wave per tract, votes into the group's tables, then a new backbone per group (DESIGN.md
+// section 18).  Band class c: a lane owns c consecutive diagonals, the band holds 64 c.
+#define NRA_CONS_MAX_N 200000
+#define NRA_CONS_CLASSES 5                    // c = 1, 2, 4, 8, 16
+#define NRA_CONS_CODE_OTHER 4                 // a tract byte other than ACGT: mismatches every base, abstains from votes
+#define NRA_CONS_CODE_PAD 5                   // beyond the backbone
+#define NRA_CONS_INF (1 << 28)
+#define NRA_CONS_TAB 9                        // table ints per backbone position j: col[j][0..4], ins[j][0..3]
+#define NRA_CONS_WIDEN (-1)                   // status: the band could not decide, align again in the next class
+#define NRA_CONS_LEFT_OUT (-2)                // status: distance > max_dist
+
+// one group of a round: backbone at byte `bb` of the backbone buffer (t bases), the new one (and its supports) from
+// byte / entry `nb` of the new buffers (room for 2 t + 1), its tables at int `tab` ((t + 1) * NRA_CONS_TAB ints)
+struct NraConsGroup {
+    uint64_t bb;
+    uint64_t nb;
+    uint64_t tab;
+    int32_t t;
+    int32_t pad;
+};
+
+// one alignment of a launch: codes at byte `seq` of the tract buffer (a multiple of 16), traceback pointers from
+// uint4 `ptr` ([row block][lane], 64 / c rows to a block), group slot of the round, status slot of the launch
+struct NraConsItem {
+    uint64_t seq;
+    uint64_t ptr;
+    int32_t n;
+    int32_t group;
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+
+// allele consensus (nra_consensus.hip).  Alignment: workgroup i (one wave) aligns items[i] in band class c (1, 2, 4, 8
+// or 16) and, when its banded distance d proves exact and d <= max_dist, adds its votes to the group's tables, 1 to
+// voters[group], and writes status[i] = d; else status[i] = NRA_CONS_WIDEN or NRA_CONS_LEFT_OUT.  Build: wave g writes
+// the new backbone and supports of groups[g] and res[3 g ..] = new length, changed (0 / 1), voters
+int nra_launch_cons_align(hipStream_t st, int c, int n_items, const NraConsItem* items, const NraConsGroup* groups,
+                          const uint8_t* seqs, const uint8_t* backbones, uint4* ptrs, int32_t* tabs, int32_t* voters,
+                          int32_t* status, int max_dist);
+int nra_launch_cons_build(hipStream_t st, int n_groups, const NraConsGroup* groups, const uint8_t* backbones,
+                          const int32_t* tabs, const int32_t* voters, uint8_t* new_backbones, int32_t* support,
+                          int32_t* res);
 
 // the error message nra_last_error() returns; returns `code` (nra_host.cpp)
 int nra_set_error(int code, const char* msg);
