@@ -539,6 +539,56 @@ int nra_tract_consensus(int device, int32_t n_groups, const int64_t* group_off, 
                         const int64_t* seq_off, int32_t max_dist, int32_t max_rounds, int64_t cons_cap,
                         char* consensus, int32_t* support, int64_t* cons_off, int32_t* group_res, int64_t* stats);
 
+/* ---- allele split: two haplotypes of one size allele, told apart by tract sequence (no counterpart in the reference)
+ *
+ * Integer arithmetic throughout: the outputs are a function of the group and its backbone, bit for bit.  Every rule
+ * counts and none looks at the order of the tracts: permuting the tracts of a group permutes the labels.
+ * A group is a list of m tracts, coded as for the consensus (A C G T -> 0..3, any other byte -> 4; empty tracts stay),
+ * and one backbone of t bases, all A, C, G or T (in practice the group's consensus).
+ *   Step 1, pileup.  Each tract is aligned to the backbone by exactly the consensus alignment and traceback above (same
+ *   band classes, same widening rule and proof).  A tract with D[n][t] <= max_dist gets a row: sym[j], per backbone
+ *   column j, is the code 0..4 of the base aligned to it (4 abstains from every count) or 5, deleted.  Any other tract is
+ *   left out: no row, label -1, distance -1.  m_v tracts have a row.  Insertion slots are not used by this version: in
+ *   a tandem tract left-shifted insertion runs pile up at the run starts, and a column of them says little.
+ *   Step 2, variant sites.  Per column, n[c] = the rows that show base c (c in A, C, G, T); a = the most voted base,
+ *   b = the second (ties: the smaller code).  Column j is a site iff n[b] >= min_count and
+ *   100 n[b] >= min_share_pct (n[a] + n[b]) and 2 (n[a] + n[b]) >= m_v.  Only substitution sites are called, deletion
+ *   columns are not.  Sites are listed by ascending column; of more than max_sites those with the largest n[b] stay
+ *   (ties: the smaller column), still listed by column.
+ *   Step 3, two haplotypes.  The anchor is the site with the largest n[b] (ties: the smaller column).  Start labels: 0
+ *   where the row shows a at the anchor, 1 where it shows b, else 2, undecided.  Up to max_iter times: per haplotype
+ *   and site, its symbol is the most voted base among the rows with its label (ties: the smaller code; when none of them
+ *   shows a base there, a of the site for haplotype 0 and b for 1); per row, its mismatches against either haplotype
+ *   over the sites where it shows a base; fewer wins, a tie keeps the label (undecided included); all rows change
+ *   together; stop after an iteration that changed no label.  Without a site every row has label 0 and no iteration runs.
+ *   Step 4, verdict, on the symbols and counts of the final labels.  A site is supported when the two haplotype symbols
+ *   differ and, in each haplotype, at least one row shows its symbol and 100 * (rows showing it) >= min_purity_pct *
+ *   (rows showing a base there).  split = 1 iff both haplotypes have at least min_count rows and at least min_sites
+ *   sites are supported.  Haplotype 0 is the one with more rows (a tie: the one that started as 0); labels, symbols and
+ *   counts are swapped to make it so.
+ * An empty backbone or a group without tracts has no sites and no split.  DESIGN.md section 19. */
+
+#define NRA_SPLIT_MAX_SITES   4096
+#define NRA_SPLIT_MAX_ITER    64
+#define NRA_SPLIT_N_STATS     16     /* int64 counters as NRA_CONS_N_STATS, but [10] sites called and [15] groups split */
+
+/* Groups and tracts as for nra_tract_consensus; backbone g = bytes [bb_off[g], bb_off[g+1]) of `backbones` (at most
+ * 200 000 bases, NRA_E_RANGE beyond; a byte other than A, C, G, T in either case is NRA_E_ARG).  0 <= max_dist <= 1000;
+ * min_count, min_sites >= 1; min_share_pct, min_purity_pct in 1..100; max_sites in 1..4096; max_iter in 1..64 (below:
+ * NRA_E_ARG, above: NRA_E_RANGE).  Writes label[r] (-1, 0, 1, 2 undecided) and dist[r] per tract;
+ * group_res[8 g ..] = split, rows in haplotype 0, in 1, undecided, tracts left out, n_sites, n_supported, iterations;
+ * the sites of group g as records [site_off[g], site_off[g+1]) of `sites`, 12 ints each: column, symbol of haplotype 0,
+ * of 1, the A C G T counts of haplotype 0, of 1, supported; and at site_sym[sym_off[g] + q m + i] what tract i of the
+ * group shows at its site q (0..5, 6 without a row).  `sites` holds site_cap records and site_sym sym_cap bytes
+ * (NRA_E_RANGE when they do not suffice: min(max_sites, t) sites per group always do); stats[] if not NULL.  Arguments
+ * are checked before the device is touched. */
+int nra_allele_split(int device, int32_t n_groups, const int64_t* group_off, int32_t n_tracts, const char* seqs,
+                     const int64_t* seq_off, const char* backbones, const int64_t* bb_off, int32_t max_dist,
+                     int32_t min_count, int32_t min_share_pct, int32_t min_purity_pct, int32_t min_sites,
+                     int32_t max_sites, int32_t max_iter, int32_t* label, int32_t* dist, int32_t* group_res,
+                     int64_t site_cap, int32_t* sites, int64_t* site_off, int64_t sym_cap, uint8_t* site_sym,
+                     int64_t* sym_off, int64_t* stats);
+
 #ifdef __cplusplus
 }
 #endif

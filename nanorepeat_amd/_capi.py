@@ -37,7 +37,7 @@ EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count
            "nra_batch1d_fetch", "nra_batch1d_resweeps", "nra_batch2d_fetch", "nra_batch_destroy",
            "nra_screen_create", "nra_screen_reads", "nra_screen_stats", "nra_screen_destroy",
            "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts", "nra_mixture_fit",
-           "nra_tract_consensus")
+           "nra_tract_consensus", "nra_allele_split")
 
 
 E_RANGE = -3      # NRA_E_RANGE
@@ -185,6 +185,9 @@ def load():
     lib.nra_mixture_fit.restype = C.c_int
     lib.nra_mixture_fit.argtypes = [C.c_int, C.c_int64, pf64, C.c_int32, pi64, pi32, pi32, C.c_int32, pi32, pi32, pi32,
                                     C.c_int32, pf64, pf64, pf64, pf64, pi32, pi32]
+    lib.nra_allele_split.restype = C.c_int
+    lib.nra_allele_split.argtypes = [C.c_int, C.c_int32, pi64, C.c_int32, C.c_char_p, pi64, C.c_char_p, pi64] + \
+                                    [C.c_int32] * 7 + [pi32, pi32, pi32, C.c_int64, pi32, pi64, C.c_int64, p8, pi64, pi64]
     lib.nra_tract_consensus.restype = C.c_int
     lib.nra_tract_consensus.argtypes = [C.c_int, C.c_int32, pi64, C.c_int32, C.c_char_p, pi64, C.c_int32, C.c_int32,
                                         C.c_int64, C.c_char_p, pi32, pi64, pi32, pi64]
@@ -745,3 +748,57 @@ def tract_consensus(groups, max_dist=CONS_MAX_DIST, max_rounds=8, device=0):
                 support=[support[coff[g]:coff[g + 1]].copy() for g in range(ng)],
                 n_rounds=res[:, 0].copy(), converged=res[:, 1].copy(), voted=res[:, 2].copy(),
                 left_out=res[:, 3].copy(), stats={k: int(v) for k, v in zip(CONS_STATS, stats)})
+
+
+SPLIT_DEFAULTS = dict(max_dist=CONS_MAX_DIST, min_count=3, min_share_pct=25, min_purity_pct=75, min_sites=1,
+                      max_sites=256, max_iter=16)      # min_sites: chosen from the table of DESIGN.md section 19.3
+SPLIT_STATS = CONS_STATS[:10] + ("sites", "launches", "widened", "left_out_by_length", "max_pointer_bytes",
+                                 "groups_split")
+SPLIT_RES = ("split", "n0", "n1", "undecided", "left_out", "n_sites", "n_supported", "iterations")
+
+
+def allele_split(groups, backbones, device=0, **thresholds):
+    """nra_allele_split: the tracts of every group piled up on its backbone, the variant sites and the two haplotypes
+    (thresholds: SPLIT_DEFAULTS) -> dict(label, dist [int32 array per group: per tract], sites [int32 [n_sites, 12]
+    per group: column, symbol of haplotype 0, of 1, A C G T counts of 0, of 1, supported], site_sym [uint8
+    [n_sites, tracts] per group], split, n0, n1, undecided, left_out, n_sites, n_supported, iterations [int32 per
+    group], stats {name: count})."""
+    lib = load()
+    unknown = set(thresholds) - set(SPLIT_DEFAULTS)
+    if unknown:
+        raise TypeError(f"allele_split: unknown threshold(s) {sorted(unknown)}")
+    p = dict(SPLIT_DEFAULTS, **thresholds)
+    groups = [list(g) for g in groups]
+    backbones = list(backbones)
+    ng = len(groups)
+    if len(backbones) != ng:
+        raise ValueError("one backbone per group")
+    sizes = np.array([len(g) for g in groups], np.int64)
+    goff = np.zeros(ng + 1, np.int64)
+    np.cumsum(sizes, out=goff[1:])
+    tracts = [t for g in groups for t in g]
+    data, off = pack_reads(tracts)
+    bdata, boff = pack_reads(backbones)
+    nt = len(tracts)
+    most = np.minimum(np.diff(boff), max(1, min(int(p["max_sites"]), 4096)))
+    site_cap, sym_cap = int(most.sum()), int((most * sizes).sum())
+    label, dist = np.zeros(max(nt, 1), np.int32), np.zeros(max(nt, 1), np.int32)
+    res = np.zeros((ng, 8), np.int32)
+    sites = np.zeros((max(site_cap, 1), 12), np.int32)
+    sym = np.zeros(max(sym_cap, 1), np.uint8)
+    soff, yoff = np.zeros(ng + 1, np.int64), np.zeros(ng + 1, np.int64)
+    stats = np.zeros(16, np.int64)
+    _check(lib.nra_allele_split(device, ng, _ptr(goff, C.c_int64), nt, data, _ptr(off, C.c_int64), bdata,
+                                _ptr(boff, C.c_int64), *(int(p[k]) for k in SPLIT_DEFAULTS), _ptr(label, C.c_int32),
+                                _ptr(dist, C.c_int32), _ptr(res, C.c_int32), site_cap, _ptr(sites, C.c_int32),
+                                _ptr(soff, C.c_int64), sym_cap, _ptr(sym, C.c_uint8), _ptr(yoff, C.c_int64),
+                                _ptr(stats, C.c_int64)))
+    out = dict(label=[label[goff[g]:goff[g + 1]].copy() for g in range(ng)],
+               dist=[dist[goff[g]:goff[g + 1]].copy() for g in range(ng)],
+               sites=[sites[soff[g]:soff[g + 1]].copy() for g in range(ng)],
+               site_sym=[sym[yoff[g]:yoff[g + 1]].reshape(int(soff[g + 1] - soff[g]), int(sizes[g])).copy()
+                         for g in range(ng)],
+               stats={k: int(v) for k, v in zip(SPLIT_STATS, stats)})
+    for q, name in enumerate(SPLIT_RES):
+        out[name] = res[:, q].copy()
+    return out

@@ -37,15 +37,21 @@ class AlleleConsensus:
         return int(self.support.min()) / self.voted
 
 
-def allele_groups(region):
-    """[(allele id, [tract of each read of the allele, phased_reads.txt order, empty tracts dropped])] in phasing order."""
+def named_allele_groups(region):
+    """[(allele id, [(read name, tract) of each read of the allele, phased_reads.txt order, empty tracts dropped])] in
+    phasing order."""
     res = phasing.results_of(region)
     ordered = structure._ordered_reads(region)
     out = []
     for label in range(1, len(res.quantified_allele_list) + 1):
-        tracts = [structure.tract_of(region, name).upper() for name, allele in ordered if allele == str(label)]
-        out.append((label, [t for t in tracts if 0 < len(t) <= MAX_TRACT_LEN]))
+        tracts = [(name, structure.tract_of(region, name).upper()) for name, allele in ordered if allele == str(label)]
+        out.append((label, [(n, t) for n, t in tracts if 0 < len(t) <= MAX_TRACT_LEN]))
     return out
+
+
+def allele_groups(region):
+    """named_allele_groups without the names: [(allele id, [tract])]."""
+    return [(label, [t for _, t in tracts]) for label, tracts in named_allele_groups(region)]
 
 
 def consensus_regions(repeat_regions, device=0, engine=None, structure_engine=None, max_dist=None, max_rounds=8):
@@ -70,12 +76,25 @@ def consensus_regions(repeat_regions, device=0, engine=None, structure_engine=No
         return repeat_regions
     kw = {} if max_dist is None else dict(max_dist=max_dist)
     out = engine(groups, max_rounds=max_rounds, device=device, **kw)
-    motifs, motif_of, seqs, seq_motif, described = [], {}, [], [], []
-    for g, (region, ac) in enumerate(owners):
+    fill_consensuses(owners, out)
+    describe_consensuses(owners, structure_engine, device)
+    return repeat_regions
+
+
+def fill_consensuses(owners, out):
+    """Result g of a tract_consensus call into the AlleleConsensus of owners[g] = (region, consensus)."""
+    for g, (_, ac) in enumerate(owners):
         ac.sequence = out["consensus"][g]
         ac.support = np.asarray(out["support"][g], np.int32)
         ac.n_rounds, ac.converged = int(out["n_rounds"][g]), int(out["converged"][g])
         ac.voted, ac.left_out = int(out["voted"][g]), int(out["left_out"][g])
+
+
+def describe_consensuses(owners, structure_engine, device=0):
+    """The structure fields of every consensus of owners = [(region, consensus)] in the region's motif, in one call of
+    `structure_engine` (none when no motif can be aligned)."""
+    motifs, motif_of, seqs, seq_motif, described = [], {}, [], [], []
+    for region, ac in owners:
         unit = region.repeat_unit_seq.upper()
         if structure.motif_supported(unit) and ac.sequence:
             if unit not in motif_of:
@@ -90,17 +109,20 @@ def consensus_regions(repeat_regions, device=0, engine=None, structure_engine=No
         for i, (ac, p) in enumerate(described):
             ac.purity, ac.pure_units, ac.longest_pure_run, ac.interruptions = structure.derive_units(
                 seqs[i], p, int(st["start_phase"][i]), st["path"][off[i]:off[i + 1]])
-    return repeat_regions
 
 
-def consensus_fasta_text(region):
-    p = len(region.repeat_unit_seq)
+def fasta_records(consensuses, p):
+    """FASTA text of AlleleConsensus objects in a motif of p bases."""
     lines = []
-    for ac in getattr(region, "allele_consensus", None) or []:
+    for ac in consensuses:
         lines.append(f">allele{ac.allele_id} reads={ac.voted} left_out={ac.left_out} len={len(ac.sequence)} "
                      f"units={ac.units(p):.1f} rounds={ac.n_rounds} converged={ac.converged}\n")
         lines += [ac.sequence[i:i + 80] + "\n" for i in range(0, len(ac.sequence), 80)]
     return "".join(lines)
+
+
+def consensus_fasta_text(region):
+    return fasta_records(getattr(region, "allele_consensus", None) or [], len(region.repeat_unit_seq))
 
 
 def write_allele_consensus(region):

@@ -5,6 +5,7 @@
 // uploaded once; groups that are done drop out of the next round.
 #include "nanorepeat_amd.h"
 #include "nra_internal.h"
+#include "nra_cons_host.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -25,34 +26,7 @@ int fail(int code, const std::string& msg) { return nra_set_error(code, msg.c_st
                         std::string(#expr) + ": " + hipGetErrorString(e_));                      \
     } while (0)
 
-const int64_t kPtrBudget = int64_t(1) << 30;    // traceback pointer bytes per launch (one tract beyond it goes alone)
-
-int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-
-// a grow-only device buffer
-template <class T> struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t ensure(size_t n)
-    {
-        n = std::max<size_t>(n, 1);
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T));
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-};
-
-// what band class c_idx (c = 1 << c_idx) proves for a tract of n bases on a backbone of t: -1 if it holds no band
-int proven(int c_idx, int n, int t)
-{
-    const int extra = 64 * (1 << c_idx) - 1 - std::abs(t - n);
-    return extra < 0 ? -1 : std::abs(t - n) + 2 * (extra / 2);
-}
+using namespace nra_cons;
 
 struct Tract {
     uint64_t seq;              // byte offset of its codes on the device
@@ -75,8 +49,7 @@ struct Work {
 int run(int32_t n_groups, std::vector<Group>& groups, std::vector<Tract>& tracts, const std::vector<uint8_t>& codes,
         int max_dist, int max_rounds, int64_t* stats)
 {
-    int64_t ptr_budget = kPtrBudget;
-    if (const char* e = getenv("NRA_TEST_CONS_PTR_BYTES")) ptr_budget = std::max<int64_t>(1, atoll(e));
+    const int64_t ptr_budget = nra_cons::ptr_budget();
     DevBuf<uint8_t> d_codes, d_bb, d_nb;
     DevBuf<NraConsGroup> d_groups;
     DevBuf<NraConsItem> d_items;
@@ -138,10 +111,7 @@ int run(int32_t n_groups, std::vector<Group>& groups, std::vector<Tract>& tracts
                     continue;
                 }
                 int cls = tracts[r].cls;
-                if (cls < 0 || proven(cls, n, t) < 0) {
-                    const int want = std::min(max_dist, ad + n / 6 + 8);
-                    for (cls = 0; cls < NRA_CONS_CLASSES - 1 && proven(cls, n, t) < want; ++cls) {}
-                }
+                if (cls < 0 || proven(cls, n, t) < 0) cls = start_class(n, t, max_dist);
                 tracts[r].cls = -1;
                 work.push_back(Work{r, (int32_t)a, cls});
             }

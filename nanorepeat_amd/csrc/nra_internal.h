@@ -304,6 +304,45 @@ struct NraConsItem {
     int32_t group;
 };
 
+// Allele split (nra_split.hip, nra_split_host.cpp): pileup rows by the consensus alignment, column
+// counts and site calls, two haplotypes per group.
+#define NRA_SPLIT_SYM_DELETED 5               // row byte: the tract deleted the column (0..3 base, 4 a code-4 base)
+#define NRA_SPLIT_SYM_NONE 6                  // matrix byte of a tract without a row
+#define NRA_SPLIT_UNDECIDED 2                 // label of a row on neither haplotype
+#define NRA_SPLIT_SITE_INTS 12                // column, two symbols, 4 + 4 counts, supported
+#define NRA_SPLIT_RES_INTS 8                  // split, reads in 0, in 1, undecided, left out, sites, supported, iterations
+#define NRA_SPLIT_THREADS 256                 // k_split_count and k_split_phase
+
+// one alignment of a launch, as NraConsItem; its row starts at byte `row` of the row buffer (a multiple of 16)
+struct NraSplitItem {
+    uint64_t seq;
+    uint64_t ptr;
+    uint64_t row;
+    int32_t n;
+    int32_t group;
+};
+
+// one group: backbone at byte `bb` (t codes); rowtab[rows .. rows + m): the byte offset of each tract's row, -1 without
+// one; its t column entries from `col`; its [site][tract] matrix from byte `mat` (min(max_sites, t) * m bytes); its site
+// records from record `site` (room for min(max_sites, t)); its tracts' labels from `first`
+struct NraSplitGroup {
+    uint64_t bb;
+    uint64_t rows;
+    uint64_t col;
+    uint64_t mat;
+    uint64_t site;
+    int32_t t, m, mv, first;
+};
+
+// one workgroup of k_split_count: 256 columns of a group from col0
+struct NraSplitBlock {
+    int32_t group, col0;
+};
+
+struct NraSplitParams {
+    int32_t min_count, min_share_pct, min_purity_pct, min_sites, max_sites, max_iter;
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -318,6 +357,22 @@ int nra_launch_cons_align(hipStream_t st, int c, int n_items, const NraConsItem*
 int nra_launch_cons_build(hipStream_t st, int n_groups, const NraConsGroup* groups, const uint8_t* backbones,
                           const int32_t* tabs, const int32_t* voters, uint8_t* new_backbones, int32_t* support,
                           int32_t* res);
+
+// allele split (nra_split.hip).  Alignment: as nra_launch_cons_align, but a decided tract leaves its row of column
+// symbols at rows + item.row instead of votes.  Count: per column of every group the base counts over its rows; a site
+// leaves n[b] in col_nb and (a << 2 | b) in col_ab, any other column 0.  Phase: workgroup g lists the sites of group g,
+// cuts them to max_sites, gathers the matrix and runs steps 3 and 4 of the contract; col_pos and col_key are its
+// scratch lists (t entries per group, like col_nb)
+int nra_launch_split_align(hipStream_t st, int c, int n_items, const NraSplitItem* items, const NraSplitGroup* groups,
+                           const uint8_t* seqs, const uint8_t* backbones, uint4* ptrs, uint8_t* rows, int32_t* status,
+                           int max_dist);
+int nra_launch_split_count(hipStream_t st, int n_blocks, const NraSplitBlock* blocks, const NraSplitGroup* groups,
+                           const int64_t* rowtab, const uint8_t* rows, NraSplitParams prm, int32_t* col_nb,
+                           uint8_t* col_ab);
+int nra_launch_split_phase(hipStream_t st, int n_groups, const NraSplitGroup* groups, const int64_t* rowtab,
+                           const uint8_t* rows, NraSplitParams prm, const int32_t* col_nb, const uint8_t* col_ab,
+                           int32_t* col_pos, int32_t* col_key, uint8_t* mats, int32_t* labels, int32_t* sites,
+                           int32_t* res);
 
 // the error message nra_last_error() returns; returns `code` (nra_host.cpp)
 int nra_set_error(int code, const char* msg);

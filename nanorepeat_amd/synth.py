@@ -425,3 +425,52 @@ def motif_panel(reads_per_allele=8, anchor_len=1000, model="hifi", seed=SEED):
     reads = [reads[i] for i in order]
     return dict(ref={"chr1": chrom}, bed=[f"{c}\t{st}\t{en}\t{u}\n" for c, st, en, u in regions], regions=regions,
                 reads=reads, truth=truth, planted=[[want for _, want in alleles] for _, _, alleles in loci])
+
+
+def split_panel(reads_per_haplotype=8, anchor_len=1000, model="hifi", seed=6):
+    """A small panel whose size alleles hold planted pairs of haplotypes of equal size, for the allele split
+    (split.py): an HTT-like locus (BED CAG) with one size allele of two sequences, (CAG)20 CAA CAG beside (CAG)22, and a
+    homogeneous (CAG)40; an FMR1-like one (BED CGG) with two AGG interruptions beside one in 30 units; an RFC1-like one
+    (BED AAAAG) with (AAAAG)18 (AAGGG)4 (AAAAG)18 beside (AAAAG)40 (reads of pure (AAGGG)40 are not sized 40 in an AAAAG
+    template, so the size phasing never puts them into one allele with (AAAAG)40); and a TATTG control with two homogeneous alleles (12 and 30 units).
+    Every haplotype gets `reads_per_haplotype` reads that span both anchors, half reverse-complemented, through the
+    `model` error channel.  Its own random stream; the default seed is one for which the contract's restatement puts
+    every read of every pair on its planted haplotype (other seeds leave a read or two undecided or left out).
+
+    Returns dict(ref, bed, regions, reads, truth) like panel() (truth = {name: (region, size allele)}), plus
+    haplotype = {name: 0 / 1 within a planted pair, None in a homogeneous allele} and planted = [per region, per size
+    allele in size order: (tract of haplotype 0, tract of 1) or None].
+    """
+    rng = np.random.default_rng(seed)
+    fmr = "CGG" * 9 + "AGG" + "CGG" * 9 + "AGG" + "CGG" * 10
+    loci = [("CAG", "CAG" * 22, [("CAG" * 20 + "CAACAG", "CAG" * 22), ("CAG" * 40,)]),
+            ("CGG", "CGG" * 30, [(fmr, "CGG" * 9 + "AGG" + "CGG" * 20)]),
+            ("AAAAG", "AAAAG" * 40, [("AAAAG" * 18 + "AAGGG" * 4 + "AAAAG" * 18, "AAAAG" * 40)]),
+            ("TATTG", "TATTG" * 16, [("TATTG" * 12,), ("TATTG" * 30,)])]
+    gap, extra = 3000, 800
+    parts, regions, at = [], [], 0
+    for unit, ref_tract, _ in loci:
+        left, right = rand_seq(rng, anchor_len + extra), rand_seq(rng, anchor_len + extra)
+        start = at + gap + len(left)
+        regions.append(("chr1", start, start + len(ref_tract), unit))
+        parts += [rand_seq(rng, gap), left, ref_tract, right]
+        at += gap + len(left) + len(ref_tract) + len(right)
+    parts.append(rand_seq(rng, gap))
+    chrom = "".join(parts)
+    raw, truth, haplotype = [], {}, {}
+    for g, ((_, _, alleles), (_, st, en, _)) in enumerate(zip(loci, regions)):
+        for a, tracts in enumerate(alleles):
+            for h, tract in enumerate(tracts):
+                for i in range(reads_per_haplotype):
+                    lo, ro = anchor_len + int(rng.integers(0, 301)), anchor_len + int(rng.integers(0, 301))
+                    name = f"h{g}_{a}_{h}_{i:02d}"
+                    raw.append((name, chrom[st - lo:st] + tract + chrom[en:en + ro]))
+                    truth[name] = (g, a)
+                    haplotype[name] = h if len(tracts) == 2 else None
+    seqs = apply_errors_batch(rng, [s for _, s in raw], model)
+    reads = [(name, revcomp(s) if rng.random() < 0.5 else s) for (name, _), s in zip(raw, seqs)]
+    order = rng.permutation(len(reads))
+    reads = [reads[i] for i in order]
+    return dict(ref={"chr1": chrom}, bed=[f"{c}\t{st}\t{en}\t{u}\n" for c, st, en, u in regions], regions=regions,
+                reads=reads, truth=truth, haplotype=haplotype,
+                planted=[[tr if len(tr) == 2 else None for tr in alleles] for _, _, alleles in loci])
