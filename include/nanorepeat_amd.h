@@ -589,6 +589,46 @@ int nra_allele_split(int device, int32_t n_groups, const int64_t* group_off, int
                      int64_t site_cap, int32_t* sites, int64_t* site_off, int64_t sym_cap, uint8_t* site_sym,
                      int64_t* sym_off, int64_t* stats);
 
+/* ---- motif runs: which motifs a tract is made of, how many units of each, and where (no counterpart in the reference)
+ *
+ * A motif set is M motifs u_0 .. u_{M-1}, 1 <= M <= 8, each uppercase ACGT of p_m = 1..32 bases, with S = sum of p_m <=
+ * 32 states.  State (m, j) means "in motif m, j = motif bases consumed mod p_m"; the states are ordered by (m, j).  A
+ * tract s (n <= 200 000 bases, upper-cased first; a byte other than ACGT mismatches every motif base) is aligned
+ * globally in s against the set, every motif repeated without end, starting and ending at any state; W is the price of
+ * changing motif, 1 <= W <= 1000.  Unit costs otherwise:
+ *   D[0][m,j] = 0 for every state;  for i >= 1, c = s[i-1]:
+ *   T[m,j] = min(D[i-1][m,(j-1) mod p_m] + (c != u_m[(j-1) mod p_m])   diagonal, consumes u_m[(j-1) mod p_m]
+ *                D[i-1][m,j] + 1)                                      insertion; a tie takes the diagonal
+ *   A[m,j] = min(T[m,j], A[m,(j-1) mod p_m] + 1)                       deletion, cyclic inside motif m until stable; a
+ *                                                                      tie keeps T
+ *   b1 = the smallest A over all states, at the smallest state that attains it; b2 = the same over the states of every
+ *        motif other than b1's (absent when M = 1)
+ *   D[i][m,j] = min(A[m,j], (m is not b1's motif ? b1 : b2) + W)       switch; a tie keeps A
+ *   edits = min D[n][.]; the end state is the smallest one that attains it.
+ * No second deletion pass follows the switch: every state of a motif is offered the same b + W, so a cell that takes
+ * the switch has a predecessor at b + W or less and gains nothing from a deletion, and a cell that keeps A has
+ * A <= b + W already and A is closed under deletions.  D[i] is closed as it stands.
+ * Traceback from (n, end state), in the priority diagonal, insertion, deletion, switch: a cell of row i that took the
+ * switch continues at the A-layer of its source state (b1's or b2's) in the same row, so at most one switch happens
+ * between two tract bases; a deletion stays in row i and moves to (m, j-1); an insertion goes to D[i-1][m,j], a
+ * diagonal step to D[i-1][m,j-1].  start_motif and start_phase are the state in which the path reaches row 0 (0, 0 for
+ * an empty tract).  Per tract base one path byte exactly as nra_read_structure writes it (bits 0-1 the op: 0 match, 1
+ * mismatch, 2 insertion; bits 2-7 the motif bases deleted right after it), and one byte with the index, within the
+ * set, of the motif that consumed or inserted the base.  With M = 1 the contract is that of nra_read_structure:
+ * edits, start_phase and the path bytes are the same.  DESIGN.md section 20. */
+
+/* set q = motifs [set_motif_off[q], set_motif_off[q+1]) of the motif list (n_sets >= 1); motif m = bytes [motif_off[m],
+ * motif_off[m+1]) of `motifs`; tract t = bytes [seq_off[t], seq_off[t+1]) of `seqs`, aligned against set tract_set[t].
+ * Writes edits[t], start_phase[t], start_motif[t], and the path bytes and motif bytes of tract t at path[seq_off[t] ...]
+ * and motif_of[seq_off[t] ...] (seq_off[n_tracts] bytes each).  switch_cost <= 0, a set without motifs, a motif of 0
+ * bases or with a byte other than A, C, G, T is NRA_E_ARG; a set of more than 8 motifs or more than 32 motif bases in
+ * all, a tract of more than 200 000 bases or switch_cost > 1000 is NRA_E_RANGE.  Arguments are checked before the
+ * device is touched. */
+int nra_tract_segments(int device, int32_t n_sets, const int32_t* set_motif_off, const char* motifs,
+                       const int64_t* motif_off, int32_t n_tracts, const char* seqs, const int64_t* seq_off,
+                       const int32_t* tract_set, int32_t switch_cost, int32_t* edits, int32_t* start_phase,
+                       int32_t* start_motif, uint8_t* path, uint8_t* motif_of);
+
 #ifdef __cplusplus
 }
 #endif

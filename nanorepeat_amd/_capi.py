@@ -37,7 +37,7 @@ EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count
            "nra_batch1d_fetch", "nra_batch1d_resweeps", "nra_batch2d_fetch", "nra_batch_destroy",
            "nra_screen_create", "nra_screen_reads", "nra_screen_stats", "nra_screen_destroy",
            "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts", "nra_mixture_fit",
-           "nra_tract_consensus", "nra_allele_split")
+           "nra_tract_consensus", "nra_allele_split", "nra_tract_segments")
 
 
 E_RANGE = -3      # NRA_E_RANGE
@@ -191,6 +191,9 @@ def load():
     lib.nra_tract_consensus.restype = C.c_int
     lib.nra_tract_consensus.argtypes = [C.c_int, C.c_int32, pi64, C.c_int32, C.c_char_p, pi64, C.c_int32, C.c_int32,
                                         C.c_int64, C.c_char_p, pi32, pi64, pi32, pi64]
+    lib.nra_tract_segments.restype = C.c_int
+    lib.nra_tract_segments.argtypes = [C.c_int, C.c_int32, pi32, C.c_char_p, pi64, C.c_int32, C.c_char_p, pi64, pi32,
+                                       C.c_int32, pi32, pi32, pi32, p8, p8]
     _LIB = lib
     return lib
 
@@ -801,4 +804,29 @@ def allele_split(groups, backbones, device=0, **thresholds):
                stats={k: int(v) for k, v in zip(SPLIT_STATS, stats)})
     for q, name in enumerate(SPLIT_RES):
         out[name] = res[:, q].copy()
+    return out
+
+
+def tract_segments(sets, tracts, tract_set, switch_cost, device=0):
+    """nra_tract_segments: the alignment of every tract against its motif set (sets[tract_set[i]], a list of motifs)
+    with `switch_cost` for changing motif -> dict(edits, start_phase, start_motif, path, motif_of, path_off): the path
+    bytes and the motif index per base of tract i are path / motif_of[path_off[i]:path_off[i + 1]]."""
+    lib = load()
+    sets = [list(x) for x in sets]
+    soff = np.zeros(len(sets) + 1, np.int32)
+    if sets:
+        np.cumsum([len(x) for x in sets], out=soff[1:])
+    mdata, moff = pack_reads([u for x in sets for u in x])
+    data, off = pack_reads(list(tracts))
+    ts = np.ascontiguousarray(tract_set, np.int32)
+    n = len(off) - 1
+    if len(ts) != n:
+        raise ValueError("one set index per tract")
+    out = dict(edits=np.zeros(n, np.int32), start_phase=np.zeros(n, np.int32), start_motif=np.zeros(n, np.int32),
+               path=np.zeros(int(off[-1]), np.uint8), motif_of=np.zeros(int(off[-1]), np.uint8), path_off=off)
+    _check(lib.nra_tract_segments(device, len(sets), _ptr(soff, C.c_int32), mdata, _ptr(moff, C.c_int64), n, data,
+                                  _ptr(off, C.c_int64), _ptr(ts, C.c_int32), int(switch_cost),
+                                  _ptr(out["edits"], C.c_int32), _ptr(out["start_phase"], C.c_int32),
+                                  _ptr(out["start_motif"], C.c_int32), _ptr(out["path"], C.c_uint8),
+                                  _ptr(out["motif_of"], C.c_uint8)))
     return out

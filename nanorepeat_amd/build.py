@@ -1,7 +1,7 @@
 """Build nanorepeat_amd/libnanorepeat_amd.so (HIP kernels + C ABI) in-tree for gfx950.
 
 hipcc cross-compiles without a GPU.  The kernel file is split into parts
-(-DNRA_PART=1..33) that compile in parallel; the shared library carries only gfx950 code.
+(-DNRA_PART=1..34) that compile in parallel; the shared library carries only gfx950 code.
 """
 import os
 import subprocess
@@ -15,8 +15,8 @@ LIB = os.path.join(HERE, "libnanorepeat_amd.so")
 OBJ = os.path.join(HERE, "csrc", "build")
 
 SOURCES = ["nra_kernels.hip", "nra_sweep.hip", "nra_joint.hip", "nra_trace.hip", "nra_screen.hip", "nra_structure.hip",
-           "nra_motif.hip", "nra_extend.hip", "nra_mixture.hip", "nra_consensus.hip", "nra_split.hip", "nra_host.cpp", "nra_screen_host.cpp", "nra_structure_host.cpp",
-           "nra_motif_host.cpp", "nra_extend_host.cpp", "nra_mixture_host.cpp", "nra_consensus_host.cpp", "nra_split_host.cpp",
+           "nra_motif.hip", "nra_extend.hip", "nra_mixture.hip", "nra_consensus.hip", "nra_split.hip", "nra_segment.hip", "nra_host.cpp", "nra_screen_host.cpp", "nra_structure_host.cpp",
+           "nra_motif_host.cpp", "nra_extend_host.cpp", "nra_mixture_host.cpp", "nra_consensus_host.cpp", "nra_split_host.cpp", "nra_segment_host.cpp",
            "nra_internal.h", "nra_device.h", "nra_pk16.h", "nra_cons_dp.h", "nra_cons_host.h"]
 ARCH = "gfx950"
 
@@ -82,8 +82,11 @@ def build_library(force=False, jobs=None, verbose=False):
     o = os.path.join(OBJ, "nra_split_p33.o")
     objs.append(o)
     cmds.append(common + ["-DNRA_PART=33", "-c", os.path.join(CSRC, "nra_split.hip"), "-o", o])
+    o = os.path.join(OBJ, "nra_segment_p34.o")
+    objs.append(o)
+    cmds.append(common + ["-DNRA_PART=34", "-c", os.path.join(CSRC, "nra_segment.hip"), "-o", o])
     for host in ("nra_host", "nra_screen_host", "nra_structure_host", "nra_motif_host", "nra_extend_host",
-                 "nra_mixture_host", "nra_consensus_host", "nra_split_host"):
+                 "nra_mixture_host", "nra_consensus_host", "nra_split_host", "nra_segment_host"):
         o = os.path.join(OBJ, host + ".o")
         objs.append(o)
         cmds.append(common + ["-pthread", "-c", os.path.join(CSRC, host + ".cpp"), "-o", o])

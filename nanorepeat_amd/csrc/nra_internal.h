@@ -229,6 +229,29 @@ struct NraStructRead {
 // traceback pointer words per (row, lane): ins bits of the P phases, then del bits
 #define NRA_STRUCT_WORDS(P) ((P) <= 16 ? 1 : (P) <= 32 ? 2 : 4)
 
+// Motif runs (nra_segment.hip, nra_segment_host.cpp): the alignment of a tract against a set of motifs with a price for
+// changing motif, one lane per tract.  A launch takes tracts of one state class SC in {8, 16, 32}
+// (the set's states S <= SC), sorted by tract length, descending, 64 to a wave.  Codes, blocks and tract records are
+// those of the repeat structure (NraStructRead.motif = the tract's set).
+#define NRA_SEG_MAX_MOTIFS 8
+#define NRA_SEG_MAX_STATES 32
+#define NRA_SEG_MAX_SWITCH 1000
+
+// a motif set as masks over its S states, state g = (motif m, phase j) in (m, j) order: eq[c] bit g: the motif base a
+// diagonal step into g consumes, u_m[(j - 1) mod p_m], has code c; first / last bit g: g is the first / last state of
+// its motif
+struct NraSegSet {
+    uint32_t eq[4];
+    uint32_t first;
+    uint32_t last;
+    int32_t S;
+    int32_t pad;
+};
+
+// traceback pointer words per (row, lane).  SC 8: ins | del << 8 | sw << 16 | s1 << 24 | s2 << 27; SC 16: (ins |
+// del << 16, sw | s1 << 16 | s2 << 20); SC 32: (ins, del, sw, s1 | s2 << 8).  s1, s2: the states of b1 and b2
+#define NRA_SEG_WORDS(SC) ((SC) <= 8 ? 1 : (SC) <= 16 ? 2 : 4)
+
 // Tandem motifs (nra_motif.hip, nra_motif_host.cpp): per read tract, the tandem positions of each period 1..6 and
 // the counts of their motif classes.  A class is a Lyndon word of p <= 6 bases; its code is the
 // word in base 4, first base most significant; its dense id orders the 964 classes by (p, code).
@@ -394,6 +417,12 @@ int nra_launch_screen_hits(hipStream_t st, int64_t n_tiles, const NraScreenTile*
 // res[2 i] = edits, res[2 i + 1] = start phase of read i
 int nra_launch_structure(hipStream_t st, int P, int n_reads, const NraStructRead* reads, const NraStructMotif* motifs,
                          const uint8_t* codes, uint32_t* ptrs, uint8_t* path, int32_t* res);
+
+// motif runs (nra_segment.hip): one lane per tract, forward DP then traceback.  SC in {8, 16, 32}; res[4 i ..] = edits,
+// start phase, start motif of tract i; `which`: the motif index per tract base, laid out as `path`
+int nra_launch_segment(hipStream_t st, int SC, int n_tracts, const NraStructRead* tracts, const NraSegSet* sets,
+                       const uint8_t* codes, int switch_cost, uint32_t* ptrs, uint8_t* path, uint8_t* which,
+                       int32_t* res);
 
 // anchored extension (nra_extend.hip): one lane per read, forward only, reads and motifs as for nra_launch_structure
 // (NraStructRead.ptr unused).  P in {1..6, 8, 16, 32, 64}; res[4 i ..] = score, end row, end phase, motif bases of read i

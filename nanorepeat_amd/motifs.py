@@ -92,10 +92,11 @@ class ReadMotifs:
 
 def motif_regions(repeat_regions, fast_mode=False, device=0, engine=None, scorer=None, scoring=None,
                   max_period=MAX_PERIOD, top_n=TOP_N, min_motif_count=MIN_MOTIF_COUNT,
-                  min_motif_share=MIN_MOTIF_SHARE):
+                  min_motif_share=MIN_MOTIF_SHARE, resize=True):
     """The motifs of every read with a core in every region (one call of `engine`, default _capi.tract_motifs; tests
     pass a restatement with the same signature), the calls, and the re-sizing of the reads whose call is not the BED
-    class (one call of `scorer`, default _capi.round3_1d, as round 3 uses it).  Sets `region.read_motifs` =
+    class (one call of `scorer`, default _capi.round3_1d, as round 3 uses it; not with resize=False, which leaves
+    every Size_In_Motif empty: segments.py wants the classes only).  Sets `region.read_motifs` =
     {read_name: ReadMotifs} and `region.motif_bed_class`; returns the regions."""
     engine = engine or _capi.tract_motifs
     scorer = scorer or _capi.round3_1d
@@ -118,7 +119,8 @@ def motif_regions(repeat_regions, fast_mode=False, device=0, engine=None, scorer
             rm.top = [(class_string(int(p), int(c)), int(k))
                       for p, c, k in zip(out["top_p"][i], out["top_code"][i], out["top_count"][i]) if k > 0]
             rm.call = dominant_call(rm.top, rm.tract_len, min_motif_count, min_motif_share)
-    _resize(repeat_regions, fast_mode, device, scorer, scoring)
+    if resize:
+        _resize(repeat_regions, fast_mode, device, scorer, scoring)
     return repeat_regions
 
 

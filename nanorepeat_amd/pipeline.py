@@ -169,7 +169,8 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
                       remove_noisy_reads=False, no_check_repeat_motif_in_ref=False, no_details=False,
                       num_cpu=1, device=0, scoring=None, seed=None, read_structure=False, discover_motifs=False,
                       min_motif_count=4, min_motif_share=0.1, partial_reads=False, mixture="sklearn",
-                      allele_consensus=False, allele_split=False, **engines):
+                      allele_consensus=False, allele_split=False, motif_runs=False, segment_motifs=None,
+                      switch_cost=None, **engines):
     """The BAM command from files to files (nanoRepeat_bam.py:614-751): for every region of the BED
     file, reads from the alignment file -> `<out_prefix>.details/<chr>/<region>.*` ->
     `<out_prefix>.NanoRepeat_output.tsv`.  The reference forks up to 16 workers, one region each;
@@ -182,8 +183,12 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
     read shows more than the largest spanning read.  mixture="gpu" fits the phasing mixtures on the GPU (see
     phase_regions).  allele_consensus=True adds the consensus sequence of every allele's tract (consensus.py);
     allele_split=True adds the allele split files: alleles that hold two sequences of one size (split.py).
+    motif_runs=True adds the motif run files (segments.py): every read's tract and every allele's consensus cut into
+    runs of the motifs of the region's motif set (the BED motif, then segment_motifs[region key] when that dict names
+    the region, else the motifs discovered in the reads); switch_cost is the price of changing motif (None: the
+    default of segments.py).
     `engines` may carry aligner / scorer / structure_engine / motif_engine / extension_engine / mixture_engine /
-    consensus_engine / split_engine stand-ins.  Returns the regions."""
+    consensus_engine / split_engine / segment_engine stand-ins.  Returns the regions."""
     from . import bam as nr_bam, mixture as nr_mixture
     nr_mixture.check_engine_name(mixture)
     regions = nr_io.read_repeat_region_file(repeat_region_bed, no_details)
@@ -202,7 +207,8 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
     _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
                         read_structure, _motif_options(discover_motifs, min_motif_count, min_motif_share),
-                        partial_reads, mixture, allele_consensus, allele_split)
+                        partial_reads, mixture, allele_consensus, allele_split,
+                        _run_options(motif_runs, segment_motifs, switch_cost))
     return regions
 
 
@@ -221,10 +227,14 @@ def _motif_options(discover_motifs, min_motif_count, min_motif_share):
     return dict(min_motif_count=min_motif_count, min_motif_share=min_motif_share) if discover_motifs else None
 
 
+def _run_options(motif_runs, segment_motifs, switch_cost):
+    return dict(segment_motifs=segment_motifs, switch_cost=switch_cost) if motif_runs else None
+
+
 def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
                         read_structure=False, motif_options=None, partial_reads=False, mixture="sklearn",
-                        allele_consensus=False, allele_split=False):
+                        allele_consensus=False, allele_split=False, run_options=None):
     """The commands' common tail: steps 1-4 for the regions with reads, then one TSV row per BED region; with
     read_structure, the structure of every read with a size and the two structure files; with motif_options (a dict
     of motifs.motif_regions keywords), the tandem motifs of every read with a core and the two motif files; with
@@ -232,7 +242,8 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
     such reads show more repeat units than any spanning read; with allele_consensus, the consensus of every allele's
     tracts, the two consensus files and one NOTICE counting the alleles that did not converge or left reads out; with
     allele_split, the split of every allele by tract sequence, the three split files and one NOTICE counting the alleles
-    split."""
+    split; with run_options (a dict of segments.segments_regions keywords), the motif runs of every read with a core and
+    of every allele's consensus, the two run files and one NOTICE counting the alleles of more than one run."""
     quantify_regions(live, reads_of, data_type, fast_mode, num_cpu, device, scoring,
                      engines.get("aligner"), engines.get("scorer"))
     phase_regions(live, data_type, ploidy, max_mutual_overlap, max_num_components, remove_noisy_reads, seed,
@@ -277,6 +288,16 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
             split.write_allele_split(region)
         split.write_split_summary(regions, out_prefix)
         split.report_split_alleles(live)
+    if run_options is not None:
+        from . import segments
+        segments.segments_regions(live, device=device, engine=engines.get("segment_engine"),
+                                  motif_engine=engines.get("motif_engine"),
+                                  consensus_engine=engines.get("consensus_engine"),
+                                  structure_engine=engines.get("structure_engine"), **run_options)
+        for region in live:
+            segments.write_read_runs(region)
+        segments.write_runs_summary(regions, out_prefix)
+        segments.report_multi_run_alleles(live)
     if no_details:
         import shutil
         shutil.rmtree(f"{out_prefix}.details", ignore_errors=True)
@@ -287,7 +308,8 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         remove_noisy_reads=False, no_check_repeat_motif_in_ref=False, no_details=False,
                         num_cpu=1, device=0, scoring=None, seed=None, screen=True, k=15, min_hits=4, max_occ=16,
                         chunk_bases=1 << 28, read_structure=False, discover_motifs=False, min_motif_count=4,
-                        min_motif_share=0.1, mixture="sklearn", allele_consensus=False, allele_split=False, **engines):
+                        min_motif_share=0.1, mixture="sklearn", allele_consensus=False, allele_split=False,
+                        motif_runs=False, segment_motifs=None, switch_cost=None, **engines):
     """The FASTQ / FASTA command (nanoRepeat.py:109, `-t fastq|fasta`) from files to files, without a genome mapper:
     the reads each region sees are chosen by the anchor k-mer screen (screen.reads_by_region) instead of a
     genome-wide mapping and a BAM window, then the BAM command's steps run unchanged.  Every region's reference
@@ -297,8 +319,9 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
     panels.  read_structure=True adds the repeat structure files (structure.py); discover_motifs=True adds the
     tandem motif files (motifs.py).  mixture="gpu" fits the phasing mixtures on the GPU (see phase_regions).
     allele_consensus=True adds the consensus sequence of every allele's tract (consensus.py); allele_split=True adds
-    the allele split files (split.py).  `engines` may carry aligner / scorer / screener / structure_engine /
-    motif_engine / mixture_engine / consensus_engine / split_engine stand-ins.  Returns the regions."""
+    the allele split files (split.py); motif_runs=True adds the motif run files (segments.py; segment_motifs and
+    switch_cost as for quantify_from_bam).  `engines` may carry aligner / scorer / screener / structure_engine /
+    motif_engine / mixture_engine / consensus_engine / split_engine / segment_engine stand-ins.  Returns the regions."""
     from . import screen as nr_screen, mixture as nr_mixture
     nr_mixture.check_engine_name(mixture)
     regions = nr_io.read_repeat_region_file(repeat_region_bed, no_details)
@@ -325,7 +348,8 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
     _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
                         read_structure, _motif_options(discover_motifs, min_motif_count, min_motif_share),
-                        mixture=mixture, allele_consensus=allele_consensus, allele_split=allele_split)
+                        mixture=mixture, allele_consensus=allele_consensus, allele_split=allele_split,
+                        run_options=_run_options(motif_runs, segment_motifs, switch_cost))
     return regions
 
 
