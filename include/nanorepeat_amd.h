@@ -250,6 +250,19 @@ int nra_align_pairs_cigar(int device,
                           int32_t* qstart, int32_t* qend,
                           char* cigar, int64_t cigar_cap, int64_t* cigar_off);
 
+/* The same call for queries of any length: arguments and outputs as nra_align_pairs_cigar, query <= 200 000 bases,
+ * target <= 65 000, qlen * tlen bytes of trace per pair and 8 GiB per call at most (NRA_E_RANGE beyond any of these,
+ * before the device is touched).  A query beyond 3072 bases is filled in row blocks of 1536 rows, each a wave of its
+ * own, chained like the sweeps of nra_round3_1d; a pair whose score may pass 32 000 runs in 64-bit cells.  Every
+ * output equals the oracle's traceback bit for bit.  DESIGN.md section 21. */
+int nra_align_paths(int device,
+                    int32_t n_seqs, const char* seqs, const int64_t* seq_off,
+                    int64_t n_pairs, const int32_t* pair_query, const int32_t* pair_target,
+                    const nra_scoring_t* sc, int32_t flags,
+                    int32_t* score, int32_t* tstart, int32_t* tend,
+                    int32_t* qstart, int32_t* qend,
+                    char* cigar, int64_t cigar_cap, int64_t* cigar_off);
+
 /* ---- device-resident batches (what bench.py times): create = encode + H2D,
  *      run = kernels only (asynchronous on the batch's own stream), fetch = D2H ------- */
 int  nra_batch1d_create(int device,

@@ -32,7 +32,7 @@ F_FULL_ANCHORS = 8192  # testing / comparison, 1D: the exact cell over every anc
 
 # every symbol include/nanorepeat_amd.h declares
 EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count",
-           "nra_default_scoring", "nra_release_cached_memory", "nra_round3_1d", "nra_joint_2d", "nra_align_pairs", "nra_align_pairs_cigar", "nra_batch1d_create",
+           "nra_default_scoring", "nra_release_cached_memory", "nra_round3_1d", "nra_joint_2d", "nra_align_pairs", "nra_align_pairs_cigar", "nra_align_paths", "nra_batch1d_create",
            "nra_batch2d_create", "nra_batch2d_create_reads", "nra_batch2d_set_cells", "nra_joint_grid_cells", "nra_batch2d_set_grid", "nra_batch2d_invalidate", "nra_batch2d_sweep_flanks", "nra_batch2d_refine", "nra_batch_run", "nra_batch_sync", "nra_batch_stats",
            "nra_batch1d_fetch", "nra_batch1d_resweeps", "nra_batch2d_fetch", "nra_batch_destroy",
            "nra_screen_create", "nra_screen_reads", "nra_screen_stats", "nra_screen_destroy",
@@ -129,6 +129,8 @@ def load():
     lib.nra_align_pairs_cigar.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, C.c_int64, pi32, pi32,
                                           C.POINTER(Scoring), C.c_int32, pi32, pi32, pi32, pi32, pi32,
                                           C.c_char_p, C.c_int64, pi64]
+    lib.nra_align_paths.restype = C.c_int
+    lib.nra_align_paths.argtypes = lib.nra_align_pairs_cigar.argtypes
     lib.nra_batch1d_create.restype = C.c_int
     lib.nra_batch1d_create.argtypes = [C.c_int, C.POINTER(Region), C.c_int32, C.c_int32, C.c_char_p,
                                        pi64, pi32, pi32, pi32, C.POINTER(Scoring), C.c_int32,
@@ -389,7 +391,7 @@ def align_pairs(seqs, pair_query, pair_target, sc=None, flags=0, device=0):
     return out
 
 
-def align_pairs_cigar(seqs, pair_query, pair_target, sc=None, flags=0, device=0):
+def align_pairs_cigar(seqs, pair_query, pair_target, sc=None, flags=0, device=0, entry="nra_align_pairs_cigar"):
     """nra_align_pairs_cigar: like align_pairs, plus qstart/qend and the --eqx CIGAR of each pair."""
     lib = load()
     sc = sc or default_scoring()
@@ -402,10 +404,10 @@ def align_pairs_cigar(seqs, pair_query, pair_target, sc=None, flags=0, device=0)
     cap = int(sum(12 * (int(lens[q]) + int(lens[t])) + 16 for q, t in zip(pq, pt))) + 16
     buf = C.create_string_buffer(cap)
     coff = np.zeros(n + 1, np.int64)
-    _check(lib.nra_align_pairs_cigar(device, len(seqs), data, _ptr(off, C.c_int64), n, _ptr(pq, C.c_int32),
-                                     _ptr(pt, C.c_int32), C.byref(sc), flags,
-                                     *[_ptr(out[k], C.c_int32) for k in ("score", "tstart", "tend", "qstart", "qend")],
-                                     buf, cap, _ptr(coff, C.c_int64)))
+    _check(getattr(lib, entry)(device, len(seqs), data, _ptr(off, C.c_int64), n, _ptr(pq, C.c_int32),
+                               _ptr(pt, C.c_int32), C.byref(sc), flags,
+                               *[_ptr(out[k], C.c_int32) for k in ("score", "tstart", "tend", "qstart", "qend")],
+                               buf, cap, _ptr(coff, C.c_int64)))
     raw = buf.raw
     out["cigar"] = [raw[coff[i]:coff[i + 1] - 1].decode() for i in range(n)]
     return out
@@ -414,8 +416,24 @@ def align_pairs_cigar(seqs, pair_query, pair_target, sc=None, flags=0, device=0)
 TRACE_CHUNK_BYTES = 6 << 30        # nra_align_pairs_cigar keeps one trace byte per DP cell, <= 8 GiB per call
 
 
+def align_paths(seqs, pair_query, pair_target, sc=None, flags=0, device=0):
+    """nra_align_paths: align_pairs_cigar for queries of up to 200 000 bases (targets of up to 65 000)."""
+    return align_pairs_cigar(seqs, pair_query, pair_target, sc=sc, flags=flags, device=device, entry="nra_align_paths")
+
+
+PATHS_MAX_QUERY = 200000           # nra_align_paths: NRA_E_RANGE beyond these
+PATHS_MAX_TARGET = 65000
+PATHS_MAX_TRACE = 8 << 30
+
+
+def align_paths_chunked(seqs, pair_query, pair_target, sc=None, flags=0, device=0, chunk_bytes=TRACE_CHUNK_BYTES):
+    """align_paths for any number of pairs, split like align_pairs_cigar_chunked."""
+    return align_pairs_cigar_chunked(seqs, pair_query, pair_target, sc=sc, flags=flags, device=device,
+                                     chunk_bytes=chunk_bytes, call=align_paths)
+
+
 def align_pairs_cigar_chunked(seqs, pair_query, pair_target, sc=None, flags=0, device=0,
-                              chunk_bytes=TRACE_CHUNK_BYTES):
+                              chunk_bytes=TRACE_CHUNK_BYTES, call=align_pairs_cigar):
     """align_pairs_cigar for any number of pairs: splits the list so that each call's trace
     (query length x target length bytes per pair) stays below `chunk_bytes`, and sends each call
     only the sequences it uses."""
@@ -432,8 +450,8 @@ def align_pairs_cigar_chunked(seqs, pair_query, pair_target, sc=None, flags=0, d
             used += cost; hi += 1
         ids = sorted({int(x) for x in pair_query[lo:hi]} | {int(x) for x in pair_target[lo:hi]})
         local = {g: i for i, g in enumerate(ids)}
-        part = align_pairs_cigar([seqs[g] for g in ids], [local[int(x)] for x in pair_query[lo:hi]],
-                                 [local[int(x)] for x in pair_target[lo:hi]], sc=sc, flags=flags, device=device)
+        part = call([seqs[g] for g in ids], [local[int(x)] for x in pair_query[lo:hi]],
+                    [local[int(x)] for x in pair_target[lo:hi]], sc=sc, flags=flags, device=device)
         for k in ("score", "tstart", "tend", "qstart", "qend"):
             out[k][lo:hi] = part[k]
         out["cigar"][lo:hi] = part["cigar"]

@@ -3506,69 +3506,138 @@ int nra_align_pairs(int device, int32_t n_seqs, const char* seqs, const int64_t*
     return NRA_OK;
 }
 
-int nra_align_pairs_cigar(int device, int32_t n_seqs, const char* seqs, const int64_t* seq_off, int64_t n_pairs,
-                          const int32_t* pair_query, const int32_t* pair_target, const nra_scoring_t* sc,
-                          int32_t flags, int32_t* score, int32_t* tstart, int32_t* tend, int32_t* qstart,
-                          int32_t* qend, char* cigar, int64_t cigar_cap, int64_t* cigar_off)
+namespace {
+
+// nra_align_pairs_cigar and nra_align_paths: the trace of every pair, its best cell, the walk back and the CIGAR.
+// paths = false: queries of one register block in int32 cells, a launch per rows-per-lane bucket (k_trace_fill).
+// paths = true: those pairs the same way; a query beyond one register block, or a pair whose score outgrows the
+// int32 cell, in row blocks of block_r rows per lane (k_trace_fill_mt), and with force_blocks every pair so.
+int align_cigar_pairs(int device, int32_t n_seqs, const char* seqs, const int64_t* seq_off, int64_t n_pairs,
+                      const int32_t* pair_query, const int32_t* pair_target, const nra_scoring_t* sc, bool paths,
+                      int block_r, bool force_blocks, int32_t* score, int32_t* tstart, int32_t* tend, int32_t* qstart,
+                      int32_t* qend, char* cigar, int64_t cigar_cap, int64_t* cigar_off)
 {
-    (void)flags;
     if (n_pairs > 0 && (!score || !tstart || !tend || !qstart || !qend || !cigar || !cigar_off || cigar_cap < 1))
         return fail(NRA_E_ARG, "NULL output array");
     PairSetup ps;
     int rc = prepare_pairs(device, n_seqs, seqs, seq_off, n_pairs, pair_query, pair_target, sc, ps,
-                           NRA_MAX_QLEN_1BLOCK, NRA_MAX_TLEN, kScoreCapI32);
+                           paths ? NRA_MAX_QLEN : NRA_MAX_QLEN_1BLOCK, NRA_MAX_TLEN,
+                           paths ? (int64_t)1 << 40 : kScoreCapI32);
     if (rc) return rc;
     if (cigar_off) cigar_off[0] = 0;
     if (n_pairs == 0) return NRA_OK;
 
-    // one launch per rows-per-lane bucket; tasks keep their pair index through `order`
+    // launch groups: row blocks in 64-bit cells, row blocks in int32 cells, then one per rows-per-lane bucket;
+    // tasks keep their pair index through `order`
     std::vector<std::vector<int64_t>> by_bucket((size_t)kNumR);
+    std::vector<int64_t> by_blocks[2];                 // [wide]
     for (int64_t i = 0; i < n_pairs; ++i) {
         const int32_t qi = ps.as_query[pair_query[i]];
-        if (ps.dreads[qi].qlen == 0 || ps.dregs[ps.as_target[pair_target[i]]].l1 == 0) continue;
-        by_bucket[rows_for_qlen(ps.dreads[qi].qlen)].push_back(i);
+        const int64_t ql = ps.dreads[qi].qlen, tl = ps.dregs[ps.as_target[pair_target[i]]].l1;
+        if (ql == 0 || tl == 0) continue;
+        const bool wide = paths && max_score(sc, std::min(ql, tl)) > kScoreCapI32;
+        if (paths && (force_blocks || wide || ql > NRA_MAX_QLEN_1BLOCK)) by_blocks[wide ? 1 : 0].push_back(i);
+        else by_bucket[rows_for_qlen((int)ql)].push_back(i);
     }
+    struct Launch { int R; size_t off; int count; bool blocks, wide; size_t blk_off; int n_blocks; };
     std::vector<NraTraceTask> tasks;
     std::vector<int64_t> order;
-    std::vector<std::pair<int, size_t>> launches;
-    std::vector<int> counts;
-    uint64_t trace_bytes = 0, ops_bytes = 0;
+    std::vector<Launch> launches;
+    std::vector<NraTraceBlock> blocks;
+    uint64_t trace_bytes = 0, ops_bytes = 0, strip_granules = 0;
+    size_t n_blk_slots = 0;
+    auto add_task = [&](int64_t i) {
+        NraTraceTask t{};
+        t.read = ps.as_query[pair_query[i]];
+        t.region = ps.as_target[pair_target[i]];
+        const uint64_t ql = (uint64_t)ps.dreads[t.read].qlen, tl = (uint64_t)ps.dregs[t.region].l1;
+        t.ops_cap = (int32_t)(ql + tl);
+        t.trace_off = trace_bytes; t.ops_off = ops_bytes;
+        trace_bytes += ql * tl; ops_bytes += ql + tl;
+        tasks.push_back(t); order.push_back(i);
+    };
+    const int block_rows = 64 * block_r;
+    for (int w = 1; w >= 0; --w) {
+        if (by_blocks[w].empty()) continue;
+        Launch L{block_r, tasks.size(), (int)by_blocks[w].size(), true, w == 1, blocks.size(), 0};
+        std::vector<uint64_t> strip0;                  // the strip under block 0 of each task of the launch
+        int most = 0;
+        for (int64_t i : by_blocks[w]) {
+            add_task(i);
+            NraTraceTask& t = tasks.back();
+            const int nblk = (ps.dreads[t.read].qlen + block_rows - 1) / block_rows;
+            t.blk0 = (int32_t)n_blk_slots;
+            n_blk_slots += (size_t)nblk;
+            strip0.push_back(strip_granules);
+            strip_granules += (uint64_t)(nblk - 1) * (w ? 6 : 3) * (uint64_t)((ps.dregs[t.region].l1 + 63) & ~63);
+            most = std::max(most, nblk);
+        }
+        // a producer precedes its consumer: the blocks 0 of every task, then the blocks 1, ...
+        for (int b = 0; b < most; ++b)
+            for (int k = 0; k < L.count; ++k) {
+                const NraTraceTask& t = tasks[L.off + (size_t)k];
+                const int nblk = (ps.dreads[t.read].qlen + block_rows - 1) / block_rows;
+                if (b >= nblk) continue;
+                const uint64_t per = (uint64_t)(w ? 6 : 3) * (uint64_t)((ps.dregs[t.region].l1 + 63) & ~63);
+                NraTraceBlock nb{};
+                nb.task = k; nb.blk = b; nb.nblk = nblk;
+                nb.strip_in = b > 0 ? strip0[(size_t)k] + (uint64_t)(b - 1) * per : 0;
+                nb.strip_out = b + 1 < nblk ? strip0[(size_t)k] + (uint64_t)b * per : 0;
+                blocks.push_back(nb);
+            }
+        L.n_blocks = (int)(blocks.size() - L.blk_off);
+        launches.push_back(L);
+    }
     for (int bi = kNumR - 1; bi >= 0; --bi) {
         if (by_bucket[bi].empty()) continue;
-        launches.push_back({kRList[bi], tasks.size()});
-        counts.push_back((int)by_bucket[bi].size());
-        for (int64_t i : by_bucket[bi]) {
-            NraTraceTask t{};
-            t.read = ps.as_query[pair_query[i]];
-            t.region = ps.as_target[pair_target[i]];
-            const uint64_t ql = (uint64_t)ps.dreads[t.read].qlen, tl = (uint64_t)ps.dregs[t.region].l1;
-            t.ops_cap = (int32_t)(ql + tl);
-            t.trace_off = trace_bytes; t.ops_off = ops_bytes;
-            trace_bytes += ql * tl; ops_bytes += ql + tl;
-            tasks.push_back(t); order.push_back(i);
-        }
+        launches.push_back(Launch{kRList[bi], tasks.size(), (int)by_bucket[bi].size(), false, false, 0, 0});
+        for (int64_t i : by_bucket[bi]) add_task(i);
     }
     if (trace_bytes > (8ull << 30)) return fail(NRA_E_RANGE, "trace needs more than 8 GiB: split the call");
     const size_t nt = tasks.size();
     Arena arena;                       // before the buffers: released after them
     arena.device = device;
     ArenaScope arena_scope(&arena);
-    arena.expect(ps.pool.size() + ps.q2bit.size() * 6 + nt * 128 + (size_t)ops_bytes + (2u << 20));
+    arena.expect(ps.pool.size() + ps.q2bit.size() * 6 + nt * 128 + (size_t)ops_bytes + blocks.size() * 48 + (2u << 20));
     DevBuf<uint8_t> d_pool, d_trace, d_ops; DevBuf<uint32_t> d_q2, d_nm; DevBuf<NraDevRegion> d_regs;
-    DevBuf<NraDevRead> d_reads; DevBuf<NraTraceTask> d_tasks; DevBuf<int32_t> d_fill, d_back;
+    DevBuf<NraDevRead> d_reads; DevBuf<NraTraceTask> d_tasks; DevBuf<int32_t> d_fill, d_back, d_best, d_words;
+    DevBuf<NraTraceBlock> d_blocks; DevBuf<uint64_t> d_strips;
     HIP_TRY(d_pool.upload(ps.pool)); HIP_TRY(d_q2.upload(ps.q2bit)); HIP_TRY(d_nm.upload(ps.nmask));
     HIP_TRY(d_regs.upload(ps.dregs)); HIP_TRY(d_reads.upload(ps.dreads)); HIP_TRY(d_tasks.upload(tasks));
     HIP_TRY(d_trace.alloc((size_t)trace_bytes)); HIP_TRY(d_ops.alloc((size_t)ops_bytes));
     HIP_TRY(d_fill.alloc(nt * 5)); HIP_TRY(d_back.alloc(nt * 3));
+    if (!blocks.empty()) {
+        // words: a ticket per launch of row blocks, then the error word; the strips start without this call's epoch
+        HIP_TRY(d_blocks.upload(blocks)); HIP_TRY(d_best.alloc(n_blk_slots * 4)); HIP_TRY(d_words.alloc(4));
+        HIP_TRY(d_strips.alloc((size_t)strip_granules + 1));
+        HIP_TRY(hipMemsetAsync(d_words.p, 0, 4 * sizeof(int32_t), nullptr));
+        HIP_TRY(hipMemsetAsync(d_strips.p, 0, ((size_t)strip_granules + 1) * 8, nullptr));
+    }
     const NraScoreParams sp = to_params(*sc);
-    for (size_t i = 0; i < launches.size(); ++i) {
-        const size_t off = launches[i].second;
-        LAUNCH_TRY(nra_launch_trace_fill(launches[i].first, ps.has_n ? 1 : 0, nullptr, counts[i], d_tasks.p + off,
-                                         d_reads.p, d_regs.p, d_pool.p, d_q2.p, d_nm.p, sp, d_trace.p, d_fill.p + off * 5));
-        LAUNCH_TRY(nra_launch_trace_back(nullptr, counts[i], d_tasks.p + off, d_reads.p, d_regs.p, d_trace.p,
+    int n_block_launches = 0;
+    for (const Launch& L : launches) {
+        const size_t off = L.off;
+        if (L.blocks) {
+            LAUNCH_TRY(nra_launch_trace_fill_mt(L.R, ps.has_n ? 1 : 0, L.wide ? 1 : 0, nullptr, L.n_blocks,
+                                                d_blocks.p + L.blk_off, d_words.p + n_block_launches, d_tasks.p + off,
+                                                d_reads.p, d_regs.p, d_pool.p, d_q2.p, d_nm.p, sp, d_trace.p, d_best.p,
+                                                d_strips.p, 1u, d_words.p + 3));
+            LAUNCH_TRY(nra_launch_trace_best(nullptr, L.count, d_tasks.p + off, d_reads.p, block_rows, L.wide ? 1 : 0,
+                                             d_best.p, sp, d_fill.p + off * 5));
+            ++n_block_launches;
+        } else {
+            LAUNCH_TRY(nra_launch_trace_fill(L.R, ps.has_n ? 1 : 0, nullptr, L.count, d_tasks.p + off,
+                                             d_reads.p, d_regs.p, d_pool.p, d_q2.p, d_nm.p, sp, d_trace.p, d_fill.p + off * 5));
+        }
+        LAUNCH_TRY(nra_launch_trace_back(nullptr, L.count, d_tasks.p + off, d_reads.p, d_regs.p, d_trace.p,
                                          d_fill.p + off * 5, d_ops.p, d_back.p + off * 3));
     }
     HIP_TRY(hipDeviceSynchronize());
+    if (!blocks.empty()) {
+        int32_t gave_up = 0;
+        HIP_TRY(copy_d2h(&gave_up, d_words.p + 3, 4));
+        if (gave_up) return fail(NRA_E_DEVICE, "trace fill: a row block waited too long for the block above it");
+    }
     std::vector<int32_t> fill(nt * 5), back(nt * 3);
     std::vector<uint8_t> ops((size_t)ops_bytes);
     if (nt) {
@@ -3605,6 +3674,56 @@ int nra_align_pairs_cigar(int device, int32_t n_seqs, const char* seqs, const in
     }
     cigar_off[n_pairs] = pos;
     return NRA_OK;
+}
+
+}  // namespace
+
+int nra_align_pairs_cigar(int device, int32_t n_seqs, const char* seqs, const int64_t* seq_off, int64_t n_pairs,
+                          const int32_t* pair_query, const int32_t* pair_target, const nra_scoring_t* sc,
+                          int32_t flags, int32_t* score, int32_t* tstart, int32_t* tend, int32_t* qstart,
+                          int32_t* qend, char* cigar, int64_t cigar_cap, int64_t* cigar_off)
+{
+    (void)flags;
+    return align_cigar_pairs(device, n_seqs, seqs, seq_off, n_pairs, pair_query, pair_target, sc, false, 0, false,
+                             score, tstart, tend, qstart, qend, cigar, cigar_cap, cigar_off);
+}
+
+int nra_align_paths(int device, int32_t n_seqs, const char* seqs, const int64_t* seq_off, int64_t n_pairs,
+                    const int32_t* pair_query, const int32_t* pair_target, const nra_scoring_t* sc,
+                    int32_t flags, int32_t* score, int32_t* tstart, int32_t* tend, int32_t* qstart,
+                    int32_t* qend, char* cigar, int64_t cigar_cap, int64_t* cigar_off)
+{
+    (void)flags;
+    // the limits, before the device is touched
+    if (n_seqs < 0 || n_pairs < 0) return fail(NRA_E_ARG, "negative count");
+    if (n_seqs > 0 && (!seqs || !seq_off)) return fail(NRA_E_ARG, "NULL sequence array");
+    if (n_pairs > 0 && (!pair_query || !pair_target)) return fail(NRA_E_ARG, "NULL pair array");
+    uint64_t trace_bytes = 0;
+    for (int64_t i = 0; i < n_pairs; ++i) {
+        const int32_t q = pair_query[i], t = pair_target[i];
+        if (q < 0 || q >= n_seqs || t < 0 || t >= n_seqs) return fail(NRA_E_ARG, "pair index out of range");
+        const int64_t ql = seq_off[q + 1] - seq_off[q], tl = seq_off[t + 1] - seq_off[t];
+        if (ql < 0 || tl < 0) return fail(NRA_E_ARG, "seq_off must be non-decreasing");
+        if (ql > NRA_MAX_QLEN) return fail(NRA_E_RANGE, "query longer than " + std::to_string(NRA_MAX_QLEN));
+        if (tl > NRA_MAX_TLEN) return fail(NRA_E_RANGE, "target longer than " + std::to_string(NRA_MAX_TLEN));
+        trace_bytes += (uint64_t)ql * (uint64_t)tl;
+        if (trace_bytes > (8ull << 30)) return fail(NRA_E_RANGE, "trace needs more than 8 GiB: split the call");
+    }
+    // NRA_TEST_TRACE_BLOCK_ROWS (tests): every pair in row blocks of so many rows, a height the kernel is built for
+    int block_r = NRA_TRACE_CHAIN_R;
+    bool force_blocks = false;
+    if (const char* e = getenv("NRA_TEST_TRACE_BLOCK_ROWS")) {
+        const int rows = atoi(e);
+        bool built = false;
+#define CASE(r) built = built || rows == 64 * (r);
+        NRA_TRACE_MT_R_LIST(CASE)
+#undef CASE
+        if (!built) return fail(NRA_E_ARG, "NRA_TEST_TRACE_BLOCK_ROWS: 64 x one of 1, 2, 3, 4, 6, 8, 12, 16, 24");
+        block_r = rows / 64;
+        force_blocks = true;
+    }
+    return align_cigar_pairs(device, n_seqs, seqs, seq_off, n_pairs, pair_query, pair_target, sc, true, block_r,
+                             force_blocks, score, tstart, tend, qstart, qend, cigar, cigar_cap, cigar_off);
 }
 
 // ---- common -------------------------------------------------------------------------

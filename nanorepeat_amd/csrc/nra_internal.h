@@ -124,10 +124,24 @@ struct NraTraceTask {
     int32_t read;        // query (2-bit pool)
     int32_t region;      // target = piece 1 of this region
     int32_t ops_cap;     // qlen + tlen
-    int32_t pad;
+    int32_t blk0;        // k_trace_fill_mt: the slot of the pair's first row block in the best-cell records
     uint64_t trace_off;  // qlen * tlen bytes, row-major
     uint64_t ops_off;
 };
+
+// One (pair, row block) of the trace fill in row blocks (k_trace_fill_mt): waves take these by ticket, in list
+// order -- a producer (block b) precedes its consumer (block b + 1).  A strip is 3 planes (6 in 64-bit cells) of
+// the pair's columns, rounded up to 64, in 8-byte granules; strip_in / strip_out are granule offsets.
+struct NraTraceBlock {
+    int32_t task;
+    int32_t blk, nblk;
+    int32_t pad;
+    uint64_t strip_in, strip_out;
+};
+#define NRA_TRACE_CHAIN_R NRA_CHAIN_R          // rows per lane of a row block: the height the chained payload sweeps use
+// the rows per lane k_trace_fill_mt is built for: NRA_TRACE_CHAIN_R, and the smaller ones the tests may ask for
+// (NRA_TEST_TRACE_BLOCK_ROWS = 64 * one of these).  48 rows per lane of 64-bit cells would spill.
+#define NRA_TRACE_MT_R_LIST(X) X(1) X(2) X(3) X(4) X(6) X(8) X(12) X(16) X(24)
 
 // One candidate scored with a payload (extents / window kernels).
 struct NraTask {
@@ -628,6 +642,13 @@ int nra_launch_trace_fill(int R, int has_n, hipStream_t st, int n_tasks, const N
 int nra_launch_trace_back(hipStream_t st, int n_tasks, const NraTraceTask* tasks, const NraDevRead* reads,
                           const NraDevRegion* regions, const uint8_t* trace, const int32_t* fill_out,
                           uint8_t* ops, int32_t* out);
+int nra_launch_trace_fill_mt(int R, int has_n, int wide, hipStream_t st, int n_blocks, const NraTraceBlock* blocks,
+                             int32_t* ticket, const NraTraceTask* tasks, const NraDevRead* reads,
+                             const NraDevRegion* regions, const uint8_t* pool, const uint32_t* q2bit,
+                             const uint32_t* qnmask, NraScoreParams sp, uint8_t* trace, int32_t* blk_best,
+                             uint64_t* strips, uint32_t epoch, int32_t* error);
+int nra_launch_trace_best(hipStream_t st, int n_tasks, const NraTraceTask* tasks, const NraDevRead* reads,
+                          int block_rows, int wide, const int32_t* blk_best, NraScoreParams sp, int32_t* out);
 
 // 1D selectors (one wave per read).  append_mode: 0 none, 1 ambiguous ties only, 2 every tie
 int nra_launch_select_best_1d(hipStream_t st, int n_reads, const int32_t* kmin, const int32_t* kmax,

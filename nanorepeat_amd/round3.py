@@ -82,9 +82,10 @@ def _check_data_type(data_type):
 
 
 def round3_estimation_regions(data_type, fast_mode, repeat_regions, num_cpu=1, device=0,
-                              scoring=None, scorer=None):
+                              scoring=None, scorer=None, keep_candidates=False):
     """Round 3 for a list of regions in one batch.  `scorer` is the C-ABI call
-    (`_capi.round3_1d`); tests may inject a twin with the same signature."""
+    (`_capi.round3_1d`); tests may inject a twin with the same signature.  keep_candidates: the call also
+    returns every candidate's score and each read keeps its own (alignments.keep_candidates)."""
     _check_data_type(data_type)
     scorer = scorer or _capi.round3_1d
     regions, reads, kmin, kmax, rr, owners = [], [], [], [], [], []
@@ -112,7 +113,14 @@ def round3_estimation_regions(data_type, fast_mode, repeat_regions, num_cpu=1, d
     if not reads:
         return None
     out = scorer(regions, reads, np.array(kmin, np.int32), np.array(kmax, np.int32),
-                 read_region=np.array(rr, np.int32), sc=scoring, device=device, per_candidate=False)
+                 read_region=np.array(rr, np.int32), sc=scoring, device=device, per_candidate=keep_candidates)
+    if keep_candidates:
+        from . import alignments
+        at = 0
+        for read, lo, hi in zip(owners, kmin, kmax):
+            n = max(0, hi - lo + 1)
+            alignments.keep_candidates(read, lo, out["cand_score"][at:at + n])
+            at += n
     for i, read in enumerate(owners):
         st = int(out["status"][i])
         read.round3_status = st
