@@ -14,10 +14,23 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libnanorepeat_amd.so")
 OBJ = os.path.join(HERE, "csrc", "build")
 
-SOURCES = ["nra_kernels.hip", "nra_sweep.hip", "nra_joint.hip", "nra_trace.hip", "nra_screen.hip", "nra_structure.hip",
-           "nra_motif.hip", "nra_extend.hip", "nra_mixture.hip", "nra_consensus.hip", "nra_split.hip", "nra_segment.hip", "nra_host.cpp", "nra_screen_host.cpp", "nra_structure_host.cpp",
-           "nra_motif_host.cpp", "nra_extend_host.cpp", "nra_mixture_host.cpp", "nra_consensus_host.cpp", "nra_split_host.cpp", "nra_segment_host.cpp",
-           "nra_internal.h", "nra_device.h", "nra_pk16.h", "nra_cons_dp.h", "nra_cons_host.h"]
+# the kernel files and the parts (-DNRA_PART) each is compiled in
+KERNELS = (("nra_kernels.hip", (1, 2, 3, 4)),
+           ("nra_sweep.hip", (5, 6, 11, 12, 13, 14, 15, 16, 18, 19, 25, 26)),
+           ("nra_joint.hip", (7, 8, 10, 17, 20, 21, 22, 23)),
+           ("nra_trace.hip", (9,)),
+           ("nra_screen.hip", (27,)),
+           ("nra_structure.hip", (28,)),
+           ("nra_motif.hip", (29,)),
+           ("nra_extend.hip", (30,)),
+           ("nra_mixture.hip", (31,)),
+           ("nra_consensus.hip", (32,)),
+           ("nra_split.hip", (33,)),
+           ("nra_segment.hip", (34,)))
+HOSTS = ("nra_host.cpp", "nra_screen_host.cpp", "nra_structure_host.cpp", "nra_motif_host.cpp", "nra_extend_host.cpp",
+         "nra_mixture_host.cpp", "nra_consensus_host.cpp", "nra_split_host.cpp", "nra_segment_host.cpp")
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))
+SOURCES = [k for k, _ in KERNELS] + list(HOSTS) + HEADERS
 ARCH = "gfx950"
 
 
@@ -46,53 +59,18 @@ def build_library(force=False, jobs=None, verbose=False):
               "-Wno-unused-command-line-argument"]
     cmds = []
     objs = []
-    for part in (1, 2, 3, 4):
-        o = os.path.join(OBJ, f"nra_kernels_p{part}.o")
+    for kernel, parts in KERNELS:
+        for part in parts:
+            o = os.path.join(OBJ, f"{kernel[:-len('.hip')]}_p{part}.o")
+            objs.append(o)
+            cmds.append(common + [f"-DNRA_PART={part}", "-c", os.path.join(CSRC, kernel), "-o", o])
+    for host in HOSTS:
+        o = os.path.join(OBJ, host[:-len(".cpp")] + ".o")
         objs.append(o)
-        cmds.append(common + [f"-DNRA_PART={part}", "-c", os.path.join(CSRC, "nra_kernels.hip"), "-o", o])
-    for part in (5, 6, 11, 12, 13, 14, 15, 16, 18, 19, 25, 26):
-        o = os.path.join(OBJ, f"nra_sweep_p{part}.o")
-        objs.append(o)
-        cmds.append(common + [f"-DNRA_PART={part}", "-c", os.path.join(CSRC, "nra_sweep.hip"), "-o", o])
-    for part in (7, 8, 10, 17, 20, 21, 22, 23):
-        o = os.path.join(OBJ, f"nra_joint_p{part}.o")
-        objs.append(o)
-        cmds.append(common + [f"-DNRA_PART={part}", "-c", os.path.join(CSRC, "nra_joint.hip"), "-o", o])
-    o = os.path.join(OBJ, "nra_trace_p9.o")
-    objs.append(o)
-    cmds.append(common + ["-DNRA_PART=9", "-c", os.path.join(CSRC, "nra_trace.hip"), "-o", o])
-    o = os.path.join(OBJ, "nra_screen_p27.o")
-    objs.append(o)
-    cmds.append(common + ["-DNRA_PART=27", "-c", os.path.join(CSRC, "nra_screen.hip"), "-o", o])
-    o = os.path.join(OBJ, "nra_structure_p28.o")
-    objs.append(o)
-    cmds.append(common + ["-DNRA_PART=28", "-c", os.path.join(CSRC, "nra_structure.hip"), "-o", o])
-    o = os.path.join(OBJ, "nra_motif_p29.o")
-    objs.append(o)
-    cmds.append(common + ["-DNRA_PART=29", "-c", os.path.join(CSRC, "nra_motif.hip"), "-o", o])
-    o = os.path.join(OBJ, "nra_extend_p30.o")
-    objs.append(o)
-    cmds.append(common + ["-DNRA_PART=30", "-c", os.path.join(CSRC, "nra_extend.hip"), "-o", o])
-    o = os.path.join(OBJ, "nra_mixture_p31.o")
-    objs.append(o)
-    cmds.append(common + ["-DNRA_PART=31", "-c", os.path.join(CSRC, "nra_mixture.hip"), "-o", o])
-    o = os.path.join(OBJ, "nra_consensus_p32.o")
-    objs.append(o)
-    cmds.append(common + ["-DNRA_PART=32", "-c", os.path.join(CSRC, "nra_consensus.hip"), "-o", o])
-    o = os.path.join(OBJ, "nra_split_p33.o")
-    objs.append(o)
-    cmds.append(common + ["-DNRA_PART=33", "-c", os.path.join(CSRC, "nra_split.hip"), "-o", o])
-    o = os.path.join(OBJ, "nra_segment_p34.o")
-    objs.append(o)
-    cmds.append(common + ["-DNRA_PART=34", "-c", os.path.join(CSRC, "nra_segment.hip"), "-o", o])
-    for host in ("nra_host", "nra_screen_host", "nra_structure_host", "nra_motif_host", "nra_extend_host",
-                 "nra_mixture_host", "nra_consensus_host", "nra_split_host", "nra_segment_host"):
-        o = os.path.join(OBJ, host + ".o")
-        objs.append(o)
-        cmds.append(common + ["-pthread", "-c", os.path.join(CSRC, host + ".cpp"), "-o", o])
+        cmds.append(common + ["-pthread", "-c", os.path.join(CSRC, host), "-o", o])
 
     # an object is rebuilt when its source, a header next to it or the public header is newer
-    headers = [os.path.join(CSRC, h) for h in SOURCES if h.endswith(".h")] + [os.path.join(INCLUDE, "nanorepeat_amd.h")]
+    headers = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(INCLUDE, "nanorepeat_amd.h")]
 
     def fresh(cmd):
         obj, src = cmd[-1], cmd[-3]

@@ -1,35 +1,12 @@
 // nra_cons_host.h -- host-side pieces shared by the two callers of the banded tract alignment (nra_consensus_host.cpp,
-// nra_split_host.cpp): the pointer budget of a launch, a grow-only device buffer, and what a band class proves.
+// nra_split_host.cpp): the pointer budget of a launch and what a band class proves.
 #ifndef NRA_CONS_HOST_H
 #define NRA_CONS_HOST_H
-#include "nra_internal.h"
-
-#include <algorithm>
-#include <cstdlib>
+#include "nra_host_util.h"
 
 namespace nra_cons {
 
 const int64_t kPtrBudget = int64_t(1) << 30;    // traceback pointer bytes per launch (one tract beyond it goes alone)
-
-inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-
-// a grow-only device buffer
-template <class T> struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t ensure(size_t n)
-    {
-        n = std::max<size_t>(n, 1);
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T));
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-};
 
 // what band class c_idx (c = 1 << c_idx) proves for a tract of n bases on a backbone of t: -1 if it holds no band
 inline int proven(int c_idx, int n, int t)
@@ -39,11 +16,7 @@ inline int proven(int c_idx, int n, int t)
 }
 
 // the traceback pointer bytes a launch may use: kPtrBudget, or NRA_TEST_CONS_PTR_BYTES (tests force small chunks)
-inline int64_t ptr_budget()
-{
-    if (const char* e = getenv("NRA_TEST_CONS_PTR_BYTES")) return std::max<int64_t>(1, atoll(e));
-    return kPtrBudget;
-}
+inline int64_t ptr_budget() { return nra_host::test_bytes("NRA_TEST_CONS_PTR_BYTES", kPtrBudget); }
 
 // the band class a tract of n bases is first aligned in on a backbone of t
 inline int start_class(int n, int t, int max_dist)

@@ -3,8 +3,6 @@
 // chunked under a budget of traceback pointer memory, repeated in the next class for the tracts whose band could not
 // decide), one launch of k_cons_build, and the new backbones back (nra_consensus.hip).  The tracts are packed and
 // uploaded once; groups that are done drop out of the next round.
-#include "nanorepeat_amd.h"
-#include "nra_internal.h"
 #include "nra_cons_host.h"
 
 #include <algorithm>
@@ -14,19 +12,10 @@
 #include <string>
 #include <vector>
 
-namespace {
-
-int fail(int code, const std::string& msg) { return nra_set_error(code, msg.c_str()); }
-
-#define CONS_HIP_TRY(expr)                                                                       \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return fail(e_ == hipErrorOutOfMemory ? NRA_E_NOMEM : NRA_E_DEVICE,                  \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                      \
-    } while (0)
-
+using namespace nra_host;
 using namespace nra_cons;
+
+namespace {
 
 struct Tract {
     uint64_t seq;              // byte offset of its codes on the device
@@ -55,8 +44,8 @@ int run(int32_t n_groups, std::vector<Group>& groups, std::vector<Tract>& tracts
     DevBuf<NraConsItem> d_items;
     DevBuf<uint4> d_ptr;
     DevBuf<int32_t> d_tabs, d_voters, d_status, d_sup, d_res;
-    CONS_HIP_TRY(d_codes.ensure(codes.size()));
-    CONS_HIP_TRY(hipMemcpy(d_codes.p, codes.data(), codes.size(), hipMemcpyHostToDevice));
+    NRA_HIP_TRY(d_codes.ensure(codes.size()));
+    NRA_HIP_TRY(hipMemcpy(d_codes.p, codes.data(), codes.size(), hipMemcpyHostToDevice));
 
     std::vector<int32_t> act;
     std::vector<NraConsGroup> dg;
@@ -88,17 +77,17 @@ int run(int32_t n_groups, std::vector<Group>& groups, std::vector<Tract>& tracts
             const Group& g = groups[act[a]];
             if (!g.bb.empty()) std::memcpy(bbs.data() + dg[a].bb, g.bb.data(), g.bb.size());
         }
-        CONS_HIP_TRY(d_bb.ensure(bbs.size()));
-        CONS_HIP_TRY(d_nb.ensure((size_t)nb_bytes));
-        CONS_HIP_TRY(d_sup.ensure((size_t)nb_bytes));
-        CONS_HIP_TRY(d_groups.ensure(na));
-        CONS_HIP_TRY(d_tabs.ensure((size_t)tab_ints));
-        CONS_HIP_TRY(d_voters.ensure(na));
-        CONS_HIP_TRY(d_res.ensure(3 * na));
-        CONS_HIP_TRY(hipMemcpy(d_bb.p, bbs.data(), bbs.size(), hipMemcpyHostToDevice));
-        CONS_HIP_TRY(hipMemcpy(d_groups.p, dg.data(), na * sizeof(NraConsGroup), hipMemcpyHostToDevice));
-        CONS_HIP_TRY(hipMemset(d_tabs.p, 0, (size_t)tab_ints * sizeof(int32_t)));
-        CONS_HIP_TRY(hipMemset(d_voters.p, 0, na * sizeof(int32_t)));
+        NRA_HIP_TRY(d_bb.ensure(bbs.size()));
+        NRA_HIP_TRY(d_nb.ensure((size_t)nb_bytes));
+        NRA_HIP_TRY(d_sup.ensure((size_t)nb_bytes));
+        NRA_HIP_TRY(d_groups.ensure(na));
+        NRA_HIP_TRY(d_tabs.ensure((size_t)tab_ints));
+        NRA_HIP_TRY(d_voters.ensure(na));
+        NRA_HIP_TRY(d_res.ensure(3 * na));
+        NRA_HIP_TRY(hipMemcpy(d_bb.p, bbs.data(), bbs.size(), hipMemcpyHostToDevice));
+        NRA_HIP_TRY(hipMemcpy(d_groups.p, dg.data(), na * sizeof(NraConsGroup), hipMemcpyHostToDevice));
+        NRA_HIP_TRY(hipMemset(d_tabs.p, 0, (size_t)tab_ints * sizeof(int32_t)));
+        NRA_HIP_TRY(hipMemset(d_voters.p, 0, na * sizeof(int32_t)));
 
         // the alignments of the round: every tract of every active group, in the class that decided it last time
         work.clear();
@@ -141,16 +130,16 @@ int run(int32_t n_groups, std::vector<Group>& groups, std::vector<Tract>& tracts
                 const size_t ni = items.size();
                 stats[11] += 1;
                 stats[14] = std::max<int64_t>(stats[14], pieces * 16);
-                CONS_HIP_TRY(d_items.ensure(ni));
-                CONS_HIP_TRY(d_status.ensure(ni));
-                CONS_HIP_TRY(d_ptr.ensure((size_t)pieces));
-                CONS_HIP_TRY(hipMemcpy(d_items.p, items.data(), ni * sizeof(NraConsItem), hipMemcpyHostToDevice));
+                NRA_HIP_TRY(d_items.ensure(ni));
+                NRA_HIP_TRY(d_status.ensure(ni));
+                NRA_HIP_TRY(d_ptr.ensure((size_t)pieces));
+                NRA_HIP_TRY(hipMemcpy(d_items.p, items.data(), ni * sizeof(NraConsItem), hipMemcpyHostToDevice));
                 const int e = nra_launch_cons_align(nullptr, c, (int)ni, d_items.p, d_groups.p, d_codes.p, d_bb.p, d_ptr.p,
                                                     d_tabs.p, d_voters.p, d_status.p, max_dist);
                 if (e != 0) return fail(NRA_E_DEVICE, std::string("k_cons_align: ") + hipGetErrorString((hipError_t)e));
-                CONS_HIP_TRY(hipStreamSynchronize(nullptr));
+                NRA_HIP_TRY(hipStreamSynchronize(nullptr));
                 status.resize(ni);
-                CONS_HIP_TRY(hipMemcpy(status.data(), d_status.p, ni * sizeof(int32_t), hipMemcpyDeviceToHost));
+                NRA_HIP_TRY(hipMemcpy(status.data(), d_status.p, ni * sizeof(int32_t), hipMemcpyDeviceToHost));
                 for (size_t q = 0; q < ni; ++q) {
                     const Work& wk = work[i + q];
                     if (status[q] == NRA_CONS_WIDEN) {
@@ -169,13 +158,13 @@ int run(int32_t n_groups, std::vector<Group>& groups, std::vector<Tract>& tracts
         const int e = nra_launch_cons_build(nullptr, (int)na, d_groups.p, d_bb.p, d_tabs.p, d_voters.p, d_nb.p, d_sup.p,
                                             d_res.p);
         if (e != 0) return fail(NRA_E_DEVICE, std::string("k_cons_build: ") + hipGetErrorString((hipError_t)e));
-        CONS_HIP_TRY(hipStreamSynchronize(nullptr));
+        NRA_HIP_TRY(hipStreamSynchronize(nullptr));
         res.resize(3 * na);
         nbs.resize((size_t)nb_bytes);
         sups.resize((size_t)nb_bytes);
-        CONS_HIP_TRY(hipMemcpy(res.data(), d_res.p, res.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        CONS_HIP_TRY(hipMemcpy(nbs.data(), d_nb.p, nbs.size(), hipMemcpyDeviceToHost));
-        CONS_HIP_TRY(hipMemcpy(sups.data(), d_sup.p, sups.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        NRA_HIP_TRY(hipMemcpy(res.data(), d_res.p, res.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        NRA_HIP_TRY(hipMemcpy(nbs.data(), d_nb.p, nbs.size(), hipMemcpyDeviceToHost));
+        NRA_HIP_TRY(hipMemcpy(sups.data(), d_sup.p, sups.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
         for (size_t a = 0; a < na; ++a) {
             Group& g = groups[act[a]];
             const int32_t len = res[3 * a], changed = res[3 * a + 1], mv = res[3 * a + 2];
@@ -222,29 +211,17 @@ int nra_tract_consensus(int device, int32_t n_groups, const int64_t* group_off, 
         if (group_off[g + 1] < group_off[g]) return fail(NRA_E_ARG, "group offsets must not decrease");
     if (n_tracts > 0) {
         if (!seq_off) return fail(NRA_E_ARG, "seq_off is NULL");
-        if (seq_off[0] < 0) return fail(NRA_E_ARG, "negative tract offset");
-        for (int32_t r = 0; r < n_tracts; ++r) {
-            const int64_t len = seq_off[r + 1] - seq_off[r];
-            if (len < 0) return fail(NRA_E_ARG, "tract offsets must not decrease");
-            if (len > NRA_CONS_MAX_N) return fail(NRA_E_RANGE, "tract " + std::to_string(r) + " is longer than 200000 bases");
-        }
+        if (int rc = check_tract_offsets(n_tracts, seq_off, NRA_CONS_MAX_N, "tract")) return rc;
         if (seq_off[n_tracts] > seq_off[0] && !seqs) return fail(NRA_E_ARG, "seqs is NULL");
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(NRA_E_DEVICE, "no HIP device: nanorepeat_amd has no CPU path");
-    if (device < 0 || device >= ndev) return fail(NRA_E_ARG, "device index out of range");
+    if (int rc = use_device(device, n_groups > 0)) return rc;
     int64_t st[NRA_CONS_N_STATS] = {0};
     cons_off[0] = 0;
     if (n_groups == 0) {
         if (stats) std::memcpy(stats, st, sizeof(st));
         return NRA_OK;
     }
-    CONS_HIP_TRY(hipSetDevice(device));
     try {
-        uint8_t lut[256];
-        for (int c = 0; c < 256; ++c) lut[c] = NRA_CONS_CODE_OTHER;
-        lut['A'] = lut['a'] = 0; lut['C'] = lut['c'] = 1; lut['G'] = lut['g'] = 2; lut['T'] = lut['t'] = 3;
         std::vector<Tract> tracts((size_t)n_tracts);
         int64_t code_bytes = 0;
         for (int32_t r = 0; r < n_tracts; ++r) {
@@ -254,11 +231,7 @@ int nra_tract_consensus(int device, int32_t n_groups, const int64_t* group_off, 
             code_bytes += round_up(tracts[r].n, 16);
         }
         std::vector<uint8_t> codes((size_t)code_bytes + 16, (uint8_t)NRA_CONS_CODE_OTHER);
-        for (int32_t r = 0; r < n_tracts; ++r) {
-            const unsigned char* s = reinterpret_cast<const unsigned char*>(seqs + seq_off[r]);
-            uint8_t* dst = codes.data() + tracts[r].seq;
-            for (int32_t i = 0; i < tracts[r].n; ++i) dst[i] = lut[s[i]];
-        }
+        for (int32_t r = 0; r < n_tracts; ++r) encode(codes.data() + tracts[r].seq, seqs + seq_off[r], tracts[r].n);
         std::vector<Group> groups((size_t)n_groups);
         bool any = false;
         for (int32_t g = 0; g < n_groups; ++g) {

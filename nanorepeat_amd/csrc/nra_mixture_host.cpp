@@ -1,8 +1,7 @@
 // nra_mixture_host.cpp -- C ABI of the mixture fits (nra_mixture_fit): argument checks, the samples packed at even
 // offsets, one upload, one launch of k_mixture (nra_mixture.hip) per (axes, register class), one download of the
 // per-fit results.  A fit is one workgroup and shares nothing with another, so a call is never chunked.
-#include "nanorepeat_amd.h"
-#include "nra_internal.h"
+#include "nra_host_util.h"
 
 #include <algorithm>
 #include <cmath>
@@ -11,23 +10,9 @@
 #include <string>
 #include <vector>
 
+using namespace nra_host;
+
 namespace {
-
-int fail(int code, const std::string& msg) { return nra_set_error(code, msg.c_str()); }
-
-#define MIX_HIP_TRY(expr)                                                                        \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return fail(e_ == hipErrorOutOfMemory ? NRA_E_NOMEM : NRA_E_DEVICE,                  \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                      \
-    } while (0)
-
-template <class T> struct DevBuf {
-    T* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T)); }
-};
 
 // the register class of a problem of n points: 256 * kreg holds it; 0 streams
 int kreg_of(int64_t n, int32_t flags)
@@ -77,12 +62,8 @@ int nra_mixture_fit(int device, int64_t n_samples, const double* samples, int32_
             off += fit_n[f];
         }
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(NRA_E_DEVICE, "no HIP device: nanorepeat_amd has no CPU path");
-    if (device < 0 || device >= ndev) return fail(NRA_E_ARG, "device index out of range");
+    if (int rc = use_device(device, n_fits > 0)) return rc;
     if (n_fits == 0) return NRA_OK;
-    MIX_HIP_TRY(hipSetDevice(device));
     try {
         const size_t np = (size_t)n_problems, nf = (size_t)n_fits;
         // every problem at an even offset: a row of two doubles is one aligned 16-byte load
@@ -123,33 +104,33 @@ int nra_mixture_fit(int device, int64_t n_samples, const double* samples, int32_
         DevBuf<NraMixProblem> d_pr;
         DevBuf<NraMixFit> d_ft;
         DevBuf<int32_t> d_ids, d_st, d_it;
-        MIX_HIP_TRY(d_x.alloc(packed.size()));
-        MIX_HIP_TRY(d_pr.alloc(np));
-        MIX_HIP_TRY(d_ft.alloc(nf));
-        MIX_HIP_TRY(d_ids.alloc(nf));
-        MIX_HIP_TRY(d_st.alloc((size_t)n_comp));
-        MIX_HIP_TRY(d_lb.alloc(nf));
-        MIX_HIP_TRY(d_w.alloc((size_t)n_comp));
-        MIX_HIP_TRY(d_mu.alloc(2 * (size_t)n_comp));
-        MIX_HIP_TRY(d_var.alloc(2 * (size_t)n_comp));
-        MIX_HIP_TRY(d_it.alloc(2 * nf));
-        MIX_HIP_TRY(hipMemcpy(d_x.p, packed.data(), packed.size() * sizeof(double), hipMemcpyHostToDevice));
-        MIX_HIP_TRY(hipMemcpy(d_pr.p, pr.data(), np * sizeof(NraMixProblem), hipMemcpyHostToDevice));
-        MIX_HIP_TRY(hipMemcpy(d_ft.p, ft.data(), nf * sizeof(NraMixFit), hipMemcpyHostToDevice));
-        MIX_HIP_TRY(hipMemcpy(d_ids.p, ids.data(), nf * sizeof(int32_t), hipMemcpyHostToDevice));
-        MIX_HIP_TRY(hipMemcpy(d_st.p, starts, (size_t)n_comp * sizeof(int32_t), hipMemcpyHostToDevice));
+        NRA_HIP_TRY(d_x.alloc(packed.size()));
+        NRA_HIP_TRY(d_pr.alloc(np));
+        NRA_HIP_TRY(d_ft.alloc(nf));
+        NRA_HIP_TRY(d_ids.alloc(nf));
+        NRA_HIP_TRY(d_st.alloc((size_t)n_comp));
+        NRA_HIP_TRY(d_lb.alloc(nf));
+        NRA_HIP_TRY(d_w.alloc((size_t)n_comp));
+        NRA_HIP_TRY(d_mu.alloc(2 * (size_t)n_comp));
+        NRA_HIP_TRY(d_var.alloc(2 * (size_t)n_comp));
+        NRA_HIP_TRY(d_it.alloc(2 * nf));
+        NRA_HIP_TRY(hipMemcpy(d_x.p, packed.data(), packed.size() * sizeof(double), hipMemcpyHostToDevice));
+        NRA_HIP_TRY(hipMemcpy(d_pr.p, pr.data(), np * sizeof(NraMixProblem), hipMemcpyHostToDevice));
+        NRA_HIP_TRY(hipMemcpy(d_ft.p, ft.data(), nf * sizeof(NraMixFit), hipMemcpyHostToDevice));
+        NRA_HIP_TRY(hipMemcpy(d_ids.p, ids.data(), nf * sizeof(int32_t), hipMemcpyHostToDevice));
+        NRA_HIP_TRY(hipMemcpy(d_st.p, starts, (size_t)n_comp * sizeof(int32_t), hipMemcpyHostToDevice));
         for (const Launch& l : launches) {
             const int e = nra_launch_mixture(nullptr, l.d, l.kreg, (int)l.count, d_ids.p + l.begin, d_ft.p, d_pr.p, d_x.p,
                                              d_st.p, d_lb.p, d_w.p, d_mu.p, d_var.p, d_it.p);
             if (e != 0) return fail(NRA_E_DEVICE, std::string("k_mixture: ") + hipGetErrorString((hipError_t)e));
         }
-        MIX_HIP_TRY(hipStreamSynchronize(nullptr));
+        NRA_HIP_TRY(hipStreamSynchronize(nullptr));
         std::vector<int32_t> it(2 * nf);
-        MIX_HIP_TRY(hipMemcpy(lb, d_lb.p, nf * sizeof(double), hipMemcpyDeviceToHost));
-        MIX_HIP_TRY(hipMemcpy(w, d_w.p, (size_t)n_comp * sizeof(double), hipMemcpyDeviceToHost));
-        MIX_HIP_TRY(hipMemcpy(mu, d_mu.p, 2 * (size_t)n_comp * sizeof(double), hipMemcpyDeviceToHost));
-        MIX_HIP_TRY(hipMemcpy(var, d_var.p, 2 * (size_t)n_comp * sizeof(double), hipMemcpyDeviceToHost));
-        MIX_HIP_TRY(hipMemcpy(it.data(), d_it.p, it.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        NRA_HIP_TRY(hipMemcpy(lb, d_lb.p, nf * sizeof(double), hipMemcpyDeviceToHost));
+        NRA_HIP_TRY(hipMemcpy(w, d_w.p, (size_t)n_comp * sizeof(double), hipMemcpyDeviceToHost));
+        NRA_HIP_TRY(hipMemcpy(mu, d_mu.p, 2 * (size_t)n_comp * sizeof(double), hipMemcpyDeviceToHost));
+        NRA_HIP_TRY(hipMemcpy(var, d_var.p, 2 * (size_t)n_comp * sizeof(double), hipMemcpyDeviceToHost));
+        NRA_HIP_TRY(hipMemcpy(it.data(), d_it.p, it.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
         for (size_t f = 0; f < nf; ++f) {
             n_iter[f] = it[2 * f];
             converged[f] = it[2 * f + 1];

@@ -1,8 +1,7 @@
 // nra_motif_host.cpp -- C ABI of the tandem motif discovery (nra_tract_motifs): argument checks, the class tables,
 // the order of the tracts (length, descending), the chunks that bound the device buffers, and the launches of
 // k_tract_motifs (nra_motif.hip).
-#include "nanorepeat_amd.h"
-#include "nra_internal.h"
+#include "nra_host_util.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -12,33 +11,12 @@
 #include <string>
 #include <vector>
 
+using namespace nra_host;
+
 namespace {
-
-int fail(int code, const std::string& msg) { return nra_set_error(code, msg.c_str()); }
-
-#define MOTIF_HIP_TRY(expr)                                                                      \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return fail(e_ == hipErrorOutOfMemory ? NRA_E_NOMEM : NRA_E_DEVICE,                  \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                      \
-    } while (0)
 
 const int64_t kCodeBudget = int64_t(1) << 28;   // tract bytes per chunk (one tract beyond it goes alone)
 const int kGroupsPerCU = 5;                     // workgroups of 4 waves resident per CU (26 KiB of LDS each)
-
-int base_code(unsigned char ch)
-{
-    switch (ch) {
-    case 'A': case 'a': return 0;
-    case 'C': case 'c': return 1;
-    case 'G': case 'g': return 2;
-    case 'T': case 't': return 3;
-    default: return NRA_MOTIF_CODE_OTHER;
-    }
-}
-
-int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 int code_offset(int p) { return ((1 << (2 * p)) - 4) / 3; }
 
@@ -65,12 +43,6 @@ void class_tables(std::vector<int16_t>& dense_of, std::vector<int8_t>& p_of, std
     }
 }
 
-template <class T> struct DevBuf {
-    T* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T)); }
-};
-
 struct Outputs {
     int32_t max_p, top_n;
     int32_t *n_tandem, *top_code, *top_count;
@@ -92,35 +64,28 @@ int run_chunk(size_t first, size_t last, const std::vector<int32_t>& order, cons
         tr[l].pad = 0;
         code_bytes += round_up(tr[l].n, NRA_MOTIF_BLOCK);
     }
-    uint8_t lut[256];
-    for (int c = 0; c < 256; ++c) lut[c] = (uint8_t)base_code((unsigned char)c);
     std::vector<uint8_t> codes((size_t)code_bytes + NRA_MOTIF_PAD, (uint8_t)NRA_MOTIF_CODE_OTHER);
-    for (size_t l = 0; l < n; ++l) {
-        const int32_t t = order[first + l];
-        const unsigned char* s = reinterpret_cast<const unsigned char*>(seqs + seq_off[t]);
-        uint8_t* dst = codes.data() + tr[l].off;
-        for (int32_t i = 0; i < tr[l].n; ++i) dst[i] = lut[s[i]];
-    }
+    for (size_t l = 0; l < n; ++l) encode(codes.data() + tr[l].off, seqs + seq_off[order[first + l]], tr[l].n);
     DevBuf<NraMotifTract> d_tr;
     DevBuf<uint8_t> d_codes;
     DevBuf<int32_t> d_tandem;
     DevBuf<uint32_t> d_key;
-    MOTIF_HIP_TRY(d_tr.alloc(n));
-    MOTIF_HIP_TRY(d_codes.alloc(codes.size()));
-    MOTIF_HIP_TRY(d_tandem.alloc(n * NRA_MOTIF_MAX_P));
-    MOTIF_HIP_TRY(d_key.alloc(n * NRA_MOTIF_MAX_TOP));
-    MOTIF_HIP_TRY(hipMemcpy(d_tr.p, tr.data(), n * sizeof(NraMotifTract), hipMemcpyHostToDevice));
-    MOTIF_HIP_TRY(hipMemcpy(d_codes.p, codes.data(), codes.size(), hipMemcpyHostToDevice));
+    NRA_HIP_TRY(d_tr.alloc(n));
+    NRA_HIP_TRY(d_codes.alloc(codes.size()));
+    NRA_HIP_TRY(d_tandem.alloc(n * NRA_MOTIF_MAX_P));
+    NRA_HIP_TRY(d_key.alloc(n * NRA_MOTIF_MAX_TOP));
+    NRA_HIP_TRY(hipMemcpy(d_tr.p, tr.data(), n * sizeof(NraMotifTract), hipMemcpyHostToDevice));
+    NRA_HIP_TRY(hipMemcpy(d_codes.p, codes.data(), codes.size(), hipMemcpyHostToDevice));
     const int64_t groups = ((int64_t)n + 3) / 4;
     const int grid = (int)std::min<int64_t>(groups, (int64_t)n_cu * kGroupsPerCU);
     const int e = nra_launch_tract_motifs(nullptr, grid, (int)n, d_tr.p, d_codes.p, dev_dense, o.max_p, o.top_n,
                                           d_tandem.p, d_key.p);
     if (e != 0) return fail(NRA_E_DEVICE, std::string("k_tract_motifs: ") + hipGetErrorString((hipError_t)e));
-    MOTIF_HIP_TRY(hipStreamSynchronize(nullptr));
+    NRA_HIP_TRY(hipStreamSynchronize(nullptr));
     std::vector<int32_t> tandem(n * NRA_MOTIF_MAX_P);
     std::vector<uint32_t> key(n * NRA_MOTIF_MAX_TOP);
-    MOTIF_HIP_TRY(hipMemcpy(tandem.data(), d_tandem.p, tandem.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    MOTIF_HIP_TRY(hipMemcpy(key.data(), d_key.p, key.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    NRA_HIP_TRY(hipMemcpy(tandem.data(), d_tandem.p, tandem.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    NRA_HIP_TRY(hipMemcpy(key.data(), d_key.p, key.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (size_t l = 0; l < n; ++l) {
         const int64_t t = order[first + l];
         for (int p = 0; p < o.max_p; ++p) o.n_tandem[t * o.max_p + p] = tandem[l * NRA_MOTIF_MAX_P + (size_t)p];
@@ -150,31 +115,21 @@ int nra_tract_motifs(int device, int32_t n_tracts, const char* seqs, const int64
     if (n_tracts < 0) return fail(NRA_E_ARG, "negative tract count");
     if (n_tracts > 0) {
         if (!seq_off || !n_tandem || !top_p || !top_code || !top_count) return fail(NRA_E_ARG, "NULL tract array");
-        if (seq_off[0] < 0) return fail(NRA_E_ARG, "negative tract offset");
-        for (int32_t t = 0; t < n_tracts; ++t) {
-            const int64_t len = seq_off[t + 1] - seq_off[t];
-            if (len < 0) return fail(NRA_E_ARG, "tract offsets must not decrease");
-            if (len > NRA_MOTIF_MAX_N)
-                return fail(NRA_E_RANGE, "tract " + std::to_string(t) + " is longer than 200000 bases");
-        }
+        if (int rc = check_tract_offsets(n_tracts, seq_off, NRA_MOTIF_MAX_N, "tract")) return rc;
         if (seq_off[n_tracts] > seq_off[0] && !seqs) return fail(NRA_E_ARG, "seqs is NULL");
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(NRA_E_DEVICE, "no HIP device: nanorepeat_amd has no CPU path");
-    if (device < 0 || device >= ndev) return fail(NRA_E_ARG, "device index out of range");
+    if (int rc = use_device(device, n_tracts > 0)) return rc;
     if (n_tracts == 0) return NRA_OK;
-    MOTIF_HIP_TRY(hipSetDevice(device));
     try {
         std::vector<int16_t> dense_of;
         std::vector<int8_t> p_of;
         std::vector<int32_t> code_of;
         class_tables(dense_of, p_of, code_of);
         DevBuf<int16_t> d_dense;
-        MOTIF_HIP_TRY(d_dense.alloc(dense_of.size()));
-        MOTIF_HIP_TRY(hipMemcpy(d_dense.p, dense_of.data(), dense_of.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+        NRA_HIP_TRY(d_dense.alloc(dense_of.size()));
+        NRA_HIP_TRY(hipMemcpy(d_dense.p, dense_of.data(), dense_of.size() * sizeof(int16_t), hipMemcpyHostToDevice));
         int n_cu = 0;
-        MOTIF_HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
+        NRA_HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
         n_cu = std::max(n_cu, 1);
 
         // length descending, then index: the four tracts of a workgroup step run about as long
@@ -182,8 +137,7 @@ int nra_tract_motifs(int device, int32_t n_tracts, const char* seqs, const int64
         std::iota(order.begin(), order.end(), 0);
         auto len_of = [&](int32_t t) { return seq_off[t + 1] - seq_off[t]; };
         std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return len_of(a) > len_of(b); });
-        int64_t budget = kCodeBudget;
-        if (const char* e = getenv("NRA_TEST_MOTIF_CHUNK_BYTES")) budget = std::max<int64_t>(1, atoll(e));
+        const int64_t budget = test_bytes("NRA_TEST_MOTIF_CHUNK_BYTES", kCodeBudget);
         const Outputs o{max_period, top_n, n_tandem, top_code, top_count, top_p, p_of.data(), code_of.data()};
         for (size_t i = 0; i < order.size();) {
             size_t j = i;

@@ -1,7 +1,6 @@
 // nra_screen_host.cpp -- C ABI of the anchor k-mer screen (nra_screen_*): the index build on the host, the chunked
 // launches of k_screen_hits (nra_screen.hip) and the per-(read, region) reduction with the pass rule.
-#include "nanorepeat_amd.h"
-#include "nra_internal.h"
+#include "nra_host_util.h"
 
 #include <algorithm>
 #include <chrono>
@@ -10,46 +9,12 @@
 #include <string>
 #include <vector>
 
+using namespace nra_host;
+
 namespace {
-
-int fail(int code, const std::string& msg) { return nra_set_error(code, msg.c_str()); }
-
-#define SCREEN_HIP_TRY(expr)                                                                     \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return fail(e_ == hipErrorOutOfMemory ? NRA_E_NOMEM : NRA_E_DEVICE,                  \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                      \
-    } while (0)
 
 const int64_t kSegmentBytes = int64_t(1) << 28;   // read bytes per launch (a longer read goes alone)
 const size_t kPad = 64;                           // bytes after a chunk's copy: the kernel's last 16-byte load stays inside
-
-int base_code(unsigned char ch)
-{
-    switch (ch) {
-    case 'A': case 'a': return 0;
-    case 'C': case 'c': return 1;
-    case 'G': case 'g': return 2;
-    case 'T': case 't': return 3;
-    default: return -1;
-    }
-}
-
-// device buffer that grows and is reused across calls
-template <class T> struct Grow {
-    T* p = nullptr;
-    size_t n = 0;
-    hipError_t reserve(size_t want)
-    {
-        if (want <= n) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; n = 0; }
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(want, 1) * sizeof(T));
-        if (e == hipSuccess) n = want;
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
 
 }  // namespace
 
@@ -65,14 +30,13 @@ struct nra_screen {
     uint32_t* postings = nullptr;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    Grow<uint8_t> seqs;
-    Grow<NraScreenTile> tiles;
-    Grow<NraScreenEntry> entries;
-    Grow<unsigned long long> count;
+    DevBuf<uint8_t> seqs;              // these four grow and are reused across calls
+    DevBuf<NraScreenTile> tiles;
+    DevBuf<NraScreenEntry> entries;
+    DevBuf<unsigned long long> count;
 
     ~nra_screen()
     {
-        seqs.release(); tiles.release(); entries.release(); count.release();
         if (table) (void)hipFree(table);
         if (postings) (void)hipFree(postings);
         if (ev0) (void)hipEventDestroy(ev0);
@@ -90,8 +54,8 @@ void anchor_kmers(const char* s, int64_t n, int k, std::vector<uint32_t>& keys, 
     uint32_t fwd = 0, rev = 0;
     int run = 0;
     for (int64_t j = 0; j < n; ++j) {
-        const int c = base_code((unsigned char)s[j]);
-        if (c < 0) { run = 0; continue; }
+        const int c = kBase.of[(unsigned char)s[j]];
+        if (c > 3) { run = 0; continue; }
         fwd = ((fwd << 2) | (uint32_t)c) & kmask;
         rev = (rev >> 2) | ((uint32_t)(3 - c) << (2 * (k - 1)));
         if (++run < k) continue;
@@ -160,10 +124,10 @@ int build_index(nra_screen* s, const char* anchors, const int64_t* anchor_off, i
     s->st.n_empty_regions = (int64_t)s->empty_regions.size();
     s->st.index_bytes = (int64_t)(n_slots * 8 + post.size() * 4);
 
-    SCREEN_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->table), n_slots * 8));
-    SCREEN_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->postings), std::max<size_t>(post.size(), 1) * 4));
-    SCREEN_HIP_TRY(hipMemcpy(s->table, table.data(), n_slots * 8, hipMemcpyHostToDevice));
-    if (!post.empty()) SCREEN_HIP_TRY(hipMemcpy(s->postings, post.data(), post.size() * 4, hipMemcpyHostToDevice));
+    NRA_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->table), n_slots * 8));
+    NRA_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->postings), std::max<size_t>(post.size(), 1) * 4));
+    NRA_HIP_TRY(hipMemcpy(s->table, table.data(), n_slots * 8, hipMemcpyHostToDevice));
+    if (!post.empty()) NRA_HIP_TRY(hipMemcpy(s->postings, post.data(), post.size() * 4, hipMemcpyHostToDevice));
     return NRA_OK;
 }
 
@@ -180,38 +144,38 @@ int screen_segment(nra_screen* s, int32_t r0, int32_t r1, const char* seqs, cons
             tiles.push_back(NraScreenTile{seq_off[r] - b0 + w, r, (int32_t)std::min<int64_t>(NRA_SCREEN_TILE, n_win - w)});
     }
     if (tiles.empty()) return NRA_OK;
-    SCREEN_HIP_TRY(s->seqs.reserve((size_t)bytes + kPad));
-    SCREEN_HIP_TRY(s->tiles.reserve(tiles.size()));
-    SCREEN_HIP_TRY(s->count.reserve(1));
-    SCREEN_HIP_TRY(s->entries.reserve(std::max<size_t>(tiles.size() * 16, size_t(1) << 16)));
-    SCREEN_HIP_TRY(hipMemcpyAsync(s->seqs.p, seqs + b0, (size_t)bytes, hipMemcpyHostToDevice, s->stream));
-    SCREEN_HIP_TRY(hipMemsetAsync(s->seqs.p + bytes, 0, kPad, s->stream));
-    SCREEN_HIP_TRY(hipMemcpyAsync(s->tiles.p, tiles.data(), tiles.size() * sizeof(NraScreenTile), hipMemcpyHostToDevice,
+    NRA_HIP_TRY(s->seqs.ensure((size_t)bytes + kPad));
+    NRA_HIP_TRY(s->tiles.ensure(tiles.size()));
+    NRA_HIP_TRY(s->count.ensure(1));
+    NRA_HIP_TRY(s->entries.ensure(std::max<size_t>(tiles.size() * 16, size_t(1) << 16)));
+    NRA_HIP_TRY(hipMemcpyAsync(s->seqs.p, seqs + b0, (size_t)bytes, hipMemcpyHostToDevice, s->stream));
+    NRA_HIP_TRY(hipMemsetAsync(s->seqs.p + bytes, 0, kPad, s->stream));
+    NRA_HIP_TRY(hipMemcpyAsync(s->tiles.p, tiles.data(), tiles.size() * sizeof(NraScreenTile), hipMemcpyHostToDevice,
                                   s->stream));
     for (;;) {
         unsigned long long wanted = 0;
-        SCREEN_HIP_TRY(hipMemsetAsync(s->count.p, 0, sizeof(unsigned long long), s->stream));
-        SCREEN_HIP_TRY(hipEventRecord(s->ev0, s->stream));
+        NRA_HIP_TRY(hipMemsetAsync(s->count.p, 0, sizeof(unsigned long long), s->stream));
+        NRA_HIP_TRY(hipEventRecord(s->ev0, s->stream));
         const int e = nra_launch_screen_hits(s->stream, (int64_t)tiles.size(), s->tiles.p, s->seqs.p, s->k, s->table,
-                                             s->log2_slots, s->postings, s->entries.p, s->entries.n, s->count.p);
+                                             s->log2_slots, s->postings, s->entries.p, s->entries.cap, s->count.p);
         if (e != 0) return fail(NRA_E_DEVICE, std::string("k_screen_hits: ") + hipGetErrorString((hipError_t)e));
-        SCREEN_HIP_TRY(hipEventRecord(s->ev1, s->stream));
-        SCREEN_HIP_TRY(hipMemcpyAsync(&wanted, s->count.p, sizeof(wanted), hipMemcpyDeviceToHost, s->stream));
-        SCREEN_HIP_TRY(hipStreamSynchronize(s->stream));
+        NRA_HIP_TRY(hipEventRecord(s->ev1, s->stream));
+        NRA_HIP_TRY(hipMemcpyAsync(&wanted, s->count.p, sizeof(wanted), hipMemcpyDeviceToHost, s->stream));
+        NRA_HIP_TRY(hipStreamSynchronize(s->stream));
         float ms = 0.f;
-        SCREEN_HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+        NRA_HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
         kernel_ms += ms;
-        if (wanted <= s->entries.n) {
+        if (wanted <= s->entries.cap) {
             const size_t at = out.size();
             out.resize(at + (size_t)wanted);
             if (wanted)
-                SCREEN_HIP_TRY(hipMemcpy(out.data() + at, s->entries.p, (size_t)wanted * sizeof(NraScreenEntry),
+                NRA_HIP_TRY(hipMemcpy(out.data() + at, s->entries.p, (size_t)wanted * sizeof(NraScreenEntry),
                                          hipMemcpyDeviceToHost));
             return NRA_OK;
         }
         // overflowing LDS maps made more entries than the list holds: grow it and run the segment again (how many
         // overflow depends on the order the lanes arrive in, hence the margin)
-        SCREEN_HIP_TRY(s->entries.reserve((size_t)wanted * 2));
+        NRA_HIP_TRY(s->entries.ensure((size_t)wanted * 2));
     }
 }
 
@@ -232,11 +196,7 @@ int nra_screen_create(int device, int32_t n_regions, const char* anchors, const 
     for (int64_t i = 0; i < 2 * (int64_t)n_regions; ++i)
         if (anchor_off[i + 1] < anchor_off[i]) return fail(NRA_E_ARG, "anchor offsets must not decrease");
     if (anchor_off[2 * (int64_t)n_regions] > 0 && !anchors) return fail(NRA_E_ARG, "anchors is NULL");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(NRA_E_DEVICE, "no HIP device: nanorepeat_amd has no CPU path");
-    if (device < 0 || device >= ndev) return fail(NRA_E_ARG, "device index out of range");
-    SCREEN_HIP_TRY(hipSetDevice(device));
+    if (int rc = use_device(device)) return rc;
     nra_screen* s = new (std::nothrow) nra_screen;
     if (!s) return fail(NRA_E_NOMEM, "screen handle");
     s->device = device;
@@ -279,7 +239,7 @@ int nra_screen_reads(nra_screen_t* s, int32_t n_reads, const char* seqs, const i
             if (seq_off[r + 1] < seq_off[r]) return fail(NRA_E_ARG, "read offsets must not decrease");
         if (seq_off[n_reads] > seq_off[0] && !seqs) return fail(NRA_E_ARG, "seqs is NULL");
     }
-    SCREEN_HIP_TRY(hipSetDevice(s->device));
+    NRA_HIP_TRY(hipSetDevice(s->device));
     try {
         std::vector<NraScreenEntry> entries;
         double kernel_ms = 0.0;

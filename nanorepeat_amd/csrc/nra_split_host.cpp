@@ -2,8 +2,6 @@
 // k_split_align (by band class, tracts sorted by length, chunked under the budget of traceback pointer memory, repeated
 // in the next class for the tracts whose band could not decide: the consensus host's scheme, one round), then one launch
 // of k_split_count and one of k_split_phase for all groups, and the results back (nra_split.hip).
-#include "nanorepeat_amd.h"
-#include "nra_internal.h"
 #include "nra_cons_host.h"
 
 #include <algorithm>
@@ -12,19 +10,10 @@
 #include <string>
 #include <vector>
 
-namespace {
-
+using namespace nra_host;
 using namespace nra_cons;
 
-int fail(int code, const std::string& msg) { return nra_set_error(code, msg.c_str()); }
-
-#define SPLIT_HIP_TRY(expr)                                                                      \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return fail(e_ == hipErrorOutOfMemory ? NRA_E_NOMEM : NRA_E_DEVICE,                  \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                      \
-    } while (0)
+namespace {
 
 struct Work {
     int32_t tract, group, cls;
@@ -52,13 +41,13 @@ int run(const Host& H, std::vector<int64_t>& rowtab, int32_t n_tracts, const int
     DevBuf<uint4> d_ptr;
     DevBuf<int64_t> d_rowtab;
     DevBuf<int32_t> d_status, d_nb, d_pos, d_key, d_labels, d_sites, d_res;
-    SPLIT_HIP_TRY(d_codes.ensure(H.codes.size()));
-    SPLIT_HIP_TRY(hipMemcpy(d_codes.p, H.codes.data(), H.codes.size(), hipMemcpyHostToDevice));
-    SPLIT_HIP_TRY(d_bb.ensure(H.bbs.size()));
-    SPLIT_HIP_TRY(hipMemcpy(d_bb.p, H.bbs.data(), H.bbs.size(), hipMemcpyHostToDevice));
-    SPLIT_HIP_TRY(d_groups.ensure(ng));
-    SPLIT_HIP_TRY(hipMemcpy(d_groups.p, dg.data(), ng * sizeof(NraSplitGroup), hipMemcpyHostToDevice));
-    SPLIT_HIP_TRY(d_rows.ensure((size_t)H.row_bytes));
+    NRA_HIP_TRY(d_codes.ensure(H.codes.size()));
+    NRA_HIP_TRY(hipMemcpy(d_codes.p, H.codes.data(), H.codes.size(), hipMemcpyHostToDevice));
+    NRA_HIP_TRY(d_bb.ensure(H.bbs.size()));
+    NRA_HIP_TRY(hipMemcpy(d_bb.p, H.bbs.data(), H.bbs.size(), hipMemcpyHostToDevice));
+    NRA_HIP_TRY(d_groups.ensure(ng));
+    NRA_HIP_TRY(hipMemcpy(d_groups.p, dg.data(), ng * sizeof(NraSplitGroup), hipMemcpyHostToDevice));
+    NRA_HIP_TRY(d_rows.ensure((size_t)H.row_bytes));
 
     // ---- step 1: every tract that |t - n| does not rule out, in the class the consensus would start it in
     std::vector<Work> work, next;
@@ -97,16 +86,16 @@ int run(const Host& H, std::vector<int64_t>& rowtab, int32_t n_tracts, const int
             const size_t ni = items.size();
             stats[11] += 1;
             stats[14] = std::max<int64_t>(stats[14], pieces * 16);
-            SPLIT_HIP_TRY(d_items.ensure(ni));
-            SPLIT_HIP_TRY(d_status.ensure(ni));
-            SPLIT_HIP_TRY(d_ptr.ensure((size_t)pieces));
-            SPLIT_HIP_TRY(hipMemcpy(d_items.p, items.data(), ni * sizeof(NraSplitItem), hipMemcpyHostToDevice));
+            NRA_HIP_TRY(d_items.ensure(ni));
+            NRA_HIP_TRY(d_status.ensure(ni));
+            NRA_HIP_TRY(d_ptr.ensure((size_t)pieces));
+            NRA_HIP_TRY(hipMemcpy(d_items.p, items.data(), ni * sizeof(NraSplitItem), hipMemcpyHostToDevice));
             const int e = nra_launch_split_align(nullptr, c, (int)ni, d_items.p, d_groups.p, d_codes.p, d_bb.p, d_ptr.p,
                                                  d_rows.p, d_status.p, max_dist);
             if (e != 0) return fail(NRA_E_DEVICE, std::string("k_split_align: ") + hipGetErrorString((hipError_t)e));
-            SPLIT_HIP_TRY(hipStreamSynchronize(nullptr));
+            NRA_HIP_TRY(hipStreamSynchronize(nullptr));
             status.resize(ni);
-            SPLIT_HIP_TRY(hipMemcpy(status.data(), d_status.p, ni * sizeof(int32_t), hipMemcpyDeviceToHost));
+            NRA_HIP_TRY(hipMemcpy(status.data(), d_status.p, ni * sizeof(int32_t), hipMemcpyDeviceToHost));
             for (size_t q = 0; q < ni; ++q) {
                 const Work& wk = work[i + q];
                 if (status[q] == NRA_CONS_WIDEN) {
@@ -129,37 +118,37 @@ int run(const Host& H, std::vector<int64_t>& rowtab, int32_t n_tracts, const int
     for (size_t g = 0; g < ng; ++g)
         if (dg[g].mv > 0)
             for (int32_t c0 = 0; c0 < dg[g].t; c0 += NRA_SPLIT_THREADS) blocks.push_back(NraSplitBlock{(int32_t)g, c0});
-    SPLIT_HIP_TRY(hipMemcpy(d_groups.p, dg.data(), ng * sizeof(NraSplitGroup), hipMemcpyHostToDevice));
-    SPLIT_HIP_TRY(d_rowtab.ensure((size_t)n_tracts));
+    NRA_HIP_TRY(hipMemcpy(d_groups.p, dg.data(), ng * sizeof(NraSplitGroup), hipMemcpyHostToDevice));
+    NRA_HIP_TRY(d_rowtab.ensure((size_t)n_tracts));
     if (n_tracts > 0)
-        SPLIT_HIP_TRY(hipMemcpy(d_rowtab.p, rowtab.data(), (size_t)n_tracts * sizeof(int64_t), hipMemcpyHostToDevice));
-    SPLIT_HIP_TRY(d_blocks.ensure(blocks.size()));
+        NRA_HIP_TRY(hipMemcpy(d_rowtab.p, rowtab.data(), (size_t)n_tracts * sizeof(int64_t), hipMemcpyHostToDevice));
+    NRA_HIP_TRY(d_blocks.ensure(blocks.size()));
     if (!blocks.empty())
-        SPLIT_HIP_TRY(hipMemcpy(d_blocks.p, blocks.data(), blocks.size() * sizeof(NraSplitBlock), hipMemcpyHostToDevice));
-    SPLIT_HIP_TRY(d_nb.ensure((size_t)H.col_total));
-    SPLIT_HIP_TRY(d_ab.ensure((size_t)H.col_total));
-    SPLIT_HIP_TRY(d_pos.ensure((size_t)H.col_total));
-    SPLIT_HIP_TRY(d_key.ensure((size_t)H.col_total));
-    SPLIT_HIP_TRY(d_mats.ensure((size_t)H.mat_bytes));
-    SPLIT_HIP_TRY(d_labels.ensure((size_t)n_tracts));
-    SPLIT_HIP_TRY(d_sites.ensure((size_t)H.site_total * NRA_SPLIT_SITE_INTS));
-    SPLIT_HIP_TRY(d_res.ensure(ng * NRA_SPLIT_RES_INTS));
+        NRA_HIP_TRY(hipMemcpy(d_blocks.p, blocks.data(), blocks.size() * sizeof(NraSplitBlock), hipMemcpyHostToDevice));
+    NRA_HIP_TRY(d_nb.ensure((size_t)H.col_total));
+    NRA_HIP_TRY(d_ab.ensure((size_t)H.col_total));
+    NRA_HIP_TRY(d_pos.ensure((size_t)H.col_total));
+    NRA_HIP_TRY(d_key.ensure((size_t)H.col_total));
+    NRA_HIP_TRY(d_mats.ensure((size_t)H.mat_bytes));
+    NRA_HIP_TRY(d_labels.ensure((size_t)n_tracts));
+    NRA_HIP_TRY(d_sites.ensure((size_t)H.site_total * NRA_SPLIT_SITE_INTS));
+    NRA_HIP_TRY(d_res.ensure(ng * NRA_SPLIT_RES_INTS));
     int e = nra_launch_split_count(nullptr, (int)blocks.size(), d_blocks.p, d_groups.p, d_rowtab.p, d_rows.p, prm, d_nb.p,
                                    d_ab.p);
     if (e != 0) return fail(NRA_E_DEVICE, std::string("k_split_count: ") + hipGetErrorString((hipError_t)e));
     e = nra_launch_split_phase(nullptr, (int)ng, d_groups.p, d_rowtab.p, d_rows.p, prm, d_nb.p, d_ab.p, d_pos.p, d_key.p,
                                d_mats.p, d_labels.p, d_sites.p, d_res.p);
     if (e != 0) return fail(NRA_E_DEVICE, std::string("k_split_phase: ") + hipGetErrorString((hipError_t)e));
-    SPLIT_HIP_TRY(hipStreamSynchronize(nullptr));
+    NRA_HIP_TRY(hipStreamSynchronize(nullptr));
     res.resize(ng * NRA_SPLIT_RES_INTS);
     sites.resize((size_t)H.site_total * NRA_SPLIT_SITE_INTS);
     mats.resize((size_t)H.mat_bytes);
-    SPLIT_HIP_TRY(hipMemcpy(res.data(), d_res.p, res.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    NRA_HIP_TRY(hipMemcpy(res.data(), d_res.p, res.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (!sites.empty())
-        SPLIT_HIP_TRY(hipMemcpy(sites.data(), d_sites.p, sites.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (!mats.empty()) SPLIT_HIP_TRY(hipMemcpy(mats.data(), d_mats.p, mats.size(), hipMemcpyDeviceToHost));
+        NRA_HIP_TRY(hipMemcpy(sites.data(), d_sites.p, sites.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (!mats.empty()) NRA_HIP_TRY(hipMemcpy(mats.data(), d_mats.p, mats.size(), hipMemcpyDeviceToHost));
     if (n_tracts > 0)
-        SPLIT_HIP_TRY(hipMemcpy(label, d_labels.p, (size_t)n_tracts * sizeof(int32_t), hipMemcpyDeviceToHost));
+        NRA_HIP_TRY(hipMemcpy(label, d_labels.p, (size_t)n_tracts * sizeof(int32_t), hipMemcpyDeviceToHost));
     return NRA_OK;
 }
 
@@ -194,32 +183,16 @@ int nra_allele_split(int device, int32_t n_groups, const int64_t* group_off, int
         if (group_off[g + 1] < group_off[g]) return fail(NRA_E_ARG, "group offsets must not decrease");
     if (n_tracts > 0) {
         if (!seq_off) return fail(NRA_E_ARG, "seq_off is NULL");
-        if (seq_off[0] < 0) return fail(NRA_E_ARG, "negative tract offset");
-        for (int32_t r = 0; r < n_tracts; ++r) {
-            const int64_t len = seq_off[r + 1] - seq_off[r];
-            if (len < 0) return fail(NRA_E_ARG, "tract offsets must not decrease");
-            if (len > NRA_CONS_MAX_N) return fail(NRA_E_RANGE, "tract " + std::to_string(r) + " is longer than 200000 bases");
-        }
+        if (int rc = check_tract_offsets(n_tracts, seq_off, NRA_CONS_MAX_N, "tract")) return rc;
         if (seq_off[n_tracts] > seq_off[0] && !seqs) return fail(NRA_E_ARG, "seqs is NULL");
     }
-    uint8_t lut[256];
-    for (int c = 0; c < 256; ++c) lut[c] = NRA_CONS_CODE_OTHER;
-    lut['A'] = lut['a'] = 0; lut['C'] = lut['c'] = 1; lut['G'] = lut['g'] = 2; lut['T'] = lut['t'] = 3;
     if (n_groups > 0) {
-        if (bb_off[0] < 0) return fail(NRA_E_ARG, "negative backbone offset");
-        for (int32_t g = 0; g < n_groups; ++g) {
-            const int64_t len = bb_off[g + 1] - bb_off[g];
-            if (len < 0) return fail(NRA_E_ARG, "backbone offsets must not decrease");
-            if (len > NRA_CONS_MAX_N) return fail(NRA_E_RANGE, "backbone " + std::to_string(g) + " is longer than 200000 bases");
-        }
+        if (int rc = check_tract_offsets(n_groups, bb_off, NRA_CONS_MAX_N, "backbone", "backbone")) return rc;
         if (bb_off[n_groups] > bb_off[0] && !backbones) return fail(NRA_E_ARG, "backbones is NULL");
         for (int64_t i = bb_off[0]; i < bb_off[n_groups]; ++i)
-            if (lut[(unsigned char)backbones[i]] > 3) return fail(NRA_E_ARG, "a backbone base is not A, C, G or T");
+            if (kBase.of[(unsigned char)backbones[i]] > 3) return fail(NRA_E_ARG, "a backbone base is not A, C, G or T");
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(NRA_E_DEVICE, "no HIP device: nanorepeat_amd has no CPU path");
-    if (device < 0 || device >= ndev) return fail(NRA_E_ARG, "device index out of range");
+    if (int rc = use_device(device, n_groups > 0)) return rc;
     int64_t st[NRA_SPLIT_N_STATS] = {0};
     site_off[0] = 0;
     sym_off[0] = 0;
@@ -227,7 +200,6 @@ int nra_allele_split(int device, int32_t n_groups, const int64_t* group_off, int
         if (stats) std::memcpy(stats, st, sizeof(st));
         return NRA_OK;
     }
-    SPLIT_HIP_TRY(hipSetDevice(device));
     try {
         Host H;
         H.seq.resize((size_t)n_tracts);
@@ -240,11 +212,7 @@ int nra_allele_split(int device, int32_t n_groups, const int64_t* group_off, int
             code_bytes += round_up(H.n[r], 16);
         }
         H.codes.assign((size_t)code_bytes + 16, (uint8_t)NRA_CONS_CODE_OTHER);
-        for (int32_t r = 0; r < n_tracts; ++r) {
-            const unsigned char* s = reinterpret_cast<const unsigned char*>(seqs + seq_off[r]);
-            uint8_t* dst = H.codes.data() + H.seq[r];
-            for (int32_t i = 0; i < H.n[r]; ++i) dst[i] = lut[s[i]];
-        }
+        for (int32_t r = 0; r < n_tracts; ++r) encode(H.codes.data() + H.seq[r], seqs + seq_off[r], H.n[r]);
         std::vector<NraSplitGroup> dg((size_t)n_groups);
         int64_t bb_bytes = 0;
         for (int32_t g = 0; g < n_groups; ++g) {
@@ -264,7 +232,7 @@ int nra_allele_split(int device, int32_t n_groups, const int64_t* group_off, int
         }
         H.bbs.assign((size_t)bb_bytes, (uint8_t)NRA_CONS_CODE_PAD);
         for (int32_t g = 0; g < n_groups; ++g)
-            for (int64_t i = 0; i < dg[g].t; ++i) H.bbs[dg[g].bb + i] = lut[(unsigned char)backbones[bb_off[g] + i]];
+            for (int64_t i = 0; i < dg[g].t; ++i) H.bbs[dg[g].bb + i] = kBase.of[(unsigned char)backbones[bb_off[g] + i]];
         for (int32_t r = 0; r < n_tracts; ++r) dist[r] = -1;
         std::vector<int64_t> rowtab((size_t)n_tracts, -1);
         std::vector<int32_t> res, dsites;

@@ -129,6 +129,27 @@ def test_forced_small_chunks_equal_one_chunk(capi, seeded, monkeypatch):
     _same(capi.tract_segments(sets, tracts, ts, 3), want)
 
 
+def test_chunks_of_single_waves_and_tracts_around_one_block(capi, monkeypatch):
+    """130 tracts of 0, 1, 15, 16, 17 and 33 bases (both sides of the 16-byte block), 129 on a set of 6 states (two waves
+    and one lane more: an empty tract that is the first lane of its wave) and one on a set of 20; in one chunk per state
+    class and with every wave in a chunk of its own."""
+    rng = np.random.default_rng(22)
+    sets = [rand_set(rng, n_states=6, n_motifs=2), rand_set(rng, n_states=20, n_motifs=4)]
+    lengths = [(0, 1, 15, 16, 17, 33)[i % 6] for i in range(129)] + [17]
+    ts = np.array([0] * 129 + [1], np.int32)
+    tracts = [rand_tract(rng, sets[q], n, "runs" if i % 2 else "random") for i, (n, q) in enumerate(zip(lengths, ts))]
+    assert [len(t) for t in tracts] == lengths and min(lengths[:129]) == 0
+    order = rng.permutation(130)
+    tracts, ts = [tracts[i] for i in order], ts[order]
+    want = R.ref_tract_segments(sets, tracts, ts, 3)
+    monkeypatch.delenv("NRA_TEST_SEG_PTR_BYTES", raising=False)
+    one = capi.tract_segments(sets, tracts, ts, 3)
+    monkeypatch.setenv("NRA_TEST_SEG_PTR_BYTES", "1")
+    many = capi.tract_segments(sets, tracts, ts, 3)
+    _same(many, one)
+    _same(one, want)
+
+
 def test_shuffled_tracts_permute_the_outputs(capi, seeded):
     sets, tracts, ts, want = seeded
     perm = np.random.default_rng(3).permutation(len(tracts))

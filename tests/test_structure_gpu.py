@@ -118,6 +118,27 @@ def test_forced_small_chunks_equal_one_chunk(capi, monkeypatch):
     _same(one, ref_read_structure(motifs, tracts, rm))
 
 
+def test_chunks_of_single_waves_and_tracts_around_one_block(capi, monkeypatch):
+    """130 tracts of 0, 1, 15, 16, 17 and 33 bases (both sides of the 16-byte block), 129 of capacity 3 (two waves and
+    one lane more: an empty tract that is the first lane of its wave) and one of capacity 64; in one chunk per capacity
+    and with every wave in a chunk of its own."""
+    rng = np.random.default_rng(21)
+    motifs = ["CAG", _motif(rng, 40)]
+    lengths = [(0, 1, 15, 16, 17, 33)[i % 6] for i in range(129)] + [17]
+    rm = np.array([0] * 129 + [1], np.int32)
+    tracts = [(motifs[m] * 12)[i % 3:][:n] if i % 2 else synth.rand_seq(rng, n) for i, (n, m) in enumerate(zip(lengths, rm))]
+    assert [len(t) for t in tracts] == lengths and min(lengths[:129]) == 0
+    order = rng.permutation(130)
+    tracts, rm = [tracts[i] for i in order], rm[order]
+    want = ref_read_structure(motifs, tracts, rm)
+    monkeypatch.delenv("NRA_TEST_STRUCT_PTR_BYTES", raising=False)
+    one = capi.read_structure(motifs, tracts, rm)
+    monkeypatch.setenv("NRA_TEST_STRUCT_PTR_BYTES", "1")
+    many = capi.read_structure(motifs, tracts, rm)
+    _same(many, one)
+    _same(one, want)
+
+
 def test_config4_scale_call_matches_on_a_sample(capi):
     d = synth.config4(1000, 1000)
     motifs = [u for _, u, _ in d["regions"]]
