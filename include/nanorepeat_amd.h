@@ -441,6 +441,21 @@ int nra_read_structure(int device, int32_t n_motifs, const char* motifs, const i
 int nra_tract_motifs(int device, int32_t n_tracts, const char* seqs, const int64_t* seq_off, int32_t max_period,
                      int32_t top_n, int32_t* n_tandem, int8_t* top_p, int32_t* top_code, int32_t* top_count);
 
+/* ---- tandem periods: the lag-match spectrum of a tract for lags up to 64 (no counterpart in the reference) ---------
+ *
+ * For each tract s (n bases, upper-cased first) and each lag p = 1..max_period:
+ *   valid[p] = #{ i : 0 <= i, i + p < n, s[i] and s[i+p] both A, C, G or T }
+ *   match[p] = #{ those i with s[i] == s[i+p] }
+ * Where n <= p both are 0.  match[p] / valid[p] is the share of the tract that repeats at distance p: near 1 at the
+ * period of a tandem repeat and at its multiples, near 1/4 for sequence without a period.  The outputs are integers:
+ * the result of a tract does not depend on the other tracts of the call or on their order.  DESIGN.md section 22. */
+
+/* tract t = bytes [seq_off[t], seq_off[t+1]) of `seqs` (at most 200 000 bases, NRA_E_RANGE beyond; empty tracts and
+ * n_tracts = 0 are fine).  Writes match[t * max_period + p - 1] and valid[t * max_period + p - 1] for p = 1..max_period.
+ * 1 <= max_period <= 64, else NRA_E_ARG; arguments are checked before the device is touched. */
+int nra_tract_periods(int device, int32_t n_tracts, const char* seqs, const int64_t* seq_off, int32_t max_period,
+                      int32_t* match, int32_t* valid);
+
 /* ---- anchored extension: how many repeat units a tract shows from one anchored end (no counterpart in the reference)
  *
  * For a read with one anchor only: the sequence s that follows the anchor (n bases, upper-cased first; a byte other

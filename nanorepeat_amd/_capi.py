@@ -37,7 +37,7 @@ EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count
            "nra_batch1d_fetch", "nra_batch1d_resweeps", "nra_batch2d_fetch", "nra_batch_destroy",
            "nra_screen_create", "nra_screen_reads", "nra_screen_stats", "nra_screen_destroy",
            "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts", "nra_mixture_fit",
-           "nra_tract_consensus", "nra_allele_split", "nra_tract_segments")
+           "nra_tract_consensus", "nra_allele_split", "nra_tract_segments", "nra_tract_periods")
 
 
 E_RANGE = -3      # NRA_E_RANGE
@@ -196,6 +196,8 @@ def load():
     lib.nra_tract_segments.restype = C.c_int
     lib.nra_tract_segments.argtypes = [C.c_int, C.c_int32, pi32, C.c_char_p, pi64, C.c_int32, C.c_char_p, pi64, pi32,
                                        C.c_int32, pi32, pi32, pi32, p8, p8]
+    lib.nra_tract_periods.restype = C.c_int
+    lib.nra_tract_periods.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, C.c_int32, pi32, pi32]
     _LIB = lib
     return lib
 
@@ -688,6 +690,18 @@ def tract_motifs(tracts, max_period=6, top_n=4, device=0):
     _check(lib.nra_tract_motifs(device, n, data, _ptr(off, C.c_int64), max_period, top_n,
                                 _ptr(out["n_tandem"], C.c_int32), _ptr(out["top_p"], C.c_int8),
                                 _ptr(out["top_code"], C.c_int32), _ptr(out["top_count"], C.c_int32)))
+    return out
+
+
+def tract_periods(tracts, max_period=64, device=0):
+    """nra_tract_periods: per tract and lag p = 1..max_period, the positions i with s[i] and s[i + p] both ACGT
+    (valid) and those of them with s[i] == s[i + p] (match) -> dict(match, valid), int32 [n, max_period]."""
+    lib = load()
+    data, off = pack_reads(list(tracts))
+    n = len(off) - 1
+    out = dict(match=np.zeros((n, max(max_period, 0)), np.int32), valid=np.zeros((n, max(max_period, 0)), np.int32))
+    _check(lib.nra_tract_periods(device, n, data, _ptr(off, C.c_int64), max_period, _ptr(out["match"], C.c_int32),
+                                 _ptr(out["valid"], C.c_int32)))
     return out
 
 

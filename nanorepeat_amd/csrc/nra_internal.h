@@ -285,6 +285,16 @@ struct NraMotifTract {
     int32_t pad;
 };
 
+// Tandem periods (nra_period.hip, nra_period_host.cpp): per tract and lag p = 1..64, the positions i with s[i] and
+// s[i + p] both ACGT and those of them with s[i] == s[i + p].  One wave per tract, a lane per
+// lag; codes as for the tandem motifs, tracts start 16-byte aligned and are read in words of 32 bases.
+#define NRA_PERIOD_MAX_P 64
+#define NRA_PERIOD_MAX_N 200000
+#define NRA_PERIOD_WORD 32                    // bases per packed word: a lane loads 32 bytes
+#define NRA_PERIOD_ALIGN 16                   // tracts start at multiples of it
+#define NRA_PERIOD_PAD 32                     // bytes after the last tract of a chunk: a word may end beyond its tract
+typedef NraMotifTract NraPeriodTract;         // (off, n): the tract's codes start at byte `off` of the chunk's buffer
+
 // Mixture fits (nra_mixture.hip, nra_mixture_host.cpp): one workgroup of 256 threads per fit.
 // A problem of up to 256 * KREG_SMALL or 256 * KREG points keeps its points in registers, a larger one streams them.
 #define NRA_MIX_THREADS 256
@@ -448,6 +458,10 @@ int nra_launch_extend(hipStream_t st, int P, int n_reads, const NraStructRead* r
 int nra_launch_tract_motifs(hipStream_t st, int n_grid, int n_tracts, const NraMotifTract* tracts,
                             const uint8_t* codes, const int16_t* dense_of, int max_p, int top_n, int32_t* n_tandem,
                             uint32_t* top_key);
+
+// tandem periods (nra_period.hip): one wave per tract, n_grid workgroups of four waves.  match / valid[t * 64 + p - 1]
+int nra_launch_tract_periods(hipStream_t st, int n_grid, int n_tracts, const NraPeriodTract* tracts,
+                             const uint8_t* codes, int32_t* match, int32_t* valid);
 
 // launchers (nra_kernels.hip).  All asynchronous on `st`; return hipError_t as int.
 int nra_launch_score_pk16(int R, int has_n, hipStream_t st, int n_tasks,

@@ -159,10 +159,11 @@ def _resize(repeat_regions, fast_mode, device, scorer, scoring):
             rm.size_in_motif = np.float64(out["sum_k"][i]) / np.float64(out["n_ties"][i])
 
 
-def _ordered_reads(region):
-    """phased_reads.txt order (allele by allele), then the other reads with a core by name: [(name, allele id)]."""
+def _ordered_reads(region, per_read="read_motifs"):
+    """phased_reads.txt order (allele by allele), then the other reads with a core by name: [(name, allele id)].  The
+    reads with a core are the keys of the region's `per_read` dict."""
     res = phasing.results_of(region)
-    cored = list(getattr(region, "read_motifs", None) or {})
+    cored = list(getattr(region, per_read, None) or {})
     label = {n: q.allele_id for n, q in res.quantified_read_dict.items()}
     phased = sorted((n for n in cored if label.get(n, -1) >= 1), key=lambda n: label[n])   # stable: file order
     rest = sorted(n for n in cored if label.get(n, -1) < 1)

@@ -172,7 +172,7 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
                       num_cpu=1, device=0, scoring=None, seed=None, read_structure=False, discover_motifs=False,
                       min_motif_count=4, min_motif_share=0.1, partial_reads=False, mixture="sklearn",
                       allele_consensus=False, allele_split=False, motif_runs=False, segment_motifs=None,
-                      switch_cost=None, read_alignments=False, **engines):
+                      switch_cost=None, read_alignments=False, discover_periods=False, **engines):
     """The BAM command from files to files (nanoRepeat_bam.py:614-751): for every region of the BED
     file, reads from the alignment file -> `<out_prefix>.details/<chr>/<region>.*` ->
     `<out_prefix>.NanoRepeat_output.tsv`.  The reference forks up to 16 workers, one region each;
@@ -189,9 +189,11 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
     runs of the motifs of the region's motif set (the BED motif, then segment_motifs[region key] when that dict names
     the region, else the motifs discovered in the reads); switch_cost is the price of changing motif (None: the
     default of segments.py).  read_alignments=True adds `<region>.round3.paf` (alignments.py): the alignment of every
-    read with a round-3 size of its own to the template it was called at.
+    read with a round-3 size of its own to the template it was called at.  discover_periods=True adds the tandem
+    period files (periods.py): the period (up to 64 bases) and the unit of every allele's consensus tract, every read's
+    evidence for it, and the reads' sizes in that unit where it is not the BED motif.
     `engines` may carry aligner / scorer / structure_engine / motif_engine / extension_engine / mixture_engine /
-    consensus_engine / split_engine / segment_engine / path_aligner stand-ins.  Returns the regions."""
+    consensus_engine / split_engine / segment_engine / path_aligner / period_engine stand-ins.  Returns the regions."""
     from . import bam as nr_bam, mixture as nr_mixture
     nr_mixture.check_engine_name(mixture)
     regions = nr_io.read_repeat_region_file(repeat_region_bed, no_details)
@@ -211,7 +213,7 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
                         read_structure, _motif_options(discover_motifs, min_motif_count, min_motif_share),
                         partial_reads, mixture, allele_consensus, allele_split,
-                        _run_options(motif_runs, segment_motifs, switch_cost), read_alignments)
+                        _run_options(motif_runs, segment_motifs, switch_cost), read_alignments, discover_periods)
     return regions
 
 
@@ -237,7 +239,8 @@ def _run_options(motif_runs, segment_motifs, switch_cost):
 def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
                         read_structure=False, motif_options=None, partial_reads=False, mixture="sklearn",
-                        allele_consensus=False, allele_split=False, run_options=None, read_alignments=False):
+                        allele_consensus=False, allele_split=False, run_options=None, read_alignments=False,
+                        discover_periods=False):
     """The commands' common tail: steps 1-4 for the regions with reads, then one TSV row per BED region; with
     read_structure, the structure of every read with a size and the two structure files; with motif_options (a dict
     of motifs.motif_regions keywords), the tandem motifs of every read with a core and the two motif files; with
@@ -248,7 +251,8 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
     split; with run_options (a dict of segments.segments_regions keywords), the motif runs of every read with a core and
     of every allele's consensus, the two run files and one NOTICE counting the alleles of more than one run; with
     read_alignments, the round-3 alignment of every read with a size of its own, one file per region and a NOTICE per
-    region that left reads out."""
+    region that left reads out; with discover_periods, the tandem period of every allele's consensus tract and every
+    read's evidence for it, the two period files and one NOTICE counting the alleles whose unit is not the BED motif."""
     quantify_regions(live, reads_of, data_type, fast_mode, num_cpu, device, scoring,
                      engines.get("aligner"), engines.get("scorer"), keep_candidates=read_alignments and not no_details)
     phase_regions(live, data_type, ploidy, max_mutual_overlap, max_num_components, remove_noisy_reads, seed,
@@ -309,6 +313,16 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
         for region in live:
             alignments.write_read_alignments(region)
         alignments.report_left_out_reads(live)
+    if discover_periods:
+        from . import periods
+        periods.period_regions(live, fast_mode, device=device, engine=engines.get("period_engine"),
+                               scorer=engines.get("scorer"), scoring=scoring,
+                               consensus_engine=engines.get("consensus_engine"),
+                               structure_engine=engines.get("structure_engine"))
+        for region in live:
+            periods.write_read_periods(region)
+        periods.write_period_summary(regions, out_prefix)
+        periods.report_foreign_units(live)
     if no_details:
         import shutil
         shutil.rmtree(f"{out_prefix}.details", ignore_errors=True)
@@ -320,7 +334,8 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         num_cpu=1, device=0, scoring=None, seed=None, screen=True, k=15, min_hits=4, max_occ=16,
                         chunk_bases=1 << 28, read_structure=False, discover_motifs=False, min_motif_count=4,
                         min_motif_share=0.1, mixture="sklearn", allele_consensus=False, allele_split=False,
-                        motif_runs=False, segment_motifs=None, switch_cost=None, read_alignments=False, **engines):
+                        motif_runs=False, segment_motifs=None, switch_cost=None, read_alignments=False,
+                        discover_periods=False, **engines):
     """The FASTQ / FASTA command (nanoRepeat.py:109, `-t fastq|fasta`) from files to files, without a genome mapper:
     the reads each region sees are chosen by the anchor k-mer screen (screen.reads_by_region) instead of a
     genome-wide mapping and a BAM window, then the BAM command's steps run unchanged.  Every region's reference
@@ -331,9 +346,10 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
     tandem motif files (motifs.py).  mixture="gpu" fits the phasing mixtures on the GPU (see phase_regions).
     allele_consensus=True adds the consensus sequence of every allele's tract (consensus.py); allele_split=True adds
     the allele split files (split.py); motif_runs=True adds the motif run files (segments.py; segment_motifs and
-    switch_cost as for quantify_from_bam); read_alignments=True adds the round-3 alignment files (alignments.py).
+    switch_cost as for quantify_from_bam); read_alignments=True adds the round-3 alignment files (alignments.py);
+    discover_periods=True adds the tandem period files (periods.py).
     `engines` may carry aligner / scorer / screener / structure_engine / motif_engine / mixture_engine /
-    consensus_engine / split_engine / segment_engine / path_aligner stand-ins.  Returns the regions."""
+    consensus_engine / split_engine / segment_engine / path_aligner / period_engine stand-ins.  Returns the regions."""
     from . import screen as nr_screen, mixture as nr_mixture
     nr_mixture.check_engine_name(mixture)
     regions = nr_io.read_repeat_region_file(repeat_region_bed, no_details)
@@ -362,7 +378,7 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         read_structure, _motif_options(discover_motifs, min_motif_count, min_motif_share),
                         mixture=mixture, allele_consensus=allele_consensus, allele_split=allele_split,
                         run_options=_run_options(motif_runs, segment_motifs, switch_cost),
-                        read_alignments=read_alignments)
+                        read_alignments=read_alignments, discover_periods=discover_periods)
     return regions
 
 

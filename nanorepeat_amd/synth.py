@@ -474,3 +474,60 @@ def split_panel(reads_per_haplotype=8, anchor_len=1000, model="hifi", seed=6):
     return dict(ref={"chr1": chrom}, bed=[f"{c}\t{st}\t{en}\t{u}\n" for c, st, en, u in regions], regions=regions,
                 reads=reads, truth=truth, haplotype=haplotype,
                 planted=[[tr if len(tr) == 2 else None for tr in alleles] for _, _, alleles in loci])
+
+
+def primitive_unit(rng, m):
+    """A random unit of m bases that is no power of a shorter word."""
+    while True:
+        u = rand_unit(rng, m)
+        if not any(m % d == 0 and u[:d] * (m // d) == u for d in range(1, m)):
+            return u
+
+
+def period_panel(reads_per_allele=8, anchor_len=1000, model="hifi", seed=SEED):
+    """A small panel of long-unit loci, for the tandem periods (periods.py): a CSTB-like dodecamer (BED CCCCGCCCCGCG; 4
+    and 14 copies), a 30-mer and a 60-mer locus with seeded primitive units (6 and 14, 5 and 11 copies), a locus whose
+    BED motif is wrong (BED and reference hold the 30-mer; one allele carries 7 copies of it, the other 15 copies of
+    another seeded 30-mer), the TATTG (12 and 30 units) and CAG (15 and 40) controls, and one region whose "tract" is
+    200 bases of sequence without a period (BED ACTGG; one allele).  Reads span both anchors, half reverse-complemented,
+    through the `model` error channel.  Its own random stream.
+
+    Returns dict(ref, bed, regions, reads, truth) like panel(), plus planted = [per region, per allele in the order
+    above: (unit or None, copies)].
+    """
+    rng = np.random.default_rng(seed)
+    cstb = "CCCCGCCCCGCG"
+    u30, u60, v30 = primitive_unit(rng, 30), primitive_unit(rng, 60), primitive_unit(rng, 30)
+    plain = rand_seq(rng, 200)
+    loci = [(cstb, cstb * 3, [(cstb, 4), (cstb, 14)]),
+            (u30, u30 * 8, [(u30, 6), (u30, 14)]),
+            (u60, u60 * 6, [(u60, 5), (u60, 11)]),
+            (u30, u30 * 8, [(u30, 7), (v30, 15)]),
+            ("TATTG", "TATTG" * 16, [("TATTG", 12), ("TATTG", 30)]),
+            ("CAG", "CAG" * 20, [("CAG", 15), ("CAG", 40)]),
+            ("ACTGG", plain, [(None, 0)])]
+    gap, extra = 3000, 800
+    parts, regions, at = [], [], 0
+    for unit, ref_tract, _ in loci:
+        left, right = rand_seq(rng, anchor_len + extra), rand_seq(rng, anchor_len + extra)
+        start = at + gap + len(left)
+        regions.append(("chr1", start, start + len(ref_tract), unit))
+        parts += [rand_seq(rng, gap), left, ref_tract, right]
+        at += gap + len(left) + len(ref_tract) + len(right)
+    parts.append(rand_seq(rng, gap))
+    chrom = "".join(parts)
+    raw, truth = [], {}
+    for g, ((_, _, alleles), (_, st, en, _)) in enumerate(zip(loci, regions)):
+        for a, (unit, copies) in enumerate(alleles):
+            tract = plain if unit is None else unit * copies
+            for i in range(reads_per_allele):
+                lo, ro = anchor_len + int(rng.integers(0, 301)), anchor_len + int(rng.integers(0, 301))
+                name = f"v{g}_{a}_{i:02d}"
+                raw.append((name, chrom[st - lo:st] + tract + chrom[en:en + ro]))
+                truth[name] = (g, a)
+    seqs = apply_errors_batch(rng, [s for _, s in raw], model)
+    reads = [(name, revcomp(s) if rng.random() < 0.5 else s) for (name, _), s in zip(raw, seqs)]
+    order = rng.permutation(len(reads))
+    reads = [reads[i] for i in order]
+    return dict(ref={"chr1": chrom}, bed=[f"{c}\t{st}\t{en}\t{u}\n" for c, st, en, u in regions], regions=regions,
+                reads=reads, truth=truth, planted=[list(alleles) for _, _, alleles in loci])
