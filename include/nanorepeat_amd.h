@@ -353,6 +353,10 @@ int  nra_batch1d_fetch(nra_batch_t* b,
 /* 1D, after sync: how many sweep tasks (read pairs, or two pairs of the half-wave sweeps) and reads the relaxed anchor
  * columns sent to the exact re-sweep in the last run, and how many there were in all (0 / 0 with NRA_F_FULL_ANCHORS) */
 int  nra_batch1d_resweeps(nra_batch_t* b, int64_t* tasks, int64_t* reads, int64_t* tasks_total, int64_t* reads_total);
+/* 1D: which per-candidate arrays a run of this batch clears before its kernels start (additive, ABI 4; for tests and
+ * measurements).  *scores: cand_score and the flank verdicts -- 0 where every bucket's forward sweeps write them for every
+ * candidate; *extents: cand_tstart / cand_tend -- 0 where the selection kernel sets them to -1 on its way */
+int  nra_batch1d_clears(nra_batch_t* b, int32_t* scores, int32_t* extents);
 int  nra_batch2d_fetch(nra_batch_t* b, int8_t* read_strand,
                        int32_t* cell_score, int32_t* cell_wscore,
                        int32_t* best_wscore, int64_t* sum_k1, int64_t* sum_k2,

@@ -34,7 +34,7 @@ F_FULL_ANCHORS = 8192  # testing / comparison, 1D: the exact cell over every anc
 EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count",
            "nra_default_scoring", "nra_release_cached_memory", "nra_round3_1d", "nra_joint_2d", "nra_align_pairs", "nra_align_pairs_cigar", "nra_align_paths", "nra_batch1d_create",
            "nra_batch2d_create", "nra_batch2d_create_reads", "nra_batch2d_set_cells", "nra_joint_grid_cells", "nra_batch2d_set_grid", "nra_batch2d_invalidate", "nra_batch2d_sweep_flanks", "nra_batch2d_refine", "nra_batch_run", "nra_batch_sync", "nra_batch_stats",
-           "nra_batch1d_fetch", "nra_batch1d_resweeps", "nra_batch2d_fetch", "nra_batch_destroy",
+           "nra_batch1d_fetch", "nra_batch1d_resweeps", "nra_batch1d_clears", "nra_batch2d_fetch", "nra_batch_destroy",
            "nra_screen_create", "nra_screen_reads", "nra_screen_stats", "nra_screen_destroy",
            "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts", "nra_mixture_fit",
            "nra_tract_consensus", "nra_allele_split", "nra_tract_segments", "nra_tract_periods")
@@ -162,6 +162,8 @@ def load():
     lib.nra_batch1d_fetch.restype = C.c_int
     lib.nra_batch1d_resweeps.restype = C.c_int
     lib.nra_batch1d_resweeps.argtypes = [vp, pi64, pi64, pi64, pi64]
+    lib.nra_batch1d_clears.restype = C.c_int
+    lib.nra_batch1d_clears.argtypes = [vp, pi32, pi32]
     lib.nra_batch1d_fetch.argtypes = [vp, pi32, pi64, pi32, p8, pi32, pi32, pi32]
     lib.nra_batch2d_fetch.restype = C.c_int
     lib.nra_batch2d_fetch.argtypes = [vp, pi8, pi32, pi32, pi32, pi64, pi64, pi32, p8]
@@ -579,6 +581,12 @@ class Batch:
         v = [C.c_int64(0) for _ in range(4)]
         _check(load().nra_batch1d_resweeps(self._h, *[C.byref(x) for x in v]))
         return {"tasks": v[0].value, "reads": v[1].value, "tasks_total": v[2].value, "reads_total": v[3].value}
+
+    def clears(self):
+        """1D: which per-candidate arrays a run of this batch clears before its kernels start."""
+        v = [C.c_int32(0) for _ in range(2)]
+        _check(load().nra_batch1d_clears(self._h, *[C.byref(x) for x in v]))
+        return {"scores": bool(v[0].value), "extents": bool(v[1].value)}
 
     def fetch(self, per_candidate=True):
         lib = load()

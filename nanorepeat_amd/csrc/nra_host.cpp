@@ -584,9 +584,9 @@ struct nra_batch {
     int payload_strips = 0;                     // waves of a chained payload launch (strips in chain_payload)
     DevBuf<NraChainBlock> chain_blocks;         // k_sweep_ringmt: (task, row block) lists, launch group after launch group
     DevBuf<uint64_t> mt_strips;                 // ... the granule strips between consecutive blocks (zeroed at create)
-    DevBuf<int32_t> mt_words;                   // ... [0] launch-wide give-up word (kMtGiveUp), [1] unused, [2 + bucket] that bucket's ticket
+    DevBuf<int32_t> mt_words;                   // ... [0], [1] unused (the give-up word is mt_giveup), [2 + bucket] that bucket's ticket
     // the sweeps in quanta (k_sweep_ringq): ticket order, the words of a run ([0] give-up word, [1 + bucket] that bucket's
-    // ticket, then one arrival counter per task -- zeroed by one memset per run), the wave states at the cut
+    // ticket, then one arrival counter per task -- a view into run_words), the wave states at the cut
     DevBuf<uint32_t> q_list;
     DevBuf<int32_t> q_words, q_state;
     size_t q_words_n = 0, q_arrivals_off = 0;
@@ -594,6 +594,14 @@ struct nra_batch {
     DevBuf<NraTask> queue_tasks;
     DevBuf<int32_t> queue_count;   // per bucket: prebuilt queue length (constant)
     DevBuf<int32_t> tie_count;     // per bucket: tie queue length (device-written)
+    // 1D: the small words a run starts from zero -- q_words, the row blocks' give-up word, tie_count, redo -- are views
+    // into ONE allocation, cleared by one memset per run
+    DevBuf<int32_t> run_words;
+    int32_t* mt_giveup = nullptr;  // ... the launch-wide give-up word of the row blocks (k_sweep_ringmt)
+    // 1D: the forward sweeps of this batch write cand_score and cand_flag of every candidate, so a run clears neither
+    bool sweeps_write_all = false;
+    int32_t* giveup_out = nullptr; // 1D: two trailing words of the result block: the run's give-up words (quanta, row blocks)
+    bool results_staged = false;   // 1D: the pinned mirror holds the result block of the last run
     DevBuf<uint32_t> bucket_task_base;
     // 1D
     DevBuf<int32_t> kmin, kmax, read_bucket;
@@ -906,7 +914,7 @@ int alloc_results(nra_batch* b, size_t n, bool two_d)
 {
     const size_t n8 = two_d ? 2 : 1;
     const size_t np = (n + 7) & ~(size_t)7;                 // keeps every sub-array 8-byte aligned
-    b->result_bytes = np * (8 * n8 + 4 + 4 + 1 + (two_d ? 1 : 0));
+    b->result_bytes = np * (8 * n8 + 4 + 4 + 1 + (two_d ? 1 : 0)) + (two_d ? 0 : 8);
     HIP_TRY(b->result_block.alloc(b->result_bytes));
     HIP_TRY(g_handles.pinned_get(std::max<size_t>(b->result_bytes, 8), &b->result_stage, &b->result_stage_bytes));
     uint8_t* p = b->result_block.p;
@@ -919,6 +927,7 @@ int alloc_results(nra_batch* b, size_t n, bool two_d)
     view(b->n_ties, np * 4);
     view(b->status, np);
     if (two_d) view(b->strand_out, np);
+    else b->giveup_out = reinterpret_cast<int32_t*>(p);     // 1D: the run's give-up words, written by k_select_final_1d
     return NRA_OK;
 }
 
@@ -1423,10 +1432,7 @@ int nra_batch1d_create(int device, const nra_region_t* regions, int32_t n_region
         bool any_taint = false;
         for (const Bucket& bk : b->buckets) any_taint = any_taint || bk.taint;
         if (any_taint) {
-            HIP_TRY(b->redo.alloc(std::max<size_t>(sweep_tasks.size(), 1)));
-            // (zero before any run, so that nra_batch1d_resweeps reads no flag of a run that has not happened)
-            HIP_TRY(hipMemsetAsync(b->redo.p, 0, b->redo.n * 4, b->stream));
-            HIP_TRY(hipStreamSynchronize(b->stream));
+            b->redo.n = std::max<size_t>(sweep_tasks.size(), 1);        // (a view into run_words, below)
             b->task_reads.resize(sweep_tasks.size());
             for (size_t t = 0; t < sweep_tasks.size(); ++t) {
                 const NraSweepTask& x = sweep_tasks[t];
@@ -1494,10 +1500,39 @@ int nra_batch1d_create(int device, const nra_region_t* regions, int32_t n_region
         if (!qlist.empty()) {
             HIP_TRY(b->q_list.upload(qlist));
             b->q_arrivals_off = (1 + b->buckets.size() + 3) / 4 * 4;
-            b->q_words_n = b->q_arrivals_off + q_tasks;
-            HIP_TRY(b->q_words.alloc(b->q_words_n));
+            b->q_words_n = b->q_arrivals_off + q_tasks;            // (a view into run_words, below)
             HIP_TRY(b->q_state.alloc(q_state));
         }
+    }
+    {
+        // Does a run have to clear cand_score and cand_flag first (run_1d)?  Not where the forward sweeps write both for
+        // every candidate.  Per kernel family, from its `flush` (nra_sweep.hip): a task's sweep puts out one value per
+        // repeat count of [task kmin, task kmax], the union of its reads' windows (the boundary of kcur leaves lane W - 1
+        // while kcur <= kmax; the last, partial group of W is flushed behind the loop), and `flush` stores score (-1 below
+        // min_score) and verdict for every read of the task whose window holds that count, under no other condition.
+        // A half-wave task's empty upper half (`half_on`) has no reads.  The re-sweep only rewrites.
+        // The table records that reading, family by family: a new family, or one whose `flush` changes, goes in with
+        // `false` (its batches keep the clears) until its `flush` has been read again.
+        enum Family { F_RING, F_RING32, F_RINGQ, F_RINGMT, F_RINGCHAIN, F_PK16, F_COUNT };
+        static const bool kFlushWritesAll[F_COUNT] = {
+            true,       // k_sweep_ring      (sweep_ring_body)
+            true,       // k_sweep_ring32    (sweep_ring_body, HALF)
+            true,       // k_sweep_ringq     (sweep_ring_body, QUANTA: the part that ends the forward sweep flushes the rest)
+            true,       // k_sweep_ringmt    (the last row block's wave)
+            true,       // k_sweep_ringchain (the last row block)
+            true,       // k_sweep_pk16      (sweep_body; CHAIN: the last row block)
+        };
+        // not with brute force, NRA_F_ALL_EXTENTS or NRA_F_TIE_EXTENTS (no sweeps; the cleared flag 2 is what sends a
+        // candidate to the extents kernel there), and every read with candidates has to be in a bucket (an empty read is
+        // in none: its candidates keep the cleared -1)
+        bool all = !brute && !all_ext && (flags & NRA_F_TIE_EXTENTS) == 0;
+        for (int32_t r = 0; r < n_reads && all; ++r) all = kmin[r] > kmax[r] || pr.reads[r].qlen > 0;
+        for (const Bucket& bk : b->buckets) {
+            const Family f = bk.quanta ? F_RINGQ : bk.mt ? F_RINGMT : (bk.ring && bk.chain) ? F_RINGCHAIN
+                           : (bk.ring && bk.half) ? F_RING32 : bk.ring ? F_RING : F_PK16;
+            all = all && kFlushWritesAll[f];
+        }
+        b->sweeps_write_all = all;
     }
     HIP_TRY(b->cand_flag.alloc((size_t)total));
     if (!chain_blocks.empty()) {
@@ -1520,7 +1555,20 @@ int nra_batch1d_create(int device, const nra_region_t* regions, int32_t n_region
     if (all_ext) HIP_TRY(b->queue_tasks.upload(queue_tasks));
     else HIP_TRY(b->queue_tasks.alloc(queue_total));
     HIP_TRY(b->queue_count.upload(queue_count));
-    HIP_TRY(b->tie_count.alloc(nb));
+    {
+        // the words of a run: [q_words | the row blocks' give-up word | tie_count | redo], zero before any run too (so that
+        // nra_batch1d_resweeps reads no flag of a run that has not happened)
+        const size_t n_redo = b->redo.n, n_words = b->q_words_n + 1 + std::max<size_t>(nb, 1) + n_redo;
+        HIP_TRY(b->run_words.alloc(n_words));
+        int32_t* w = b->run_words.p;
+        auto view = [&](DevBuf<int32_t>& buf, size_t n) { buf.p = w; buf.n = n; buf.owned = false; w += n; };
+        view(b->q_words, b->q_words_n);
+        b->mt_giveup = w++;
+        view(b->tie_count, std::max<size_t>(nb, 1));
+        view(b->redo, n_redo);
+        HIP_TRY(hipMemsetAsync(b->run_words.p, 0, n_words * 4, b->stream));
+        HIP_TRY(hipStreamSynchronize(b->stream));
+    }
     HIP_TRY(b->bucket_task_base.upload(task_base));
     {
         std::vector<int32_t> v(kmin, kmin + n_reads); HIP_TRY(b->kmin.upload(v));
@@ -1558,6 +1606,10 @@ int nra_batch1d_create(int device, const nra_region_t* regions, int32_t n_region
     return NRA_OK;
 }
 
+// what a run of a 1D batch clears first (run_1d; nra_batch1d_clears reports it)
+static bool clears_scores_1d(const nra_batch* b) { return !(NRA_LEAN_CLEARS != 0 && b->sweeps_write_all); }
+static bool clears_extents_1d(const nra_batch* b) { return NRA_LEAN_CLEARS == 0 || (b->flags & NRA_F_ALL_EXTENTS) != 0; }
+
 static int run_1d(nra_batch* b)
 {
     hipStream_t st = b->stream;
@@ -1565,24 +1617,37 @@ static int run_1d(nra_batch* b)
     const bool all_ext = (b->flags & NRA_F_ALL_EXTENTS) != 0;
     const size_t nc = (size_t)b->n_cands;
     HIP_TRY(hipEventRecord(b->ev[0], st));
-    HIP_TRY(hipMemsetAsync(b->cand_score.p, 0xff, std::max<size_t>(nc, 1) * 4, st));
-    HIP_TRY(hipMemsetAsync(b->cand_tstart.p, 0xff, std::max<size_t>(nc, 1) * 4, st));
-    HIP_TRY(hipMemsetAsync(b->cand_tend.p, 0xff, std::max<size_t>(nc, 1) * 4, st));
-    HIP_TRY(hipMemsetAsync(b->tie_count.p, 0, std::max<size_t>(nb, 1) * 4, st));
-    HIP_TRY(hipMemsetAsync(b->cand_flag.p, 2, std::max<size_t>(nc, 1), st));   // 2 = "needs the extents DP"
+    b->results_staged = false;
+    // What a run clears.  cand_score (-1) and cand_flag (2 = "needs the extents DP") only where a kernel of the run may
+    // leave a candidate unwritten: the forward sweeps of a batch with sweeps_write_all write both for every candidate.
+    // cand_tstart / cand_tend read -1 where no extents were computed: k_select_best_1d writes that on its way through the
+    // candidates, but with NRA_F_ALL_EXTENTS the extents kernel runs before it.
+    // (NRA_TEST_POISON_OUTPUTS in the environment, tests only: every array that goes uncleared is filled with 0x5a instead,
+    // so that a stale or uninitialised value that reached a result would show.)
+    const bool clear_scores = clears_scores_1d(b), clear_extents = clears_extents_1d(b);
+    const bool poison = getenv("NRA_TEST_POISON_OUTPUTS") != nullptr;
+    if (clear_scores || poison) {
+        HIP_TRY(hipMemsetAsync(b->cand_score.p, clear_scores ? 0xff : 0x5a, std::max<size_t>(nc, 1) * 4, st));
+        HIP_TRY(hipMemsetAsync(b->cand_flag.p, clear_scores ? 2 : 0x5a, std::max<size_t>(nc, 1), st));
+    }
+    if (clear_extents || poison) {
+        HIP_TRY(hipMemsetAsync(b->cand_tstart.p, clear_extents ? 0xff : 0x5a, std::max<size_t>(nc, 1) * 4, st));
+        HIP_TRY(hipMemsetAsync(b->cand_tend.p, clear_extents ? 0xff : 0x5a, std::max<size_t>(nc, 1) * 4, st));
+    }
+    // the words of the run in one memset: the quanta's give-up word, tickets and arrival counters, the row blocks' give-up
+    // word, the tie queues' lengths, the re-sweep flags
+    HIP_TRY(hipMemsetAsync(b->run_words.p, 0, b->run_words.n * 4, st));
+    // (NRA_TEST_MT_GIVEUP in the environment, tests only: the run starts with the give-up words set, as if a wave had
+    // timed out -- every waiting wave leaves at its next look and the fetch reports NRA_E_DEVICE)
+    const bool test_giveup = getenv("NRA_TEST_MT_GIVEUP") != nullptr;
     if (b->chain_blocks.n > 0) {
-        // concurrent row blocks: every block adds its maximum to the read's A (atomicMax; A >= 0); the give-up word
+        // concurrent row blocks: every block adds its maximum to the read's A (atomicMax; A >= 0)
         HIP_TRY(hipMemsetAsync(b->read_a1d.p, 0, std::max<size_t>((size_t)b->n_reads, 1) * 4, st));
-        // (NRA_TEST_MT_GIVEUP in the environment, tests only: the run starts with the give-up word set, as if a wave had
-        // timed out -- every waiting wave leaves at its next look and the fetch reports NRA_E_DEVICE)
-        HIP_TRY(hipMemsetAsync(b->mt_words.p, getenv("NRA_TEST_MT_GIVEUP") ? 1 : 0, 4, st));
+        if (test_giveup) HIP_TRY(hipMemsetAsync(b->mt_giveup, 1, 4, st));
         b->mt_checked = false;
     }
-    if (b->redo.n > 0) HIP_TRY(hipMemsetAsync(b->redo.p, 0, b->redo.n * 4, st));
     if (b->q_words_n > 0) {
-        // the sweeps in quanta: tickets and arrival counters start at 0; the give-up word too (NRA_TEST_MT_GIVEUP: set)
-        HIP_TRY(hipMemsetAsync(b->q_words.p, 0, b->q_words_n * 4, st));
-        if (getenv("NRA_TEST_MT_GIVEUP")) HIP_TRY(hipMemsetAsync(b->q_words.p, 1, 4, st));
+        if (test_giveup) HIP_TRY(hipMemsetAsync(b->q_words.p, 1, 4, st));
         b->q_checked = false;
     }
     int ev = 2;
@@ -1654,7 +1719,7 @@ static int run_1d(nra_batch* b)
                                                            b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p,
                                                            b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p,
                                                            b->mt_strips.p + bk.strip_off * 5 * (size_t)b->chain_cap, b->chain_cap,
-                                                           next_epoch(), b->mt_words.p));
+                                                           next_epoch(), b->mt_giveup));
             } else if (bk.ring && bk.chain)
                 LAUNCH_TRY(nra_launch_sweep_ringchain_bwd(bk.R, b->has_n, bk.wide ? 1 : 0, q, bk.n_sweep,
                                                           b->sweep_tasks.p + bk.sweep_off, b->reads.p, b->regions.p, b->pool.p,
@@ -1684,7 +1749,7 @@ static int run_1d(nra_batch* b)
                                                            b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p, b->cand_score.p,
                                                            b->cand_flag.p,
                                                            b->mt_strips.p + bk.strip_off * 5 * (size_t)b->chain_cap, b->chain_cap,
-                                                           next_epoch(), b->mt_words.p));
+                                                           next_epoch(), b->mt_giveup));
             } else if (bk.ring && bk.chain)
                 LAUNCH_TRY(nra_launch_sweep_ringchain_fwd(bk.R, b->has_n, bk.wide ? 1 : 0, q, bk.n_sweep,
                                                           b->sweep_tasks.p + bk.sweep_off, b->reads.p, b->regions.p, b->pool.p,
@@ -1733,7 +1798,8 @@ static int run_1d(nra_batch* b)
     const int append_mode = all_ext ? 0 : ((b->brute || tie_ext) ? 2 : 1);
     LAUNCH_TRY(nra_launch_select_best_1d(st, b->n_reads, b->kmin.p, b->kmax.p, b->coff.p, b->cand_score.p,
                                          b->cand_flag.p, b->read_bucket.p, b->bucket_task_base.p, append_mode,
-                                         b->queue_tasks.p, b->tie_count.p, b->best_score.p));
+                                         b->queue_tasks.p, b->tie_count.p, b->best_score.p,
+                                         clear_extents ? nullptr : b->cand_tstart.p, clear_extents ? nullptr : b->cand_tend.p));
     if (!all_ext) {
         for (size_t i = 0; i < nb; ++i) {
             const Bucket& bk = b->buckets[i];
@@ -1752,7 +1818,9 @@ static int run_1d(nra_batch* b)
     }
     LAUNCH_TRY(nra_launch_select_final_1d(st, b->n_reads, b->kmin.p, b->kmax.p, b->coff.p, b->reads.p,
                                           b->regions.p, b->cand_score.p, b->cand_flag.p, b->cand_tstart.p,
-                                          b->cand_tend.p, b->best_score.p, b->sum_k.p, b->n_ties.p, b->status.p));
+                                          b->cand_tend.p, b->best_score.p, b->sum_k.p, b->n_ties.p, b->status.p,
+                                          b->q_words_n > 0 ? b->q_words.p : nullptr,
+                                          b->chain_blocks.n > 0 ? b->mt_giveup : nullptr, b->giveup_out));
     HIP_TRY(hipEventRecord(b->ev[1], st));
     return NRA_OK;
 }
@@ -1769,11 +1837,31 @@ static int check_mt(nra_batch* b)
     }
     if (b->mt_checked || b->chain_blocks.n == 0) return NRA_OK;
     int32_t failed = 0;
-    HIP_TRY(hipMemcpy(&failed, b->mt_words.p, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&failed, b->mt_giveup, 4, hipMemcpyDeviceToHost));
     b->mt_checked = true;
     if (failed) return fail(NRA_E_DEVICE, "chained sweep: a row block timed out waiting for the block above it");
     return NRA_OK;
 }
+
+// The same after a run of a 1D batch with reads, without a copy of its own: k_select_final_1d, the run's last kernel, left
+// both give-up words behind the per-read results, and one copy brings the whole block to the pinned mirror.  The stream is
+// idle.  nra_batch_sync stages the block and nra_batch1d_fetch finds it there; a fetch without a sync stages it itself.
+static int stage_results_1d(nra_batch* b)
+{
+    if (!b->results_staged) {
+        const int rc = fetch_results(b);
+        if (rc) return rc;
+        b->results_staged = true;
+    }
+    if (!b->ran) return NRA_OK;                             // (no run yet: nothing has written the words)
+    int32_t words[2];
+    memcpy(words, static_cast<const uint8_t*>(b->result_stage) + (reinterpret_cast<const uint8_t*>(b->giveup_out) - b->result_block.p), 8);
+    b->q_checked = true; b->mt_checked = true;
+    if (words[0]) return fail(NRA_E_DEVICE, "sweep in quanta: a second part timed out waiting for its reverse sweep / first part");
+    if (words[1]) return fail(NRA_E_DEVICE, "chained sweep: a row block timed out waiting for the block above it");
+    return NRA_OK;
+}
+static bool one_copy_1d(const nra_batch* b) { return NRA_FETCH_ONE_COPY != 0 && b->kind == 1 && b->n_reads > 0 && b->giveup_out; }
 
 int nra_batch1d_fetch(nra_batch_t* b, int32_t* best_score, int64_t* sum_k, int32_t* n_ties,
                       uint8_t* status, int32_t* cand_score, int32_t* cand_tstart, int32_t* cand_tend)
@@ -1782,7 +1870,7 @@ int nra_batch1d_fetch(nra_batch_t* b, int32_t* best_score, int64_t* sum_k, int32
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipStreamSynchronize(b->stream));
     {
-        const int rcm = check_mt(b);
+        const int rcm = one_copy_1d(b) ? stage_results_1d(b) : check_mt(b);
         if (rcm) return rcm;
     }
     // (after a refinement the per-cell arrays are the refinement's: (2 buf1)(2 buf2) entries a read)
@@ -1790,8 +1878,10 @@ int nra_batch1d_fetch(nra_batch_t* b, int32_t* best_score, int64_t* sum_k, int32
     const int32_t* src_score = b->refined ? b->rf_cell_score.p : b->cand_score.p;
     const int32_t* src_wscore = b->refined ? b->rf_cell_wscore.p : b->cand_tstart.p;
     if (n) {
-        int rc = fetch_results(b);
-        if (rc) return rc;
+        if (!one_copy_1d(b)) {
+            int rc = fetch_results(b);
+            if (rc) return rc;
+        }
         if (best_score) memcpy(best_score, staged(b, b->best_score), n * 4);
         if (sum_k) memcpy(sum_k, staged(b, b->sum_k), n * 8);
         if (n_ties) memcpy(n_ties, staged(b, b->n_ties), n * 4);
@@ -3783,7 +3873,7 @@ int nra_batch_sync(nra_batch_t* b)
     HIP_TRY(hipStreamSynchronize(b->stream));
     const int rc = account_run(b);
     if (rc || b->kind != 1) return rc;
-    return check_mt(b);
+    return one_copy_1d(b) ? stage_results_1d(b) : check_mt(b);
 }
 
 int nra_batch1d_resweeps(nra_batch_t* b, int64_t* tasks, int64_t* reads, int64_t* tasks_total, int64_t* reads_total)
@@ -3808,6 +3898,14 @@ int nra_batch1d_resweeps(nra_batch_t* b, int64_t* tasks, int64_t* reads, int64_t
     if (reads) *reads = nr;
     if (tasks_total) *tasks_total = tt;
     if (reads_total) *reads_total = tr;
+    return NRA_OK;
+}
+
+int nra_batch1d_clears(nra_batch_t* b, int32_t* scores, int32_t* extents)
+{
+    if (!b || b->kind != 1) return fail(NRA_E_ARG, "nra_batch1d_clears needs a 1D batch");
+    if (scores) *scores = clears_scores_1d(b) ? 1 : 0;
+    if (extents) *extents = clears_extents_1d(b) ? 1 : 0;
     return NRA_OK;
 }
 

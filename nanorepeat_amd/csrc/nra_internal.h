@@ -525,8 +525,20 @@ int nra_launch_sweep_ring_fwd(int R, int has_n, int half, hipStream_t st, int n_
                               int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo);
 // relax_c > 0 (these and the quanta launcher): the taint scheme -- the anchor columns up to
 // relax_c bases from the junction run the relaxed cell, and redo[task] is set where that may have reached an output;
-// relax_c <= 0 and redo non-null: the exact sweeps of the flagged tasks only (the re-sweep); both 0 / null: the exact sweeps
+// relax_c <= 0 and redo non-null: the exact sweeps of the flagged tasks only (the re-sweep); both 0 / null: the exact sweeps.
+// The switch step is flank - max(relax_c, 64) itself, where that is >= 64 (sweep_relax_steps): no multiple of anything.
 #define NRA_RELAX_C_DEFAULT 256
+
+// The lean run, one switch per item so that each can be measured by itself (-DNRA_...=0: as before it):
+#ifndef NRA_RELAX_ROUND64
+#define NRA_RELAX_ROUND64 0      // 1: the switch step rounded down to a multiple of 64, as before
+#endif
+#ifndef NRA_LEAN_CLEARS
+#define NRA_LEAN_CLEARS 1        // no per-run clear of an array that a kernel of the run writes in full (run_1d)
+#endif
+#ifndef NRA_FETCH_ONE_COPY
+#define NRA_FETCH_ONE_COPY 1     // the give-up words travel in the result block: no blocking copy of their own
+#endif
 
 // a bucket's reverse and forward sweeps as one launch of quanta taken by ticket (k_sweep_ringq).  A sweep is cut every
 // `qsteps` steps (a multiple of 64; a forward sweep also at NRA_Q_CUT of its first boundary step) into parts; qlist holds one entry per part, direction << 31 | part << NRA_Q_PART_SHIFT |
@@ -664,19 +676,24 @@ int nra_launch_trace_fill_mt(int R, int has_n, int wide, hipStream_t st, int n_b
 int nra_launch_trace_best(hipStream_t st, int n_tasks, const NraTraceTask* tasks, const NraDevRead* reads,
                           int block_rows, int wide, const int32_t* blk_best, NraScoreParams sp, int32_t* out);
 
-// 1D selectors (one wave per read).  append_mode: 0 none, 1 ambiguous ties only, 2 every tie
+// 1D selectors (one wave per read).  append_mode: 0 none, 1 ambiguous ties only, 2 every tie.  cand_tstart / cand_tend
+// non-null: every candidate's extents are set to -1 ("not computed") on the way -- the extents kernel, which runs behind
+// this one, overwrites those of the ties it resolves (null: it has run already, NRA_F_ALL_EXTENTS).
+// q_giveup / mt_giveup (either may be null) -> giveup_out[0 / 1]: the give-up words of the run's quanta and row blocks,
+// copied by the run's last kernel into the result block, so that a fetch needs no copy of their own for them
 int nra_launch_select_best_1d(hipStream_t st, int n_reads, const int32_t* kmin, const int32_t* kmax,
                               const uint32_t* coff, const int32_t* cand_score, const uint8_t* cand_flag,
                               const int32_t* read_bucket, const uint32_t* bucket_task_base,
                               int append_mode, NraTask* ext_tasks, int32_t* ext_count,
-                              int32_t* best_score);
+                              int32_t* best_score, int32_t* cand_tstart, int32_t* cand_tend);
 int nra_launch_select_final_1d(hipStream_t st, int n_reads, const int32_t* kmin, const int32_t* kmax,
                                const uint32_t* coff, const NraDevRead* reads,
                                const NraDevRegion* regions,
                                const int32_t* cand_score, const uint8_t* cand_flag,
                                const int32_t* cand_tstart, const int32_t* cand_tend,
                                const int32_t* best_score,
-                               int64_t* sum_k, int32_t* n_ties, uint8_t* status);
+                               int64_t* sum_k, int32_t* n_ties, uint8_t* status,
+                               const int32_t* q_giveup, const int32_t* mt_giveup, int32_t* giveup_out);
 // 2D: strand choice from the probe scores, then the per-read selector over its cells
 int nra_launch_pick_strand(hipStream_t st, int n_reads, const int32_t* probe_score,
                            const int8_t* strand_in, int8_t* strand_out, NraDevRead* reads);

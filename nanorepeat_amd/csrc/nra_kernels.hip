@@ -353,7 +353,9 @@ __global__ __launch_bounds__(WAVE) void k_select_best_1d(int n_reads, const int3
                                                         const uint32_t* __restrict__ bucket_task_base,
                                                         int append_mode, NraTask* __restrict__ ext_tasks,
                                                         int32_t* __restrict__ ext_count,
-                                                        int32_t* __restrict__ best_score)
+                                                        int32_t* __restrict__ best_score,
+                                                        int32_t* __restrict__ cand_tstart,
+                                                        int32_t* __restrict__ cand_tend)
 {
     const int r = blockIdx.x, lane = threadIdx.x;
     if (r >= n_reads) return;
@@ -361,7 +363,11 @@ __global__ __launch_bounds__(WAVE) void k_select_best_1d(int n_reads, const int3
     if (K <= 0) { if (lane == 0) best_score[r] = -1; return; }
     const uint32_t base = coff[r];
     int best = -1;
-    for (int c = lane; c < K; c += WAVE) best = imax(best, cand_score[base + c]);
+    for (int c = lane; c < K; c += WAVE) {
+        best = imax(best, cand_score[base + c]);
+        // "no extents computed": this wave visits every candidate of the read anyway, and the extents kernel runs behind it
+        if (cand_tstart) { cand_tstart[base + c] = -1; cand_tend[base + c] = -1; }
+    }
     best = wave_max(best);
     if (lane == 0) best_score[r] = best;
     if (!append_mode || best < 0) return;
@@ -390,10 +396,17 @@ __global__ __launch_bounds__(WAVE) void k_select_final_1d(int n_reads, const int
                                                          const int32_t* __restrict__ best_score,
                                                          int64_t* __restrict__ sum_k,
                                                          int32_t* __restrict__ n_ties,
-                                                         uint8_t* __restrict__ status)
+                                                         uint8_t* __restrict__ status,
+                                                         const int32_t* q_giveup, const int32_t* mt_giveup,
+                                                         int32_t* __restrict__ giveup_out)
 {
     const int r = blockIdx.x, lane = threadIdx.x;
     if (r >= n_reads) return;
+    // the last kernel of a run: every sweep is over, the give-up words are final
+    if (r == 0 && lane == 0 && giveup_out) {
+        giveup_out[0] = q_giveup ? *q_giveup : 0;
+        giveup_out[1] = mt_giveup ? *mt_giveup : 0;
+    }
     const int k0 = kmin[r], K = kmax[r] - k0 + 1;
     if (K <= 0) { if (lane == 0) { sum_k[r] = 0; n_ties[r] = 0; status[r] = 3; } return; }
     const int best = best_score[r];
@@ -567,11 +580,12 @@ extern "C" int nra_launch_select_best_1d(hipStream_t st, int n_reads, const int3
                                          const uint8_t* cand_flag,
                                          const int32_t* read_bucket, const uint32_t* bucket_task_base,
                                          int append_mode, NraTask* ext_tasks, int32_t* ext_count,
-                                         int32_t* best_score)
+                                         int32_t* best_score, int32_t* cand_tstart, int32_t* cand_tend)
 {
     if (n_reads <= 0) return 0;
     k_select_best_1d<<<n_reads, WAVE, 0, st>>>(n_reads, kmin, kmax, coff, cand_score, cand_flag, read_bucket,
-                                               bucket_task_base, append_mode, ext_tasks, ext_count, best_score);
+                                               bucket_task_base, append_mode, ext_tasks, ext_count, best_score,
+                                               cand_tstart, cand_tend);
     return (int)hipGetLastError();
 }
 
@@ -581,11 +595,13 @@ extern "C" int nra_launch_select_final_1d(hipStream_t st, int n_reads, const int
                                           const uint8_t* cand_flag,
                                           const int32_t* cand_tstart, const int32_t* cand_tend,
                                           const int32_t* best_score, int64_t* sum_k, int32_t* n_ties,
-                                          uint8_t* status)
+                                          uint8_t* status, const int32_t* q_giveup, const int32_t* mt_giveup,
+                                          int32_t* giveup_out)
 {
     if (n_reads <= 0) return 0;
     k_select_final_1d<<<n_reads, WAVE, 0, st>>>(n_reads, kmin, kmax, coff, reads, regions, cand_score, cand_flag,
-                                                cand_tstart, cand_tend, best_score, sum_k, n_ties, status);
+                                                cand_tstart, cand_tend, best_score, sum_k, n_ties, status,
+                                                q_giveup, mt_giveup, giveup_out);
     return (int)hipGetLastError();
 }
 

@@ -516,13 +516,19 @@ __device__ __forceinline__ SweepCounters sweep_counters_at(int s, int jfirst, in
 
 // The taint scheme (TAINT): cells hold 4 * score + 2 * taint + origin.  Steps [0, s_relax) of a sweep run
 // the relaxed cell (nra_pk16.h), whose every value is a tainted upper bound; from step s_relax on the exact cell runs,
-// seeded from the relaxed states.  s_relax is a multiple of 64 at or below flank - c (c: the host's margin, >= 64), the
-// same for every lane: lane l is exact from column s_relax - skew * l on.  0: no relaxed step (the anchor is too short).
+// seeded from the relaxed states.  s_relax = flank - c (c: the host's margin, >= 64), any step, not only a cut of the
+// quanta or a start of a block of columns: the relaxed loop ends at any step, a part that straddles s_relax runs both
+// loops, and slot, pcnt and the column tables go by the step number.  It is the same for every lane: lane l is exact
+// from column s_relax - skew * l on.  0: no relaxed step (fewer than 64 of them: the anchor is too short).
 __device__ __forceinline__ int sweep_relax_steps(int flank, int c)
 {
     if (c <= 0) return 0;
     const int t = flank - (c < 64 ? 64 : c);
+#if NRA_RELAX_ROUND64
     return t >= 64 ? t / 64 * 64 : 0;
+#else
+    return t >= 64 ? t : 0;
+#endif
 }
 // the switch to the exact cell: E2 := E (E_r >= E1, E2), Hq2 := Hq - (o2 - o1) (H_r - o2 >= H - o2); F2 arrives as F on the ring
 template <int R>
