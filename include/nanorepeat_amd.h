@@ -383,11 +383,14 @@ typedef struct nra_screen_stats {
     int64_t n_masked_max_occ;  /* distinct k-mers in more than max_occ sets, left out */
     int64_t n_empty_regions;   /* regions both of whose sets are empty: every read passes them */
     int64_t index_bytes;       /* device bytes of the table and the postings */
-    int64_t bases_screened;    /* read bases over every nra_screen_reads call */
-    int64_t n_calls;           /* nra_screen_reads calls that succeeded */
+    int64_t bases_screened;    /* read bases over every nra_screen_reads / _partial call */
+    int64_t n_calls;           /* nra_screen_reads / _partial calls that succeeded */
     double  build_ms;          /* host time of the index build in nra_screen_create */
     double  kernel_ms;         /* screen kernels of the last call (HIP events) */
     double  sum_kernel_ms;     /* ... summed over n_calls */
+    int64_t n_classes;         /* motif classes of the last nra_screen_set_motifs (0 without one) */
+    double  motif_kernel_ms;   /* k_screen_motifs of the last nra_screen_reads_partial call (HIP events) */
+    double  sum_motif_kernel_ms; /* ... summed over the nra_screen_reads_partial calls */
 } nra_screen_stats_t;
 
 /* anchors 2g / 2g+1 = left / right anchor of region g: bytes [anchor_off[i], anchor_off[i+1]) of `anchors`
@@ -404,6 +407,41 @@ int nra_screen_reads(nra_screen_t* s, int32_t n_reads, const char* seqs, const i
                      int32_t* hits_left, int32_t* hits_right);
 int nra_screen_stats(const nra_screen_t* s, nra_screen_stats_t* st);
 int nra_screen_destroy(nra_screen_t* s);
+
+/* ---- motif screen: one-anchor and in-repeat reads (additive, ABI 4) ----
+ *
+ * Windows, code, canon, K(g, s) and c(r, g, s) are those above.
+ * Motif classes.  The root of a motif (upper-cased ACGT) is its shortest word w with motif = w^j.  Two roots are in
+ * one class when one is a rotation of the other or of its reverse complement.  A region whose root is longer than 6
+ * bases has no class: class_of[g] = -1, which is not an error.
+ * Periodic windows.  A valid k-window w has period q when w[i] == w[i+q] for all i < k - q.  Its smallest period p in
+ * 1..6, if any, makes it a window of the class of w[0:p] (w[0:p] is then primitive).  m(r, C) = the window positions
+ * of read r that are windows of class C.  W(r) = max(0, len(r) - k + 1) counts every position, valid or not.
+ * Pairs.  pass(s): |K(g,s)| > 0 and c(r,g,s) >= min(min_hits, |K(g,s)|).  nra_screen_reads_partial returns, sorted by
+ * read then region, every pair (r, g) of one of four kinds:
+ *   0  both anchors  exactly the pairs nra_screen_reads returns for the same arguments (regions with empty sets
+ *                    included)
+ *   1  left only     pass(left), the right set is not empty, and not pass(right)
+ *   2  right only    pass(right), the left set is not empty, and not pass(left)
+ *   3  in repeat     none of the above, class_of[g] >= 0, W(r) >= 1 and
+ *                    m(r, class_of[g]) >= max(min_hits, ceil(motif_share_pct * W(r) / 100))
+ * Every pair carries hits_left = c(r,g,left), hits_right = c(r,g,right) and motif_windows = m(r, class_of[g]), 0
+ * without a class. */
+
+/* The motif of region g = bytes [motif_off[g], motif_off[g+1]) of `motifs`; n_regions must equal the handle's.  An
+ * empty motif or a byte other than ACGT (either case) is NRA_E_ARG, a motif over 64 bases NRA_E_RANGE.  Builds the
+ * class table on the host and keeps it on the device: 5460 uint16 entries (class + 1, or 0) at off[p] + code(p-mer),
+ * off[p] = 4 + ... + 4^(p-1), every rotation of every class root and of its reverse complement filled in.  A second
+ * call replaces the first. */
+int nra_screen_set_motifs(nra_screen_t* s, int32_t n_regions, const char* motifs, const int64_t* motif_off);
+/* nra_screen_reads with the four kinds above; min_hits >= 1, motif_share_pct in 1..100 (else NRA_E_ARG).  The capacity
+ * protocol is nra_screen_reads': *n_pairs is the capacity of the six arrays on entry and the number of pairs on return;
+ * too small a capacity writes nothing, leaves the number needed in *n_pairs and returns NRA_E_RANGE.  Without motifs
+ * set no pair is of kind 3.  One upload of the reads serves the anchor and the motif kernel. */
+int nra_screen_reads_partial(nra_screen_t* s, int32_t n_reads, const char* seqs, const int64_t* seq_off,
+                             int32_t min_hits, int32_t motif_share_pct, int64_t* n_pairs,
+                             int32_t* pair_read, int32_t* pair_region, int32_t* hits_left, int32_t* hits_right,
+                             int32_t* motif_windows, uint8_t* kind);
 
 /* ---- repeat structure: what a read's tract is made of (no counterpart in the reference) ---------------------------
  *

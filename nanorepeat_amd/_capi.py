@@ -36,6 +36,7 @@ EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count
            "nra_batch2d_create", "nra_batch2d_create_reads", "nra_batch2d_set_cells", "nra_joint_grid_cells", "nra_batch2d_set_grid", "nra_batch2d_invalidate", "nra_batch2d_sweep_flanks", "nra_batch2d_refine", "nra_batch_run", "nra_batch_sync", "nra_batch_stats",
            "nra_batch1d_fetch", "nra_batch1d_resweeps", "nra_batch1d_clears", "nra_batch2d_fetch", "nra_batch_destroy",
            "nra_screen_create", "nra_screen_reads", "nra_screen_stats", "nra_screen_destroy",
+           "nra_screen_set_motifs", "nra_screen_reads_partial",
            "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts", "nra_mixture_fit",
            "nra_tract_consensus", "nra_allele_split", "nra_tract_segments", "nra_tract_periods")
 
@@ -86,7 +87,8 @@ class Stats(C.Structure):
 class ScreenStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_keys", "n_postings", "n_masked_periodic", "n_masked_max_occ",
                                          "n_empty_regions", "index_bytes", "bases_screened", "n_calls")] + \
-               [(n, C.c_double) for n in ("build_ms", "kernel_ms", "sum_kernel_ms")]
+               [(n, C.c_double) for n in ("build_ms", "kernel_ms", "sum_kernel_ms")] + \
+               [("n_classes", C.c_int64), ("motif_kernel_ms", C.c_double), ("sum_motif_kernel_ms", C.c_double)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -173,6 +175,11 @@ def load():
     lib.nra_screen_create.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, C.c_int32, C.c_int32, C.POINTER(vp)]
     lib.nra_screen_reads.restype = C.c_int
     lib.nra_screen_reads.argtypes = [vp, C.c_int32, C.c_char_p, pi64, C.c_int32, pi64, pi32, pi32, pi32, pi32]
+    lib.nra_screen_set_motifs.restype = C.c_int
+    lib.nra_screen_set_motifs.argtypes = [vp, C.c_int32, C.c_char_p, pi64]
+    lib.nra_screen_reads_partial.restype = C.c_int
+    lib.nra_screen_reads_partial.argtypes = [vp, C.c_int32, C.c_char_p, pi64, C.c_int32, C.c_int32, pi64, pi32, pi32,
+                                             pi32, pi32, pi32, p8]
     lib.nra_screen_stats.restype = C.c_int
     lib.nra_screen_stats.argtypes = [vp, C.POINTER(ScreenStats)]
     lib.nra_screen_destroy.restype = C.c_int
@@ -656,6 +663,36 @@ def screen_reads(handle, reads, min_hits=4, capacity=None):
         n_pairs = C.c_int64(capacity)
         rc = lib.nra_screen_reads(handle, n, seqs, _ptr(off, C.c_int64), min_hits, C.byref(n_pairs),
                                   *(_ptr(out[key], C.c_int32) for key in ("read", "region", "hits_left", "hits_right")))
+        if rc == E_RANGE and n_pairs.value > capacity:
+            capacity = int(n_pairs.value)
+            continue
+        _check(rc)
+        return {key: v[:n_pairs.value] for key, v in out.items()}
+
+
+def screen_set_motifs(handle, motifs):
+    """nra_screen_set_motifs: one motif per region of the handle (a second call replaces the first)."""
+    data, off = pack_reads(list(motifs))
+    _check(load().nra_screen_set_motifs(handle, len(motifs), data, _ptr(off, C.c_int64)))
+
+
+def screen_reads_partial(handle, reads, min_hits=4, motif_share_pct=5, capacity=None):
+    """nra_screen_reads_partial -> dict(read, region, hits_left, hits_right, motif_windows, kind) of the pairs of the
+    four kinds (0 both anchors, 1 left only, 2 right only, 3 in repeat), sorted by read then region.  When the pairs
+    exceed `capacity`, the call is repeated once with the capacity the library asked for."""
+    lib = load()
+    seqs, off = pack_reads(reads)
+    n = len(reads)
+    if capacity is None:
+        capacity = n * (8 + screen_stats(handle)["n_empty_regions"]) + 1024
+    keys = ("read", "region", "hits_left", "hits_right", "motif_windows")
+    while True:
+        out = {key: np.zeros(capacity, np.int32) for key in keys}
+        out["kind"] = np.zeros(capacity, np.uint8)
+        n_pairs = C.c_int64(capacity)
+        rc = lib.nra_screen_reads_partial(handle, n, seqs, _ptr(off, C.c_int64), min_hits, motif_share_pct,
+                                          C.byref(n_pairs), *(_ptr(out[key], C.c_int32) for key in keys),
+                                          _ptr(out["kind"], C.c_uint8))
         if rc == E_RANGE and n_pairs.value > capacity:
             capacity = int(n_pairs.value)
             continue

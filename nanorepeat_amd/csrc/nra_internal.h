@@ -216,6 +216,13 @@ struct NraScreenEntry {
     int32_t read, set, count;
 };
 
+// Motif screen (nra_screen_motifs.hip): the class table is indexed directly with NRA_MOTIF_TAB_OFF(p) + code(p-mer) for
+// p = 1..NRA_MOTIF_MAX_ROOT; an entry is class + 1, or 0.  Its entries are NraScreenEntry with the class in `set`.
+#define NRA_MOTIF_MAX_ROOT 6
+#define NRA_MOTIF_TAB_OFF(p) (((1u << (2 * (p))) - 4u) / 3u)           // 4 + 16 + ... + 4^(p-1)
+#define NRA_MOTIF_TAB_ENTRIES (NRA_MOTIF_TAB_OFF(NRA_MOTIF_MAX_ROOT) + (1u << (2 * NRA_MOTIF_MAX_ROOT)))   // 5460
+#define NRA_MOTIF_MAX_LEN 64
+
 // Repeat structure (nra_structure.hip, nra_structure_host.cpp): the wraparound edit-distance alignment of a read's tract
 // against its motif repeated without end, one lane per read.  A launch takes reads of one phase
 // capacity P (motif length p <= P), sorted by tract length, descending, 64 to a wave.
@@ -436,6 +443,10 @@ int nra_launch_mixture(hipStream_t st, int d, int kreg, int n, const int32_t* fi
 int nra_launch_screen_hits(hipStream_t st, int64_t n_tiles, const NraScreenTile* tiles, const uint8_t* seqs, int k,
                            const uint64_t* table, int log2_slots, const uint32_t* postings, NraScreenEntry* entries,
                            unsigned long long cap, unsigned long long* count);
+// motif screen (nra_screen_motifs.hip): the same tiles and chunk copy; entries and *count as above, `set` = class
+int nra_launch_screen_motifs(hipStream_t st, int64_t n_tiles, const NraScreenTile* tiles, const uint8_t* seqs, int k,
+                             const uint16_t* class_tab, NraScreenEntry* entries, unsigned long long cap,
+                             unsigned long long* count);
 
 // repeat structure (nra_structure.hip): one lane per read, forward DP then traceback.  P in {1..6, 8, 16, 32, 64};
 // res[2 i] = edits, res[2 i + 1] = start phase of read i

@@ -172,7 +172,8 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
                       num_cpu=1, device=0, scoring=None, seed=None, read_structure=False, discover_motifs=False,
                       min_motif_count=4, min_motif_share=0.1, partial_reads=False, mixture="sklearn",
                       allele_consensus=False, allele_split=False, motif_runs=False, segment_motifs=None,
-                      switch_cost=None, read_alignments=False, discover_periods=False, **engines):
+                      switch_cost=None, read_alignments=False, discover_periods=False, in_repeat_reads=False,
+                      **engines):
     """The BAM command from files to files (nanoRepeat_bam.py:614-751): for every region of the BED
     file, reads from the alignment file -> `<out_prefix>.details/<chr>/<region>.*` ->
     `<out_prefix>.NanoRepeat_output.tsv`.  The reference forks up to 16 workers, one region each;
@@ -191,7 +192,9 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
     default of segments.py).  read_alignments=True adds `<region>.round3.paf` (alignments.py): the alignment of every
     read with a round-3 size of its own to the template it was called at.  discover_periods=True adds the tandem
     period files (periods.py): the period (up to 64 bases) and the unit of every allele's consensus tract, every read's
-    evidence for it, and the reads' sizes in that unit where it is not the BED motif.
+    evidence for it, and the reads' sizes in that unit where it is not the BED motif.  in_repeat_reads=True adds the
+    in-repeat read files (partial.py): for every read of the region's window without a hit of either anchor, the repeat
+    units it shows, and per region whether any such read shows more than the largest spanning read.
     `engines` may carry aligner / scorer / structure_engine / motif_engine / extension_engine / mixture_engine /
     consensus_engine / split_engine / segment_engine / path_aligner / period_engine stand-ins.  Returns the regions."""
     from . import bam as nr_bam, mixture as nr_mixture
@@ -213,7 +216,8 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
                         read_structure, _motif_options(discover_motifs, min_motif_count, min_motif_share),
                         partial_reads, mixture, allele_consensus, allele_split,
-                        _run_options(motif_runs, segment_motifs, switch_cost), read_alignments, discover_periods)
+                        _run_options(motif_runs, segment_motifs, switch_cost), read_alignments, discover_periods,
+                        in_repeat_reads=in_repeat_reads)
     return regions
 
 
@@ -240,7 +244,7 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
                         read_structure=False, motif_options=None, partial_reads=False, mixture="sklearn",
                         allele_consensus=False, allele_split=False, run_options=None, read_alignments=False,
-                        discover_periods=False):
+                        discover_periods=False, in_repeat_reads=False, candidates=None):
     """The commands' common tail: steps 1-4 for the regions with reads, then one TSV row per BED region; with
     read_structure, the structure of every read with a size and the two structure files; with motif_options (a dict
     of motifs.motif_regions keywords), the tandem motifs of every read with a core and the two motif files; with
@@ -252,7 +256,13 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
     of every allele's consensus, the two run files and one NOTICE counting the alleles of more than one run; with
     read_alignments, the round-3 alignment of every read with a size of its own, one file per region and a NOTICE per
     region that left reads out; with discover_periods, the tandem period of every allele's consensus tract and every
-    read's evidence for it, the two period files and one NOTICE counting the alleles whose unit is not the BED motif."""
+    read's evidence for it, the two period files and one NOTICE counting the alleles whose unit is not the BED motif;
+    with in_repeat_reads, the four extensions of every read without an anchor, the two in-repeat files and a NOTICE per
+    region where such reads show more repeat units than any spanning read.  `candidates` (the FASTQ command, a dict of
+    _place_candidates keywords): the one-anchor and in-repeat reads come from the screen's candidates too."""
+    if in_repeat_reads:
+        for region in live:
+            region.keep_no_anchor_reads = True
     quantify_regions(live, reads_of, data_type, fast_mode, num_cpu, device, scoring,
                      engines.get("aligner"), engines.get("scorer"), keep_candidates=read_alignments and not no_details)
     phase_regions(live, data_type, ploidy, max_mutual_overlap, max_num_components, remove_noisy_reads, seed,
@@ -273,13 +283,26 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
         for region in live:
             motifs.write_read_motifs(region)
         motifs.write_motif_summary(regions, out_prefix)
-    if partial_reads:
+    if partial_reads or in_repeat_reads:
         from . import partial
-        partial.partial_regions(live, reads_of, device=device, scoring=scoring, engine=engines.get("extension_engine"))
-        for region in live:
-            partial.write_partial_reads(region)
-        partial.write_partial_summary(regions, out_prefix)
-        partial.report_exceeding_reads(live)
+        of, of_reads, keep, shared, unscreened = live, reads_of, None, None, ()
+        if candidates is not None:
+            of, of_reads, keep, shared, unscreened = _place_candidates(
+                regions, live, reads_of, data_type, num_cpu, device, scoring, engines.get("aligner"), in_repeat_reads,
+                **candidates)
+        if partial_reads:
+            partial.partial_regions(of, of_reads, device=device, scoring=scoring, engine=engines.get("extension_engine"))
+            for region in of:
+                partial.write_partial_reads(region)
+            partial.write_partial_summary(regions, out_prefix)
+            partial.report_exceeding_reads(of)
+        if in_repeat_reads:
+            partial.in_repeat_regions(of, of_reads, device=device, scoring=scoring,
+                                      engine=engines.get("extension_engine"), keep=keep)
+            for region in of:
+                partial.write_in_repeat_reads(region)
+            partial.write_in_repeat_summary(regions, out_prefix, shared, unscreened)
+            partial.report_exceeding_in_repeat_reads(of)
     if allele_consensus:
         from . import consensus
         consensus.consensus_regions(live, device=device, engine=engines.get("consensus_engine"),
@@ -335,7 +358,8 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         chunk_bases=1 << 28, read_structure=False, discover_motifs=False, min_motif_count=4,
                         min_motif_share=0.1, mixture="sklearn", allele_consensus=False, allele_split=False,
                         motif_runs=False, segment_motifs=None, switch_cost=None, read_alignments=False,
-                        discover_periods=False, **engines):
+                        discover_periods=False, partial_reads=False, in_repeat_reads=False, motif_share_pct=5,
+                        **engines):
     """The FASTQ / FASTA command (nanoRepeat.py:109, `-t fastq|fasta`) from files to files, without a genome mapper:
     the reads each region sees are chosen by the anchor k-mer screen (screen.reads_by_region) instead of a
     genome-wide mapping and a BAM window, then the BAM command's steps run unchanged.  Every region's reference
@@ -347,9 +371,14 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
     allele_consensus=True adds the consensus sequence of every allele's tract (consensus.py); allele_split=True adds
     the allele split files (split.py); motif_runs=True adds the motif run files (segments.py; segment_motifs and
     switch_cost as for quantify_from_bam); read_alignments=True adds the round-3 alignment files (alignments.py);
-    discover_periods=True adds the tandem period files (periods.py).
-    `engines` may carry aligner / scorer / screener / structure_engine / motif_engine / mixture_engine /
-    consensus_engine / split_engine / segment_engine / path_aligner / period_engine stand-ins.  Returns the regions."""
+    discover_periods=True adds the tandem period files (periods.py).  partial_reads=True adds the one-anchor read files
+    and in_repeat_reads=True the in-repeat read files, as for quantify_from_bam: the motif screen (DESIGN.md section
+    23) offers the reads with one anchor only and the reads made of a region's motif (at least motif_share_pct % of
+    their k-mer windows) as candidates, written to `<region>.partial_candidates.fastq`; they go through the anchor step
+    apart from the region's reads and never reach the sizes or the phasing.
+    `engines` may carry aligner / scorer / screener / structure_engine / motif_engine / extension_engine /
+    mixture_engine / consensus_engine / split_engine / segment_engine / path_aligner / period_engine stand-ins.
+    Returns the regions."""
     from . import screen as nr_screen, mixture as nr_mixture
     nr_mixture.check_engine_name(mixture)
     regions = nr_io.read_repeat_region_file(repeat_region_bed, no_details)
@@ -360,11 +389,21 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
         nr_io.extract_ref_sequence(ref_fasta_dict, region, anchor_len)
         if no_check_repeat_motif_in_ref or nr_io.check_repeat_motif_in_ref(region):
             screened.append(region)
+    with_candidates = partial_reads or in_repeat_reads
     if screen:
         found = nr_screen.reads_by_region(in_reads, screened, k=k, max_occ=max_occ, min_hits=min_hits,
-                                          chunk_bases=chunk_bases, device=device, screener=engines.get("screener"))
+                                          chunk_bases=chunk_bases, device=device, screener=engines.get("screener"),
+                                          **(dict(partial=True, motif_share_pct=motif_share_pct) if with_candidates
+                                             else {}))
     else:
-        found = nr_screen.all_reads_by_region(in_reads, len(screened), chunk_bases)
+        found = nr_screen.all_reads_by_region(in_reads, len(screened), chunk_bases,
+                                              **(dict(partial=True) if with_candidates else {}))
+    candidates = None
+    if with_candidates:
+        found, offered = found
+        candidates = dict(offered={id(region): {n: c for n, c in cand.items() if n not in reads}
+                                   for region, reads, cand in zip(screened, found, offered)},
+                          k=k, min_hits=min_hits, motif_share_pct=motif_share_pct)
     found_of = {id(region): reads for region, reads in zip(screened, found)}
     live, reads_of = [], []
     for region in regions:
@@ -378,8 +417,71 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         read_structure, _motif_options(discover_motifs, min_motif_count, min_motif_share),
                         mixture=mixture, allele_consensus=allele_consensus, allele_split=allele_split,
                         run_options=_run_options(motif_runs, segment_motifs, switch_cost),
-                        read_alignments=read_alignments, discover_periods=discover_periods)
+                        read_alignments=read_alignments, discover_periods=discover_periods,
+                        partial_reads=partial_reads, in_repeat_reads=in_repeat_reads, candidates=candidates)
     return regions
+
+
+def _place_candidates(regions, live, reads_of, data_type, num_cpu, device, scoring, aligner, in_repeat_reads, offered,
+                      k, min_hits, motif_share_pct):
+    """The FASTQ command's candidates (`offered[id(region)]` = {name: (seq, qual, kind)}, none of them among the
+    region's own reads) through the anchor step, each region's against a shadow of the region: only the shadow's
+    one_anchor_reads and no_anchor_reads are carried over, so read_dict, the sizes and the phasing never see a
+    candidate.  A candidate the anchor step would place as spanning is ignored; one NOTICE counts them.  Writes
+    `<region>.partial_candidates.fastq`.  Returns (regions with reads or candidates, their {name: sequence}, the
+    in-repeat rule as partial.in_repeat_regions' `keep`, the regions per motif class in BED order, the ids of the
+    regions whose motif has no class)."""
+    import copy
+    import sys
+    from . import screen as nr_screen
+    reads_by_id = {id(region): reads for region, reads in zip(live, reads_of)}
+    shadows, shadow_reads, shadow_at = [], [], {}
+    for region in regions:
+        cand = offered.get(id(region))
+        if cand is None:
+            continue
+        if not region.no_details:
+            _write_region_fastq(f"{region.out_prefix}.partial_candidates.fastq",
+                                {n: (seq, qual) for n, (seq, qual, _) in cand.items()})
+        if cand:
+            shadow = copy.copy(region)
+            shadow.read_dict, shadow.read_core_seq_dict = {}, {}
+            shadow.one_anchor_reads = shadow.no_anchor_reads = shadow.skipped_reads = None
+            shadow.keep_no_anchor_reads = bool(in_repeat_reads)
+            shadow_at[id(region)] = len(shadows)
+            shadows.append(shadow)
+            shadow_reads.append({n: seq for n, (seq, _, _) in cand.items()})
+    upstream.find_anchor_locations_in_reads_many(data_type, shadows, shadow_reads, num_cpu, device=device,
+                                                 scoring=scoring, aligner=aligner)
+    n_spanning = 0
+    of, of_reads = [], []
+    for region in regions:
+        if id(region) not in offered:
+            continue
+        reads = dict(reads_by_id.get(id(region), {}))
+        if id(region) in shadow_at:
+            shadow = shadows[shadow_at[id(region)]]
+            n_spanning += len(shadow.read_dict)
+            for attr in ("one_anchor_reads", "no_anchor_reads"):
+                got = getattr(shadow, attr, None)
+                if got:
+                    setattr(region, attr, {**(getattr(region, attr, None) or {}), **got})
+            reads.update(shadow_reads[shadow_at[id(region)]])
+        if reads:
+            of.append(region); of_reads.append(reads)
+    if n_spanning:
+        print(f"NOTICE: {n_spanning} candidate read(s) hold both anchors by the anchor step though not by the screen: "
+              "they are no partial reads and are left out", file=sys.stderr)
+    classes = [nr_screen.motif_class(region.repeat_unit_seq) for region in regions]
+    shared = [0 if c is None else sum(c == d for d in classes) for c in classes]
+    unscreened = {id(region) for region, c in zip(regions, classes) if c is None}
+    if in_repeat_reads and unscreened:
+        print(f"NOTICE: {len(unscreened)} region(s) have a motif without a class (a root longer than 6 bases, or not "
+              "ACGT): the FASTQ / FASTA command does not look for their in-repeat reads", file=sys.stderr)
+
+    def keep(region, seq):
+        return nr_screen.in_repeat_rule(seq, region.repeat_unit_seq, k, min_hits, motif_share_pct)
+    return of, of_reads, keep, shared, unscreened
 
 
 def _write_region_fastq(path, reads):

@@ -105,6 +105,16 @@ def _record_one_anchor_read(ranked, repeat_region):
             kept[ranked[side][0].qname] = (side, ranked[side][0])
 
 
+def _record_no_anchor_read(repeat_region, name):
+    """A read without a hit of either anchor on either strand may lie wholly inside the repeat.  Only a region that
+    asks (`repeat_region.keep_no_anchor_reads`) keeps its name, on `repeat_region.no_anchor_reads`, for partial.py."""
+    if getattr(repeat_region, "keep_no_anchor_reads", False):
+        kept = getattr(repeat_region, "no_anchor_reads", None)
+        if kept is None:
+            kept = repeat_region.no_anchor_reads = {}
+        kept[name] = True
+
+
 def find_anchor_locations_in_reads(data_type, repeat_region, num_cpu=1, region_reads=None, device=0,
                                    scoring=None, aligner=None):
     """nanoRepeat_bam.py:260-286.  `region_reads` = {read_name: sequence} in file order (the
@@ -137,6 +147,8 @@ def find_anchor_locations_in_reads(data_type, repeat_region, num_cpu=1, region_r
                     continue
                 ts, te = int(out["tstart"][j]), int(out["tend"][j])
                 recs.append(AnchorHit(n, qlen, ts, te, strand, tname, int(out["score"][j]), te - ts))
+        if not recs:
+            _record_no_anchor_read(repeat_region, n)
         find_anchor_locations_for1read(recs, repeat_region)
 
 
@@ -235,6 +247,8 @@ def find_anchor_locations_in_reads_many(data_type, repeat_regions, reads_by_regi
                             continue
                         ts, te = int(out["tstart"][j]), int(out["tend"][j])
                         recs.append(AnchorHit(n, qlen, ts, te, strand, tname, int(out["score"][j]), te - ts))
+                if not recs:
+                    _record_no_anchor_read(region, n)
                 find_anchor_locations_for1read(recs, region)
 
 

@@ -7,6 +7,10 @@
           recall of the truth reads (offered by the screen / accepted by the anchor check)
   recall  a smaller panel with reads that end inside an anchor: screen=True against screen=False, per anchor overlap
 
+--partial: the motif screen alone, on the same chunk: nra_screen_reads and nra_screen_reads_partial in
+alternating calls on one handle, each from host buffers to host results, with k_screen_hits' and k_screen_motifs' time
+from HIP events (the partial call runs both kernels on one upload).
+
 --only anchors: the screen and the anchor stage alone on the panel (no other kernels), for a rocprofv3 kernel trace that
 compares k_screen_hits with the anchor stage's kernels.
 
@@ -114,6 +118,58 @@ def bench_screen(p, anchor_len, chunk_bases, reps):
                 index=scr_stats_keys(st))
 
 
+def panel_chunk(p, chunk_bases):
+    seqs = [s for _, s in p["reads"]]
+    chunk, size = [], 0
+    while size < chunk_bases:                         # the panel's reads, repeated up to chunk_bases
+        for s in seqs:
+            chunk.append(s)
+            size += len(s)
+            if size >= chunk_bases:
+                break
+    return chunk
+
+
+def bench_partial(p, anchor_len, chunk_bases, reps):
+    """nra_screen_reads and nra_screen_reads_partial in alternating calls over one prepacked chunk of ~chunk_bases."""
+    chunk = panel_chunk(p, chunk_bases)
+    data, off = _capi.pack_reads(chunk)
+    lib = _capi.load()
+    motifs = [u for _, _, _, u in p["regions"]]
+    plain, partial = [], []
+    with nr_screen.Screen(anchors_of(p, anchor_len), motifs=motifs) as scr:
+        cap = 8 * len(chunk) + 1024
+        arrs = [np.zeros(cap, np.int32) for _ in range(5)]
+        kind = np.zeros(cap, np.uint8)
+        ptrs = [_capi._ptr(a, C.c_int32) for a in arrs]
+        for rep in range(reps + 1):
+            n = C.c_int64(cap)
+            t0 = time.perf_counter()
+            rc = lib.nra_screen_reads(scr._h, len(chunk), data, _capi._ptr(off, C.c_int64), 4, C.byref(n), *ptrs[:4])
+            wall = time.perf_counter() - t0
+            _capi._check(rc)
+            a = dict(call_ms=wall * 1e3, hits_kernel_ms=scr.stats()["kernel_ms"], pairs=int(n.value))
+            n = C.c_int64(cap)
+            t0 = time.perf_counter()
+            rc = lib.nra_screen_reads_partial(scr._h, len(chunk), data, _capi._ptr(off, C.c_int64), 4, 5, C.byref(n),
+                                              *ptrs, _capi._ptr(kind, C.c_uint8))
+            wall = time.perf_counter() - t0
+            _capi._check(rc)
+            st = scr.stats()
+            b = dict(call_ms=wall * 1e3, hits_kernel_ms=st["kernel_ms"], motif_kernel_ms=st["motif_kernel_ms"],
+                     pairs=int(n.value), kinds=np.bincount(kind[:n.value], minlength=4).tolist())
+            if rep:                                   # the first round is the warm-up
+                plain.append(a); partial.append(b)
+        n_classes = st["n_classes"]
+
+    def med(rows, key):
+        return float(np.median([r[key] for r in rows]))
+    return dict(reads=len(chunk), bases=int(off[-1]), n_classes=n_classes, screen_reads=plain, screen_reads_partial=partial,
+                median=dict(hits_kernel_ms=med(plain, "hits_kernel_ms"), hits_kernel_ms_in_partial=med(partial, "hits_kernel_ms"),
+                            motif_kernel_ms=med(partial, "motif_kernel_ms"), screen_reads_call_ms=med(plain, "call_ms"),
+                            screen_reads_partial_call_ms=med(partial, "call_ms")))
+
+
 def scr_stats_keys(st):
     return {k: st[k] for k in ("n_keys", "n_postings", "n_masked_periodic", "n_masked_max_occ", "index_bytes", "build_ms")}
 
@@ -193,6 +249,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--recall-regions", type=int, default=40)
     ap.add_argument("--only", choices=("all", "anchors", "screen"), default="all")
+    ap.add_argument("--partial", action="store_true", help="the motif screen against the anchor screen, alone")
     ap.add_argument("--out", default="screen.json")
     a = ap.parse_args()
     res = dict(args=vars(a))
@@ -202,7 +259,9 @@ def main():
     res["panel"] = dict(regions=a.regions, reads=len(p["reads"]), bases=sum(len(s) for _, s in p["reads"]),
                         gen_s=time.perf_counter() - t0)
     with tempfile.TemporaryDirectory() as work:
-        if a.only == "anchors":
+        if a.partial:
+            res["partial"] = bench_partial(p, a.anchor_len, a.chunk_bases, a.reps)
+        elif a.only == "anchors":
             res["anchors_only"] = run_e2e(p, a.anchor_len, work, only_anchors=True)
         elif a.only == "screen":
             res["screen"] = bench_screen(p, a.anchor_len, a.chunk_bases, 1)
