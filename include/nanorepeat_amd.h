@@ -557,6 +557,48 @@ int nra_mixture_fit(int device, int64_t n_samples, const double* samples, int32_
                     const int32_t* fit_n, const int32_t* starts, int32_t flags,
                     double* lb, double* w, double* mu, double* var, int32_t* n_iter, int32_t* converged);
 
+/* ---- bootstrap of the mixture fits: the order search of every replicate of every problem in one call
+ *
+ * A problem is what the phasing step fits: m kept reads of d axes (x, row-major), an error rate e, the noise z of its
+ * simulated sample (100 m d doubles) and the start rows of its fits.  Replicate b of it resamples the reads by
+ * idx[b][0..m) and keeps the noise in place.  Row j (0 <= j < N = 100 m), axis a of its sample:
+ *   X_b[j][a] = x[idx[b][j mod m]][a] + (z[j d + a] e) (10 + x[idx[b][j mod m]][a])
+ * evaluated in this order in float64 with nothing contracted (idx[b] = 0, 1, ..., m - 1 gives the problem's own sample).
+ * Order search of a replicate, every fit as specified for nra_mixture_fit:
+ *   for n = first_n, first_n + 1, ...:
+ *     n > max_n: decided, order max_n with the model made for it.
+ *     n > n_cap: NRA_BOOT_NEEDS_MORE (the caller runs the problem again with a larger n_cap).
+ *     n = 1: nothing to fit and no pair to overlap; go on.
+ *     fit n components from each of the ten starts of order n; the best is the largest lb, a tie to the lowest start.
+ *     if two components i < j of the best have intervals mu +- z_o max(1, sqrt(var)) that overlap on every axis
+ *     (max of the lower ends - min of the upper ends <= 0: touching counts): decided, order n - 1 with the best model
+ *     of order n - 1.
+ * Order 1 has no parameters: every read belongs to its one component.
+ * Outputs per replicate: status, and when decided the order, the best start of that order (-1 for order 1), its lb
+ * (0 for order 1) and w, mu, var of its components.  A replicate is a function of its problem and its indices alone:
+ * not of the other replicates or problems of the call, their order, the flags or the run.  DESIGN.md section 24. */
+#define NRA_BOOT_DECIDED     0
+#define NRA_BOOT_NEEDS_MORE  1
+
+/* Problem p: prob_m[p] reads of prob_d[p] axes from x[prob_x_off[p]] (of n_x doubles), noise from z[prob_z_off[p]]
+ * (of n_z), error rate prob_e[p], interval factor prob_zo[p], orders prob_first_n[p] .. prob_n_cap[p] <= prob_max_n[p];
+ * its start rows from starts[prob_start_off[p]] (of n_starts): for every order n from max(first_n, 2) to n_cap, ten
+ * starts of n rows each, order-major.  idx: n_rep * m indices per problem, problems in order, replicate-major.
+ * Replicate b of problem p is r = p * n_rep + b; with o = n_rep * (n_cap[0] + ... + n_cap[p-1]) + b * n_cap[p] it writes
+ * status[r], order[r], best_start[r], lb[r], w[o + c], mu[2 (o + c) + axis], var[2 (o + c) + axis] for c < order[r]
+ * (axis 1 is 0 where d = 1; entries not written are 0).  flags: NRA_MIX_STREAM, NRA_MIX_ONE_CLASS, as for
+ * nra_mixture_fit; the results do not depend on them.
+ * n_rep < 1, an index or a start row out of range, a value that is not finite, d other than 1 or 2, m < 1, or orders
+ * that are not first_n = 1 or 2, 1 <= n_cap <= max_n are NRA_E_ARG; n_rep > 1000, n_cap > 32 or N > 4 194 304 is NRA_E_RANGE.
+ * Arguments are checked before the device is touched. */
+int nra_mixture_bootstrap(int device, int64_t n_x, const double* x, int64_t n_z, const double* z, int32_t n_problems,
+                          const int32_t* prob_m, const int32_t* prob_d, const int64_t* prob_x_off,
+                          const int64_t* prob_z_off, const double* prob_e, const double* prob_zo,
+                          const int32_t* prob_first_n, const int32_t* prob_n_cap, const int32_t* prob_max_n,
+                          const int64_t* prob_start_off, int64_t n_starts, const int32_t* starts, int32_t n_rep,
+                          const int32_t* idx, int32_t flags, int32_t* status, int32_t* order, int32_t* best_start,
+                          double* lb, double* w, double* mu, double* var);
+
 /* ---- allele consensus: one sequence per group of tracts (no counterpart in the reference) ----------------------------
  *
  * Integer arithmetic throughout: the outputs are a function of the group alone, bit for bit.

@@ -37,7 +37,7 @@ EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count
            "nra_batch1d_fetch", "nra_batch1d_resweeps", "nra_batch1d_clears", "nra_batch2d_fetch", "nra_batch_destroy",
            "nra_screen_create", "nra_screen_reads", "nra_screen_stats", "nra_screen_destroy",
            "nra_screen_set_motifs", "nra_screen_reads_partial",
-           "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts", "nra_mixture_fit",
+           "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts", "nra_mixture_fit", "nra_mixture_bootstrap",
            "nra_tract_consensus", "nra_allele_split", "nra_tract_segments", "nra_tract_periods")
 
 
@@ -193,6 +193,10 @@ def load():
     lib.nra_extend_tracts.restype = C.c_int
     lib.nra_extend_tracts.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, C.c_int32, C.c_char_p, pi64, pi32,
                                       C.c_int32, C.c_int32, C.c_int32, pi32, pi32, pi32, pi32]
+    lib.nra_mixture_bootstrap.restype = C.c_int
+    lib.nra_mixture_bootstrap.argtypes = [C.c_int, C.c_int64, pf64, C.c_int64, pf64, C.c_int32, pi32, pi32, pi64, pi64,
+                                          pf64, pf64, pi32, pi32, pi32, pi64, C.c_int64, pi32, C.c_int32, pi32,
+                                          C.c_int32, pi32, pi32, pi32, pf64, pf64, pf64, pf64]
     lib.nra_mixture_fit.restype = C.c_int
     lib.nra_mixture_fit.argtypes = [C.c_int, C.c_int64, pf64, C.c_int32, pi64, pi32, pi32, C.c_int32, pi32, pi32, pi32,
                                     C.c_int32, pf64, pf64, pf64, pf64, pi32, pi32]
@@ -794,6 +798,65 @@ def mixture_fit(samples, prob_off, prob_n, prob_d, fit_problem, fit_n, starts, f
                                flags, _ptr(out["lb"], C.c_double), _ptr(out["w"], C.c_double),
                                _ptr(out["mu"], C.c_double), _ptr(out["var"], C.c_double),
                                _ptr(out["n_iter"], C.c_int32), _ptr(out["converged"], C.c_int32)))
+    return out
+
+
+BOOT_DECIDED, BOOT_NEEDS_MORE = 0, 1      # NRA_BOOT_DECIDED, NRA_BOOT_NEEDS_MORE
+BOOT_STARTS = 10
+BOOT_COPIES = 100
+
+
+def boot_start_rows(first_n, n_cap):
+    """The start rows nra_mixture_bootstrap reads for a problem: ten starts of n rows for every order it may fit."""
+    return sum(BOOT_STARTS * n for n in range(max(int(first_n), 2), int(n_cap) + 1))
+
+
+def mixture_bootstrap(x, z, prob_m, prob_d, prob_e, prob_zo, prob_first_n, prob_n_cap, prob_max_n, starts, n_rep, idx,
+                      flags=0, device=0):
+    """nra_mixture_bootstrap: the order search of n_rep replicates of every problem.  x, z, starts, idx: the problems'
+    kept sizes (m * d each), noise (100 m d), start rows (boot_start_rows) and resampling indices (n_rep * m), each
+    concatenated in problem order -> dict(status, order, best_start, lb [problems, n_rep]; off = where a problem's
+    components begin (n_rep * n_cap each, replicate-major); w [components], mu and var [components, 2])."""
+    lib = load()
+    xs = np.ascontiguousarray(x, np.float64).ravel()
+    zs = np.ascontiguousarray(z, np.float64).ravel()
+    pm = np.ascontiguousarray(prob_m, np.int32)
+    pd = np.ascontiguousarray(prob_d, np.int32)
+    pe = np.ascontiguousarray(prob_e, np.float64)
+    pz = np.ascontiguousarray(prob_zo, np.float64)
+    pf = np.ascontiguousarray(prob_first_n, np.int32)
+    pc = np.ascontiguousarray(prob_n_cap, np.int32)
+    px = np.ascontiguousarray(prob_max_n, np.int32)
+    st = np.ascontiguousarray(starts, np.int32).ravel()
+    ix = np.ascontiguousarray(idx, np.int32).ravel()
+    n_rep = int(n_rep)
+    n = len(pm)
+    if not all(len(v) == n for v in (pd, pe, pz, pf, pc, px)):
+        raise ValueError("one entry per problem in every problem array")
+    md = np.maximum(pm, 0).astype(np.int64) * np.maximum(pd, 0)
+
+    def offsets(sizes):
+        off = np.zeros(n + 1, np.int64)
+        np.cumsum(sizes, out=off[1:])
+        return off
+
+    x_off, z_off = offsets(md), offsets(md * BOOT_COPIES)
+    s_off = offsets([boot_start_rows(f, c) for f, c in zip(pf, pc)])
+    off = offsets(max(n_rep, 0) * np.maximum(pc, 0).astype(np.int64))
+    if len(xs) != x_off[-1] or len(zs) != z_off[-1] or len(st) != s_off[-1]:
+        raise ValueError("x, z and starts must hold exactly what the problems need")
+    if len(ix) != max(n_rep, 0) * int(np.maximum(pm, 0).sum()):
+        raise ValueError("n_rep * m indices per problem")
+    r, t = (n, max(n_rep, 0)), int(off[-1])
+    out = dict(status=np.zeros(r, np.int32), order=np.zeros(r, np.int32), best_start=np.zeros(r, np.int32),
+               lb=np.zeros(r), off=off, w=np.zeros(t), mu=np.zeros((t, 2)), var=np.zeros((t, 2)))
+    _check(lib.nra_mixture_bootstrap(
+        device, len(xs), _ptr(xs, C.c_double), len(zs), _ptr(zs, C.c_double), n, _ptr(pm, C.c_int32),
+        _ptr(pd, C.c_int32), _ptr(x_off, C.c_int64), _ptr(z_off, C.c_int64), _ptr(pe, C.c_double), _ptr(pz, C.c_double),
+        _ptr(pf, C.c_int32), _ptr(pc, C.c_int32), _ptr(px, C.c_int32), _ptr(s_off, C.c_int64), len(st),
+        _ptr(st, C.c_int32), n_rep, _ptr(ix, C.c_int32), flags, _ptr(out["status"], C.c_int32),
+        _ptr(out["order"], C.c_int32), _ptr(out["best_start"], C.c_int32), _ptr(out["lb"], C.c_double),
+        _ptr(out["w"], C.c_double), _ptr(out["mu"], C.c_double), _ptr(out["var"], C.c_double)))
     return out
 
 

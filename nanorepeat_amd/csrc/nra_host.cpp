@@ -519,6 +519,9 @@ int64_t sweep128_cells(int R, int ncols) { return (int64_t)64 * R * ((int64_t)nc
 
 }  // namespace
 
+extern "C" int nra_copy_h2d(void* dst, const void* src, size_t bytes) { return (int)copy_h2d(dst, src, bytes); }
+extern "C" int nra_copy_d2h(void* dst, const void* src, size_t bytes) { return (int)copy_d2h(dst, src, bytes); }
+
 struct nra_batch {
     Arena arena;               // declared first: released after every DevBuf below
     Arena cell_arena;          // 2D: buffers that depend on the cell list; reset by nra_batch2d_set_cells

@@ -327,6 +327,23 @@ struct NraMixFit {
     int32_t n;
 };
 
+// Bootstrap of the mixture fits (nra_bootstrap.hip, nra_bootstrap_host.cpp): one workgroup of 256 threads runs the whole
+// order search of one replicate of one problem.
+#define NRA_BOOT_MAX_B 1000
+#define NRA_BOOT_STARTS 10
+#define NRA_BOOT_COPIES 100          // rows of the sample per kept read
+
+// one problem: m kept reads of d axes from double `x_off` of the size buffer, their noise (100 m d doubles) from double
+// `z_off` of the noise buffer, its replicates' indices (m per replicate) from entry `idx_off`, its start rows (orders
+// max(first_n, 2) .. n_cap, ten starts each, n rows per start) from entry `start_off`, and the results of its
+// replicate b at entry `rep_off + b` (status, order, best start, lb) and `comp_off + b n_cap` (w; mu and var at twice
+// that)
+struct NraBootProblem {
+    int64_t x_off, z_off, idx_off, start_off, rep_off, comp_off;
+    double e, z_o;
+    int32_t m, d, first_n, n_cap, max_n, pad;
+};
+
 // Allele consensus (nra_consensus.hip, nra_consensus_host.cpp): banded unit-cost alignment of every tract of a group to
 // the group's backbone, one wave per tract, votes into the group's tables, then a new backbone per group (DESIGN.md
 // section 18).  Band class c: a lane owns c consecutive diagonals, the band holds 64 c.
@@ -437,6 +454,18 @@ int nra_set_error(int code, const char* msg);
 int nra_launch_mixture(hipStream_t st, int d, int kreg, int n, const int32_t* fit_ids, const NraMixFit* fits,
                        const NraMixProblem* probs, const double* samples, const int32_t* starts, double* lb, double* w,
                        double* mu, double* var, int32_t* iter);
+
+// bootstrap of the mixture fits (nra_bootstrap.hip): workgroup g runs replicate jobs[g] % n_rep of problem
+// jobs[g] / n_rep.  d and kreg as for nra_launch_mixture, with n = 100 m
+int nra_launch_mixture_boot(hipStream_t st, int d, int kreg, int n, const int32_t* jobs, int n_rep,
+                            const NraBootProblem* probs, const double* x, const double* z, const int32_t* idx,
+                            const int32_t* starts, int32_t* status, int32_t* order, int32_t* best_start, double* lb,
+                            double* w, double* mu, double* var);
+
+// copies between pageable host memory and the device through the calling thread's pinned stage (nra_host.cpp);
+// they return a hipError_t
+int nra_copy_h2d(void* dst, const void* src, size_t bytes);
+int nra_copy_d2h(void* dst, const void* src, size_t bytes);
 
 // anchor screen (nra_screen.hip): one workgroup per tile.  Entries go to entries[0, cap); *count ends as the number of
 // entries wanted, which may exceed cap (the host then grows the list and runs again)

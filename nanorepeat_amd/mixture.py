@@ -42,12 +42,18 @@ def _key(seed, restart, *more):
     return key + [int(restart)] if restart else key
 
 
-def sample(x, error_rate, seed, restart=0):
-    """x: the kept sizes [m, d] -> the simulated sample [100 m, d]."""
+def noise(n_values, seed, restart=0):
+    """The noise of a problem whose kept sizes are n_values numbers (m d): one standard normal per value of its sample."""
+    rng = np.random.default_rng(_key(seed, restart) if restart else int(seed))
+    return rng.standard_normal(phasing.SIM_COPIES * n_values)
+
+
+def sample(x, error_rate, seed, restart=0, z=None):
+    """x: the kept sizes [m, d] -> the simulated sample [100 m, d] (z: its noise, when the caller has drawn it)."""
     x = np.ascontiguousarray(x, np.float64)
     flat = x.ravel()
-    rng = np.random.default_rng(_key(seed, restart) if restart else int(seed))
-    z = rng.standard_normal(phasing.SIM_COPIES * flat.size)
+    if z is None:
+        z = noise(flat.size, seed, restart)
     tiled = np.tile(flat, phasing.SIM_COPIES)
     return (tiled + z * error_rate * (10 + tiled)).reshape(-1, x.shape[1])
 
@@ -90,9 +96,15 @@ def one_component(X):
     return FittedMixture([nk / len(X)], [mu], [var])
 
 
-def components_overlap(model, overlap):
-    """phasing.auto_gmm's stop test on a fitted mixture."""
-    z = statistics.NormalDist().inv_cdf(1.0 - overlap)
+def overlap_z(overlap):
+    """The half width, in standard deviations, of the central interval that leaves `overlap` outside on each side."""
+    return statistics.NormalDist().inv_cdf(1.0 - overlap)
+
+
+def components_overlap(model, overlap, z=None):
+    """phasing.auto_gmm's stop test on a fitted mixture (z: overlap_z(overlap), when the caller has it)."""
+    if z is None:
+        z = overlap_z(overlap)
     n, d = model.means_.shape
     iv = [[(model.means_[c][a] - z * max(1.0, math.sqrt(model.covariances_[c][a])),
             model.means_[c][a] + z * max(1.0, math.sqrt(model.covariances_[c][a]))) for a in range(d)] for c in range(n)]
@@ -107,10 +119,13 @@ class Problem:
         self.x = np.ascontiguousarray(x, np.float64)
         self.seed, self.restart = seed, restart
         self.overlap, self.max_n = max_mutual_overlap, max_num_components
-        self.X = sample(self.x, error_rate, seed, restart)
+        self.error_rate, self.z_o = error_rate, overlap_z(max_mutual_overlap)
+        self.z = noise(self.x.size, seed, restart)             # kept for the bootstrap, which leaves it in place
+        self.X = sample(self.x, error_rate, seed, restart, self.z)
         self.first_n = 2 if self.x.shape[1] == 1 else 1
         self.models = {}                   # order -> FittedMixture of its best start
         self.best_start = {}
+        self.best_lb = {}
         self.next_n = self.first_n
         self.answer = None                 # (order, model) once decided
 
@@ -119,6 +134,10 @@ class Problem:
             assert n == 1
             self.models[1] = one_component(self.X)
         return self.models[n]
+
+    def starts(self, n, t):
+        """The start rows of start t of order n."""
+        return start_rows(self.seed, n, t, len(self.X), self.restart)
 
     def wanted(self, window):
         """The orders of the next call: up to `window` of them that need the device."""
@@ -138,7 +157,7 @@ class Problem:
                 self.answer = (self.max_n, self._model(self.max_n))
             elif n > 1 and n not in self.models:
                 return
-            elif components_overlap(self._model(n), self.overlap):
+            elif components_overlap(self._model(n), self.overlap, self.z_o):
                 self.answer = (n - 1, self._model(n - 1))
             else:
                 self.next_n = n + 1
@@ -165,7 +184,7 @@ def solve(problems, engine=None, device=0, window=None):
             for n in p.wanted(window):
                 for t in range(N_STARTS):
                     fit_problem.append(i); fit_n.append(n); owner.append((p, n, t))
-                    starts.append(start_rows(p.seed, n, t, N, p.restart))
+                    starts.append(p.starts(n, t))
         samples = np.concatenate([p.X.ravel() for p in active])
         got = engine(samples, prob_off, prob_n, prob_d, fit_problem, fit_n, np.concatenate(starts), device=device)
         lb, o = got["lb"], got["off"]
@@ -176,8 +195,63 @@ def solve(problems, engine=None, device=0, window=None):
             sl = slice(int(o[best]), int(o[best + 1]))
             p.models[n] = FittedMixture(got["w"][sl], got["mu"][sl, :d], got["var"][sl, :d])
             p.best_start[n] = best - f
+            p.best_lb[n] = float(lb[best])
         for p in active:
             p.advance()
+
+
+BOOT_KEY = 0x626F6F74      # "boot": the second word of the key of a problem's resampling generator
+BOOT_DECIDED, BOOT_NEEDS_MORE = 0, 1
+BOOT_EXTRA_ORDERS = 2      # the first call hands over start rows up to the called order + 2
+
+
+def resample_indices(seed, m, B):
+    """The reads of the B replicates of a problem of m kept reads: [B, m] indices into them."""
+    return np.random.default_rng([int(seed), BOOT_KEY]).integers(0, m, size=(B, m))
+
+
+def _bootstrap_call(problems, n_caps, idx, B, engine, device):
+    starts = []
+    for p, n_cap in zip(problems, n_caps):
+        starts += [p.starts(n, t) for n in range(max(p.first_n, 2), n_cap + 1) for t in range(N_STARTS)]
+    got = engine(np.concatenate([p.x.ravel() for p in problems]), np.concatenate([p.z for p in problems]),
+                 [len(p.x) for p in problems], [p.x.shape[1] for p in problems], [p.error_rate for p in problems],
+                 [p.z_o for p in problems], [p.first_n for p in problems], n_caps, [p.max_n for p in problems],
+                 np.concatenate(starts) if starts else np.zeros(0, np.int32), B,
+                 np.concatenate([i.ravel() for i in idx]).astype(np.int32), device=device)
+    out = []
+    for k, (p, n_cap) in enumerate(zip(problems, n_caps)):
+        d = p.x.shape[1]
+        sl = slice(int(got["off"][k]), int(got["off"][k + 1]))
+        out.append(dict(status=got["status"][k].copy(), order=got["order"][k].copy(),
+                        best_start=got["best_start"][k].copy(), lb=got["lb"][k].copy(),
+                        w=got["w"][sl].reshape(B, n_cap), mu=got["mu"][sl, :d].reshape(B, n_cap, d),
+                        var=got["var"][sl, :d].reshape(B, n_cap, d), idx=idx[k]))
+    return out
+
+
+def bootstrap(problems, B, engine=None, device=0):
+    """The order search of B bootstrap replicates of every solved problem: one engine call with
+    start rows up to the called order + 2, and one more, with every order up to max_n, for the problems that had a
+    replicate left undecided by that cap.  -> per problem dict(status, order, best_start, lb [B]; w [B, n_cap]; mu, var
+    [B, n_cap, d]: the model of replicate b in its first order[b] components; idx [B, m]: its reads)."""
+    if engine is None:
+        from . import _capi
+        engine = _capi.mixture_bootstrap
+    if not problems:
+        return []
+    if any(p.answer is None for p in problems):
+        raise ValueError("bootstrap needs solved problems")
+    idx = [resample_indices(p.seed, len(p.x), B) for p in problems]
+    out = _bootstrap_call(problems, [min(p.max_n, p.answer[0] + BOOT_EXTRA_ORDERS) for p in problems], idx, B, engine,
+                          device)
+    again = [k for k, r in enumerate(out) if (r["status"] == BOOT_NEEDS_MORE).any()]
+    if again:
+        more = _bootstrap_call([problems[k] for k in again], [problems[k].max_n for k in again],
+                               [idx[k] for k in again], B, engine, device)
+        for k, r in zip(again, more):
+            out[k] = r
+    return out
 
 
 class Fitter:
@@ -195,9 +269,10 @@ class Fitter:
         return p.answer
 
 
-def phase_jobs(jobs, device=0, engine=None):
+def phase_jobs(jobs, device=0, engine=None, problems_out=None):
     """jobs: ("1d" | "2d", args) as pipeline.phase_regions builds them -> what phasing.run_job returns for each, with
-    the first fit of every job made in one batch.  A job's seed must be an int (see fresh_seed)."""
+    the first fit of every job made in one batch.  A job's seed must be an int (see fresh_seed).  `problems_out`: a
+    list that receives every job's solved Problem (None for a job with too few reads), for the bootstrap."""
     problems = []
     for kind, args in jobs:
         count_dict, ploidy, error_rate, overlap, max_n, _, seed = args
@@ -209,6 +284,8 @@ def phase_jobs(jobs, device=0, engine=None):
         _, flat = phasing.remove_outlier_reads(count_dict, dimension)
         problems.append(Problem(np.array(flat, np.float64).reshape(-1, dimension), error_rate, overlap, max_n, seed))
     solve([p for p in problems if p is not None], engine, device)
+    if problems_out is not None:
+        problems_out.extend(problems)
     out = []
     for (kind, args), p in zip(jobs, problems):
         fitter = Fitter(engine, device, p)

@@ -72,7 +72,8 @@ def _fit_in_worker_processes(jobs, n_jobs):
 
 def phase_regions(repeat_regions, data_type="ont", ploidy=2, max_mutual_overlap=0.15, max_num_components=-1,
                   remove_noisy_reads=False, seed=None, out_tsv_file=None, n_jobs=None, mixture="sklearn", device=0,
-                  mixture_engine=None):
+                  mixture_engine=None, bootstrap=0, bootstrap_confidence=0.95, bootstrap_engine=None,
+                  bootstrap_tsv_file=None):
     """Step 4 for every region (nanoRepeat_bam.py:683-684) and the final table (:737-743); defaults
     are the CLI's (nanoRepeat.py:121-129,159-160).  With a seed, region i uses seed + i.  The mixture
     fits -- by far the longest step of the whole command -- run in up to 16 worker processes like
@@ -80,10 +81,15 @@ def phase_regions(repeat_regions, data_type="ont", ploidy=2, max_mutual_overlap=
     that get only the sizes and never touch the GPU.  n_jobs=1 keeps everything in this process.
     mixture="gpu" fits every region's mixtures on the GPU instead, in this process, in one C-ABI call per
     window of model orders (mixture.py): no worker processes, no scikit-learn, and a
-    run is a function of its seed (seed=None draws one).  `mixture_engine` stands in for that call (tests)."""
+    run is a function of its seed (seed=None draws one).  `mixture_engine` stands in for that call (tests).
+    bootstrap=B > 0 (mixture="gpu" only) adds bootstrap confidence intervals (bootstrap.py): the
+    order search of B resamples of every region's kept reads in one more GPU call, `<region>.bootstrap.tsv` with every
+    replicate's alleles, region.bootstrap with the intervals (bootstrap_confidence) and the allele-count support, and
+    their table in bootstrap_tsv_file when given.  `bootstrap_engine` stands in for that call (tests)."""
     import os
     from . import mixture as nr_mixture
     nr_mixture.check_engine_name(mixture)
+    _check_bootstrap(bootstrap, mixture)
     if mixture == "gpu" and seed is None:
         seed = nr_mixture.fresh_seed()
     if max_num_components == -1:
@@ -91,8 +97,9 @@ def phase_regions(repeat_regions, data_type="ont", ploidy=2, max_mutual_overlap=
     error_rate = phasing.data_type_error_rate(data_type)
     jobs = [(phasing.region_count_dict(region), ploidy, error_rate, max_mutual_overlap, max_num_components,
              remove_noisy_reads, None if seed is None else seed + i) for i, region in enumerate(repeat_regions)]
+    problems = []
     if mixture == "gpu":
-        fitted = nr_mixture.phase_jobs([("1d", j) for j in jobs], device, mixture_engine)
+        fitted = nr_mixture.phase_jobs([("1d", j) for j in jobs], device, mixture_engine, problems)
     else:
         if n_jobs is None:
             n_jobs = min(16, os.cpu_count() or 1, max(1, sum(len(j[0]) >= 2 for j in jobs)))
@@ -106,10 +113,25 @@ def phase_regions(repeat_regions, data_type="ont", ploidy=2, max_mutual_overlap=
             phasing.split_allele_using_gmm_1d(region, ploidy, error_rate, max_mutual_overlap, max_num_components,
                                               remove_noisy_reads, fitted=fit)
         rows.append(phasing.final_output_row(region))
+    if bootstrap:
+        from . import bootstrap as nr_bootstrap
+        nr_bootstrap.bootstrap_regions(repeat_regions, problems, fitted, bootstrap, ploidy, remove_noisy_reads,
+                                       bootstrap_confidence, bootstrap_engine, device)
+        for region in repeat_regions:
+            nr_bootstrap.write_region_bootstrap(region)
+        if bootstrap_tsv_file:
+            nr_bootstrap.write_bootstrap_summary(repeat_regions, bootstrap_tsv_file)
     if out_tsv_file:
         with open(out_tsv_file, "w") as f:
             f.write("".join(rows))
     return rows
+
+
+def _check_bootstrap(bootstrap, mixture):
+    if bootstrap < 0 or int(bootstrap) != bootstrap:
+        raise ValueError(f"bootstrap must be a number of replicates >= 0, not {bootstrap!r}")
+    if bootstrap and mixture != "gpu":
+        raise ValueError('bootstrap > 0 needs mixture="gpu": only that fit is a function of (sizes, seed)')
 
 
 def quantify_joint(in_fq, ref_fasta, repeat1_string, repeat2_string, out_prefix, data_type="ont", num_threads=1,
@@ -173,7 +195,7 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
                       min_motif_count=4, min_motif_share=0.1, partial_reads=False, mixture="sklearn",
                       allele_consensus=False, allele_split=False, motif_runs=False, segment_motifs=None,
                       switch_cost=None, read_alignments=False, discover_periods=False, in_repeat_reads=False,
-                      **engines):
+                      bootstrap=0, bootstrap_confidence=0.95, **engines):
     """The BAM command from files to files (nanoRepeat_bam.py:614-751): for every region of the BED
     file, reads from the alignment file -> `<out_prefix>.details/<chr>/<region>.*` ->
     `<out_prefix>.NanoRepeat_output.tsv`.  The reference forks up to 16 workers, one region each;
@@ -194,11 +216,16 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
     period files (periods.py): the period (up to 64 bases) and the unit of every allele's consensus tract, every read's
     evidence for it, and the reads' sizes in that unit where it is not the BED motif.  in_repeat_reads=True adds the
     in-repeat read files (partial.py): for every read of the region's window without a hit of either anchor, the repeat
-    units it shows, and per region whether any such read shows more than the largest spanning read.
+    units it shows, and per region whether any such read shows more than the largest spanning read.  bootstrap=B > 0
+    (with mixture="gpu") adds the bootstrap files (bootstrap.py): `<region>.bootstrap.tsv` and
+    `<out_prefix>.NanoRepeat_bootstrap.tsv` with a bootstrap_confidence interval for every allele size and the share
+    of the B replicates that have the called number of alleles.
     `engines` may carry aligner / scorer / structure_engine / motif_engine / extension_engine / mixture_engine /
-    consensus_engine / split_engine / segment_engine / path_aligner / period_engine stand-ins.  Returns the regions."""
+    consensus_engine / split_engine / segment_engine / path_aligner / period_engine / bootstrap_engine stand-ins.
+    Returns the regions."""
     from . import bam as nr_bam, mixture as nr_mixture
     nr_mixture.check_engine_name(mixture)
+    _check_bootstrap(bootstrap, mixture)
     regions = nr_io.read_repeat_region_file(repeat_region_bed, no_details)
     ref_fasta_dict = nr_io.fasta_file2dict(ref_fasta)
     live, reads_of = [], []
@@ -217,7 +244,7 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
                         read_structure, _motif_options(discover_motifs, min_motif_count, min_motif_share),
                         partial_reads, mixture, allele_consensus, allele_split,
                         _run_options(motif_runs, segment_motifs, switch_cost), read_alignments, discover_periods,
-                        in_repeat_reads=in_repeat_reads)
+                        in_repeat_reads=in_repeat_reads, bootstrap=(bootstrap, bootstrap_confidence))
     return regions
 
 
@@ -244,7 +271,7 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
                         read_structure=False, motif_options=None, partial_reads=False, mixture="sklearn",
                         allele_consensus=False, allele_split=False, run_options=None, read_alignments=False,
-                        discover_periods=False, in_repeat_reads=False, candidates=None):
+                        discover_periods=False, in_repeat_reads=False, candidates=None, bootstrap=(0, 0.95)):
     """The commands' common tail: steps 1-4 for the regions with reads, then one TSV row per BED region; with
     read_structure, the structure of every read with a size and the two structure files; with motif_options (a dict
     of motifs.motif_regions keywords), the tandem motifs of every read with a core and the two motif files; with
@@ -259,17 +286,23 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
     read's evidence for it, the two period files and one NOTICE counting the alleles whose unit is not the BED motif;
     with in_repeat_reads, the four extensions of every read without an anchor, the two in-repeat files and a NOTICE per
     region where such reads show more repeat units than any spanning read.  `candidates` (the FASTQ command, a dict of
-    _place_candidates keywords): the one-anchor and in-repeat reads come from the screen's candidates too."""
+    _place_candidates keywords): the one-anchor and in-repeat reads come from the screen's candidates too.  `bootstrap`
+    (replicates, confidence): with replicates > 0, the bootstrap of every region's phasing and the two bootstrap files."""
     if in_repeat_reads:
         for region in live:
             region.keep_no_anchor_reads = True
     quantify_regions(live, reads_of, data_type, fast_mode, num_cpu, device, scoring,
                      engines.get("aligner"), engines.get("scorer"), keep_candidates=read_alignments and not no_details)
     phase_regions(live, data_type, ploidy, max_mutual_overlap, max_num_components, remove_noisy_reads, seed,
-                  mixture=mixture, device=device, mixture_engine=engines.get("mixture_engine"))
+                  mixture=mixture, device=device, mixture_engine=engines.get("mixture_engine"),
+                  bootstrap=bootstrap[0], bootstrap_confidence=bootstrap[1],
+                  bootstrap_engine=engines.get("bootstrap_engine"))
     with open(f"{out_prefix}.NanoRepeat_output.tsv", "w") as f:
         for region in regions:
             f.write(phasing.final_output_row(region))
+    if bootstrap[0]:
+        from . import bootstrap as nr_bootstrap
+        nr_bootstrap.write_bootstrap_summary(regions, f"{out_prefix}.NanoRepeat_bootstrap.tsv")
     if read_structure:
         from . import structure
         structure.structure_regions(live, device=device, engine=engines.get("structure_engine"))
@@ -359,7 +392,7 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         min_motif_share=0.1, mixture="sklearn", allele_consensus=False, allele_split=False,
                         motif_runs=False, segment_motifs=None, switch_cost=None, read_alignments=False,
                         discover_periods=False, partial_reads=False, in_repeat_reads=False, motif_share_pct=5,
-                        **engines):
+                        bootstrap=0, bootstrap_confidence=0.95, **engines):
     """The FASTQ / FASTA command (nanoRepeat.py:109, `-t fastq|fasta`) from files to files, without a genome mapper:
     the reads each region sees are chosen by the anchor k-mer screen (screen.reads_by_region) instead of a
     genome-wide mapping and a BAM window, then the BAM command's steps run unchanged.  Every region's reference
@@ -375,12 +408,14 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
     and in_repeat_reads=True the in-repeat read files, as for quantify_from_bam: the motif screen (DESIGN.md section
     23) offers the reads with one anchor only and the reads made of a region's motif (at least motif_share_pct % of
     their k-mer windows) as candidates, written to `<region>.partial_candidates.fastq`; they go through the anchor step
-    apart from the region's reads and never reach the sizes or the phasing.
+    apart from the region's reads and never reach the sizes or the phasing.  bootstrap=B > 0 (with mixture="gpu")
+    adds the bootstrap files, as for quantify_from_bam.
     `engines` may carry aligner / scorer / screener / structure_engine / motif_engine / extension_engine /
-    mixture_engine / consensus_engine / split_engine / segment_engine / path_aligner / period_engine stand-ins.
-    Returns the regions."""
+    mixture_engine / consensus_engine / split_engine / segment_engine / path_aligner / period_engine /
+    bootstrap_engine stand-ins.  Returns the regions."""
     from . import screen as nr_screen, mixture as nr_mixture
     nr_mixture.check_engine_name(mixture)
+    _check_bootstrap(bootstrap, mixture)
     regions = nr_io.read_repeat_region_file(repeat_region_bed, no_details)
     ref_fasta_dict = nr_io.fasta_file2dict(ref_fasta)
     screened = []
@@ -418,7 +453,8 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         mixture=mixture, allele_consensus=allele_consensus, allele_split=allele_split,
                         run_options=_run_options(motif_runs, segment_motifs, switch_cost),
                         read_alignments=read_alignments, discover_periods=discover_periods,
-                        partial_reads=partial_reads, in_repeat_reads=in_repeat_reads, candidates=candidates)
+                        partial_reads=partial_reads, in_repeat_reads=in_repeat_reads, candidates=candidates,
+                        bootstrap=(bootstrap, bootstrap_confidence))
     return regions
 
 
