@@ -125,8 +125,10 @@ typedef struct nra_joint_region {
 typedef struct nra_stats {
     int64_t n_alignments;     /* (read, candidate) pairs scored */
     int64_t algorithmic_cells;/* sum of qlen * tlen over those pairs */
-    int64_t executed_cells;   /* DP cells the scoring kernels actually updated (padding included); far below
-                                 algorithmic_cells when the junction decomposition shares work across k */
+    int64_t executed_cells;   /* DP cells the scoring kernels update as planned when the batch is created (padding
+                                 included); far below algorithmic_cells when the junction decomposition shares work
+                                 across k.  An upper bound: a 1D forward sweep that leaves through the saturation exit
+                                 updates fewer (nra_batch1d_saturation reports the skipped steps of a run) */
     int64_t algorithmic_bytes;/* HBM bytes the algorithm must move (packed reads + flanks + results) */
     int64_t n_extent_tasks;   /* alignments re-run by the extents kernel (top-score ties) */
     double  score_kernel_ms;  /* dominant kernel: sum of its launches, HIP events on the batch stream */
@@ -353,6 +355,11 @@ int  nra_batch1d_fetch(nra_batch_t* b,
 /* 1D, after sync: how many sweep tasks (read pairs, or two pairs of the half-wave sweeps) and reads the relaxed anchor
  * columns sent to the exact re-sweep in the last run, and how many there were in all (0 / 0 with NRA_F_FULL_ANCHORS) */
 int  nra_batch1d_resweeps(nra_batch_t* b, int64_t* tasks, int64_t* reads, int64_t* tasks_total, int64_t* reads_total);
+/* 1D, after sync: the saturation exit of the forward sweeps in quanta in the last run (additive, ABI 4).  A sweep whose wave
+ * state repeats from one unit boundary to the next ends there and writes its last value for every repeat count left.
+ * *sweeps: sweep tasks that left that way, *steps: the sweep steps they skipped; *sweeps_total, *steps_total: the forward
+ * sweeps in quanta of the batch and their steps as planned (0 / 0 where no bucket runs in quanta) */
+int  nra_batch1d_saturation(nra_batch_t* b, int64_t* sweeps, int64_t* steps, int64_t* sweeps_total, int64_t* steps_total);
 /* 1D: which per-candidate arrays a run of this batch clears before its kernels start (additive, ABI 4; for tests and
  * measurements).  *scores: cand_score and the flank verdicts -- 0 where every bucket's forward sweeps write them for every
  * candidate; *extents: cand_tstart / cand_tend -- 0 where the selection kernel sets them to -1 on its way */

@@ -34,7 +34,7 @@ F_FULL_ANCHORS = 8192  # testing / comparison, 1D: the exact cell over every anc
 EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count",
            "nra_default_scoring", "nra_release_cached_memory", "nra_round3_1d", "nra_joint_2d", "nra_align_pairs", "nra_align_pairs_cigar", "nra_align_paths", "nra_batch1d_create",
            "nra_batch2d_create", "nra_batch2d_create_reads", "nra_batch2d_set_cells", "nra_joint_grid_cells", "nra_batch2d_set_grid", "nra_batch2d_invalidate", "nra_batch2d_sweep_flanks", "nra_batch2d_refine", "nra_batch_run", "nra_batch_sync", "nra_batch_stats",
-           "nra_batch1d_fetch", "nra_batch1d_resweeps", "nra_batch1d_clears", "nra_batch2d_fetch", "nra_batch_destroy",
+           "nra_batch1d_fetch", "nra_batch1d_resweeps", "nra_batch1d_saturation", "nra_batch1d_clears", "nra_batch2d_fetch", "nra_batch_destroy",
            "nra_screen_create", "nra_screen_reads", "nra_screen_stats", "nra_screen_destroy",
            "nra_screen_set_motifs", "nra_screen_reads_partial",
            "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts", "nra_mixture_fit", "nra_mixture_bootstrap",
@@ -164,6 +164,8 @@ def load():
     lib.nra_batch1d_fetch.restype = C.c_int
     lib.nra_batch1d_resweeps.restype = C.c_int
     lib.nra_batch1d_resweeps.argtypes = [vp, pi64, pi64, pi64, pi64]
+    lib.nra_batch1d_saturation.restype = C.c_int
+    lib.nra_batch1d_saturation.argtypes = [vp, pi64, pi64, pi64, pi64]
     lib.nra_batch1d_clears.restype = C.c_int
     lib.nra_batch1d_clears.argtypes = [vp, pi32, pi32]
     lib.nra_batch1d_fetch.argtypes = [vp, pi32, pi64, pi32, p8, pi32, pi32, pi32]
@@ -592,6 +594,13 @@ class Batch:
         v = [C.c_int64(0) for _ in range(4)]
         _check(load().nra_batch1d_resweeps(self._h, *[C.byref(x) for x in v]))
         return {"tasks": v[0].value, "reads": v[1].value, "tasks_total": v[2].value, "reads_total": v[3].value}
+
+    def saturation(self):
+        """1D, after the run: the forward sweeps in quanta that left through the saturation exit and the steps they skipped,
+        of how many sweeps and planned steps."""
+        v = [C.c_int64(0) for _ in range(4)]
+        _check(load().nra_batch1d_saturation(self._h, *[C.byref(x) for x in v]))
+        return {"sweeps": v[0].value, "steps": v[1].value, "sweeps_total": v[2].value, "steps_total": v[3].value}
 
     def clears(self):
         """1D: which per-candidate arrays a run of this batch clears before its kernels start."""

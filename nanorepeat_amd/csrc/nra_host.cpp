@@ -418,6 +418,7 @@ struct Bucket {
     bool quanta = false;       // ... and its reverse and forward sweeps as ONE launch of quanta taken by ticket (k_sweep_ringq)
     bool taint = false;        // ... with the relaxed cell over the anchor columns far from the junction, and the exact re-sweep
                                // of the tasks it flags
+    int64_t q_fwd_steps = 0;   // ... the steps of its forward sweeps (nra_batch1d_saturation)
     size_t q_off = 0, q_task_off = 0, q_state_off = 0;      // into q_list, q_words' arrivals (2 a task), q_state (int32, 2 slots a task)
     int n_quanta = 0, q_steps = 0;                            // entries of q_list; steps of a part
     int n_jbwd = 0;            // 2D decomposition: reverse sweeps (one per read)
@@ -597,6 +598,11 @@ struct nra_batch {
     DevBuf<NraTask> queue_tasks;
     DevBuf<int32_t> queue_count;   // per bucket: prebuilt queue length (constant)
     DevBuf<int32_t> tie_count;     // per bucket: tie queue length (device-written)
+    // the saturation exit of the forward sweeps in quanta: per bucket four words of the run, [0] sweeps that
+    // left, [2..3] the steps they skipped as one 64-bit word (8-byte aligned), read by nra_batch1d_saturation; sat_steps as
+    // k_sweep_ringq takes it (< 0: no exit)
+    DevBuf<int32_t> sat_count;
+    int sat_steps = -1;
     // 1D: the small words a run starts from zero -- q_words, the row blocks' give-up word, tie_count, redo -- are views
     // into ONE allocation, cleared by one memset per run
     DevBuf<int32_t> run_words;
@@ -1478,6 +1484,7 @@ int nra_batch1d_create(int device, const nra_region_t* regions, int32_t n_region
                 steps_fwd[(size_t)t] = NRA_Q_STEPS_FWD(d.l1, d.m1, bt[t].kmax, bk.half);
                 cut_fwd[(size_t)t] = NRA_Q_CUT(d.l1 + d.m1 * bt[t].kmin - 1);
                 max_steps = std::max(max_steps, std::max(steps_rev[(size_t)t], steps_fwd[(size_t)t]));
+                bk.q_fwd_steps += steps_fwd[(size_t)t];
             }
             bk.q_steps = std::max(q_steps_wanted, ((max_steps + NRA_Q_MAX_PARTS - 2) / (NRA_Q_MAX_PARTS - 1) + 63) / 64 * 64);
             for (int dir = 0; dir < 2; ++dir)
@@ -1500,6 +1507,11 @@ int nra_batch1d_create(int device, const nra_region_t* regions, int32_t n_region
             for (int v : steps_rev) max_rev = std::max(max_rev, v);
             q_state += (max_rev > bk.q_steps ? 2 : 1) * (size_t)bk.n_sweep * NRA_QSTATE_INTS(bk.R) * 64;
         }
+        // (NRA_TEST_SAT=0 and NRA_TEST_SAT_STEPS in the environment, tests and measurements only: no saturation exit, and
+        // the steps between its checkpoints)
+        b->sat_steps = NRA_SAT_EXIT ? NRA_SAT_STEPS : -1;
+        if (const char* e = getenv("NRA_TEST_SAT_STEPS")) if (NRA_SAT_EXIT) b->sat_steps = std::max(0, atoi(e));
+        if (const char* e = getenv("NRA_TEST_SAT")) if (atoi(e) == 0) b->sat_steps = -1;
         if (!qlist.empty()) {
             HIP_TRY(b->q_list.upload(qlist));
             b->q_arrivals_off = (1 + b->buckets.size() + 3) / 4 * 4;
@@ -1520,7 +1532,8 @@ int nra_batch1d_create(int device, const nra_region_t* regions, int32_t n_region
         static const bool kFlushWritesAll[F_COUNT] = {
             true,       // k_sweep_ring      (sweep_ring_body)
             true,       // k_sweep_ring32    (sweep_ring_body, HALF)
-            true,       // k_sweep_ringq     (sweep_ring_body, QUANTA: the part that ends the forward sweep flushes the rest)
+            true,       // k_sweep_ringq     (sweep_ring_body, QUANTA: the part that ends the forward sweep flushes the rest;
+                        //                    the saturation exit flushes and writes every count from kcur to the task's kmax)
             true,       // k_sweep_ringmt    (the last row block's wave)
             true,       // k_sweep_ringchain (the last row block)
             true,       // k_sweep_pk16      (sweep_body; CHAIN: the last row block)
@@ -1559,15 +1572,17 @@ int nra_batch1d_create(int device, const nra_region_t* regions, int32_t n_region
     else HIP_TRY(b->queue_tasks.alloc(queue_total));
     HIP_TRY(b->queue_count.upload(queue_count));
     {
-        // the words of a run: [q_words | the row blocks' give-up word | tie_count | redo], zero before any run too (so that
-        // nra_batch1d_resweeps reads no flag of a run that has not happened)
-        const size_t n_redo = b->redo.n, n_words = b->q_words_n + 1 + std::max<size_t>(nb, 1) + n_redo;
+        // the words of a run: [q_words | the row blocks' give-up word | tie_count | sat_count | redo], zero before any run too
+        // (so that nra_batch1d_resweeps and nra_batch1d_saturation read nothing of a run that has not happened)
+        const size_t n_redo = b->redo.n, n_words = b->q_words_n + 1 + 5 * std::max<size_t>(nb, 1) + 1 + n_redo;
         HIP_TRY(b->run_words.alloc(n_words));
         int32_t* w = b->run_words.p;
         auto view = [&](DevBuf<int32_t>& buf, size_t n) { buf.p = w; buf.n = n; buf.owned = false; w += n; };
         view(b->q_words, b->q_words_n);
         b->mt_giveup = w++;
         view(b->tie_count, std::max<size_t>(nb, 1));
+        if (reinterpret_cast<uintptr_t>(w) & 7) ++w;                     // (the 64-bit step counts of sat_count: 8-byte aligned)
+        view(b->sat_count, 4 * std::max<size_t>(nb, 1));
         view(b->redo, n_redo);
         HIP_TRY(hipMemsetAsync(b->run_words.p, 0, n_words * 4, b->stream));
         HIP_TRY(hipStreamSynchronize(b->stream));
@@ -1705,7 +1720,7 @@ static int run_1d(nra_batch* b)
                                                   b->q_state.p + bk.q_state_off, b->sweep_tasks.p + bk.sweep_off, b->reads.p,
                                                   b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p, b->kmax.p,
                                                   b->coff.p, b->snap.p, b->read_a1d.p, b->cand_score.p, b->cand_flag.p,
-                                                  bk.taint ? b->relax_c : 0, redo));
+                                                  bk.taint ? b->relax_c : 0, redo, b->sat_steps, b->sat_count.p + 4 * i));
                 if (bk.taint) LAUNCH_TRY(resweep(bk, q, redo));
                 HIP_TRY(hipEventRecord(b->ev[ev++], q));
                 HIP_TRY(hipEventRecord(b->ev[ev++], q));
@@ -3901,6 +3916,33 @@ int nra_batch1d_resweeps(nra_batch_t* b, int64_t* tasks, int64_t* reads, int64_t
     if (reads) *reads = nr;
     if (tasks_total) *tasks_total = tt;
     if (reads_total) *reads_total = tr;
+    return NRA_OK;
+}
+
+int nra_batch1d_saturation(nra_batch_t* b, int64_t* sweeps, int64_t* steps, int64_t* sweeps_total, int64_t* steps_total)
+{
+    if (!b || b->kind != 1) return fail(NRA_E_ARG, "nra_batch1d_saturation needs a 1D batch");
+    int64_t ns = 0, nst = 0, ts = 0, tst = 0;
+    bool any = false;
+    for (const Bucket& bk : b->buckets) any = any || bk.quanta;
+    if (any) {
+        HIP_TRY(hipSetDevice(b->device));
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        std::vector<int32_t> w(b->sat_count.n);
+        HIP_TRY(hipMemcpy(w.data(), b->sat_count.p, w.size() * 4, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < b->buckets.size(); ++i) {
+            const Bucket& bk = b->buckets[i];
+            if (!bk.quanta) continue;
+            ts += bk.n_sweep; tst += bk.q_fwd_steps;
+            int64_t steps64;
+            memcpy(&steps64, &w[4 * i + 2], 8);
+            ns += w[4 * i]; nst += steps64;
+        }
+    }
+    if (sweeps) *sweeps = ns;
+    if (steps) *steps = nst;
+    if (sweeps_total) *sweeps_total = ts;
+    if (steps_total) *steps_total = tst;
     return NRA_OK;
 }
 

@@ -596,6 +596,19 @@ int nra_launch_sweep_ring_fwd(int R, int has_n, int half, hipStream_t st, int n_
 #define NRA_Q_CUT(jfirst) ((jfirst) < 0 ? 0 : (jfirst) / 64 * 64)      /* a forward sweep's first cut: before its first boundary step */
 #define NRA_Q_WHOLE (1 << 30)   // "steps of a part" of a batch too small for more cuts (longer than any sweep): a reverse sweep, a forward sweep to
                                 // its first cut, the rest
+// The saturation exit: a forward sweep whose wave state repeats from one unit boundary to the next ends there and
+// writes the last emission for every repeat count left.  The exiting wave sets the sweep's forward arrival word to
+// NRA_Q_FINISHED, which no count of parts reaches: the sweep's later parts leave at their poll.  sat_steps: the state is
+// compared m steps behind a part's start and, > 0, m steps behind a checkpoint every so many steps; < 0: no exit.
+// sat_count: four words of the run per bucket, 8-byte aligned: [0] sweeps that left, [2..3] the steps they skipped (64 bits).
+#ifndef NRA_SAT_EXIT
+#define NRA_SAT_EXIT 1           // 0: the body without the check, as before it
+#endif
+#ifndef NRA_SAT_STEPS
+#define NRA_SAT_STEPS 192        // steps between the checkpoints inside a part (0: a part's start only).  Config 2, ms per step,
+                                 // medians of 7: no exit 4.41; 0: 4.29; 128: 4.33; 192: 4.26 (a checkpoint a never-repeating sweep stores is lost time)
+#endif
+#define NRA_Q_FINISHED (1 << 30)
 #define NRA_Q_STEPS_REV(l3, half) ((l3) + ((half) ? 31 : 63))
 #define NRA_Q_STEPS_FWD(l1, m, kmax, half) ((l1) + (m) * (kmax) + ((half) ? 31 : 63) * (m))
 int nra_launch_sweep_ringq(int R, int has_n, int half, hipStream_t st, int n_quanta, const uint32_t* qlist, int qsteps, int n_tasks, int32_t* ticket,
@@ -603,7 +616,8 @@ int nra_launch_sweep_ringq(int R, int has_n, int half, hipStream_t st, int n_qua
                            const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
                            const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
                            const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                           int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo);
+                           int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo,
+                           int sat_steps, int32_t* sat_count);
 
 // chained LDS-ring sweeps (k_sweep_ringchain): reads of more than NRA_RING_CHAIN_MIN_ROWS rows as row blocks of
 // 64 * NRA_RING_CHAIN_R; wide = 0: two reads per wave in packed int16, 1: one read per wave in int32 cells.

@@ -456,12 +456,33 @@ __device__ __forceinline__ int qstate_get(int i, const int (&Hq)[R], const int (
 {
     return i < R ? Hq[i] : i < 2 * R ? Hq2[i - R] : i < 3 * R ? E[i - 2 * R] : i < 4 * R ? E2[i - 3 * R] : i == 4 * R ? Hup_prev : i == 4 * R + 1 ? M : 0;
 }
-template <int R>
+// (LEAN: between two runs of a step loop, where the whole wave state and the R side are live -- 8-byte pieces one at a time,
+// so that what is in flight costs two registers and not thirty-two: at R = 4 two more would cost the kernel a wave)
+template <int R, bool LEAN = false>
 __device__ __forceinline__ void qstate_store(int32_t* __restrict__ q, const int (&Hq)[R], const int (&Hq2)[R], const int (&E)[R],
                                              const int (&E2)[R], int Hup_prev, int M, const int4* ring, const int2* racc,
                                              int out_a, int out_b, int lane)
 {
     constexpr int NR = (4 * R + 2 + 3) / 4;            // 16-byte pieces of the registers; the ring's places follow, then the outputs
+    if constexpr (LEAN) {
+        int l = lane;
+#pragma unroll
+        for (int i = 0; i < 2 * NR; ++i) {
+            asm volatile("" : "+v"(l));
+            reinterpret_cast<int2*>(q + (size_t)l * NRA_QSTATE_INTS(R))[i] =
+                make_int2(qstate_get<R>(2 * i, Hq, Hq2, E, E2, Hup_prev, M), qstate_get<R>(2 * i + 1, Hq, Hq2, E, E2, Hup_prev, M));
+        }
+#pragma unroll
+        for (int h = 0; h < 2 * SWEEP_RING_D; ++h) {
+            asm volatile("" : "+v"(l));
+            reinterpret_cast<int2*>(q + (size_t)l * NRA_QSTATE_INTS(R))[2 * NR + h] =
+                reinterpret_cast<const int2*>(ring + (h >> 1) * 64 + l)[h & 1];
+        }
+        asm volatile("" : "+v"(l));
+        reinterpret_cast<int2*>(q + (size_t)l * NRA_QSTATE_INTS(R))[2 * (NR + SWEEP_RING_D)] = make_int2(out_a, out_b);
+        reinterpret_cast<int2*>(q + (size_t)l * NRA_QSTATE_INTS(R))[2 * (NR + SWEEP_RING_D) + 1] = racc[l];
+        return;
+    }
     int4* __restrict__ q4 = reinterpret_cast<int4*>(q + (size_t)lane * NRA_QSTATE_INTS(R));
 #pragma unroll
     for (int i = 0; i < NR; ++i)
@@ -498,6 +519,36 @@ __device__ __forceinline__ void qstate_load(const int32_t* __restrict__ q, int (
             else if (k == 4 * R + 1) M = v[c];
         }
     }
+}
+// The saturation check: is the wave state, bit for bit in every lane, the one `q` holds -- the words of
+// qstate_store but the pending outputs?  8-byte loads, xor / or into one word per lane, one ballot.  The whole wave
+// state is live here, so the pieces go one after the other, two registers in flight: each load's offset is made to
+// depend on the word so far (an empty asm), or the compiler issues all loads first and keeps a hundred registers in
+// flight.  tools/ringq_registers.py holds every instantiation's registers and waves against the body without the check.
+template <int R>
+__device__ __forceinline__ bool qstate_equal(const int32_t* __restrict__ q, const int (&Hq)[R], const int (&Hq2)[R], const int (&E)[R],
+                                             const int (&E2)[R], int Hup_prev, int M, const int4* ring, const int2* racc, int lane)
+{
+    constexpr int NR = (4 * R + 2 + 3) / 4;
+    int d = 0, l = lane;
+#pragma unroll
+    for (int i = 0; i < 2 * NR; ++i) {
+        asm volatile("" : "+v"(l), "+v"(d));
+        const int2 x = reinterpret_cast<const int2*>(q + (size_t)l * NRA_QSTATE_INTS(R))[i];
+        d |= (x.x ^ qstate_get<R>(2 * i, Hq, Hq2, E, E2, Hup_prev, M)) | (x.y ^ qstate_get<R>(2 * i + 1, Hq, Hq2, E, E2, Hup_prev, M));
+    }
+#pragma unroll
+    for (int h = 0; h < 2 * SWEEP_RING_D; ++h) {
+        asm volatile("" : "+v"(l), "+v"(d));
+        const int2 x = reinterpret_cast<const int2*>(q + (size_t)l * NRA_QSTATE_INTS(R))[2 * NR + h];
+        const int2 y = reinterpret_cast<const int2*>(ring + (h >> 1) * 64 + l)[h & 1];
+        d |= (x.x ^ y.x) | (x.y ^ y.y);
+    }
+    asm volatile("" : "+v"(l), "+v"(d));
+    const int2 o = reinterpret_cast<const int2*>(q + (size_t)l * NRA_QSTATE_INTS(R))[2 * (NR + SWEEP_RING_D) + 1];
+    const int2 acc = racc[l];
+    d |= (o.x ^ acc.x) | (o.y ^ acc.y);
+    return __builtin_amdgcn_ballot_w64(d != 0) == 0;
 }
 // the forward sweep's wave-uniform counters at step s (what the loop below would have counted up to there): boundary steps
 // so far, the next repeat count lane LAG + 1 puts out, outputs waiting for their flush of W
@@ -552,7 +603,7 @@ __device__ __forceinline__ void sweep_rside_taint(const int (&Hq)[R], const int 
 // place among them and hoff the pair's first lane.  Rows, ring places and boundary accumulators are a pair's own: the
 // pair's last lane hands out what enters its first.
 template <int R, bool HAS_N, bool HALF, int DIR, bool COMB, bool QUANTA, bool TAINT>
-__device__ __forceinline__ void sweep_ring_body(const int task, const int lane, int4* ring, int2* racc,
+__device__ __forceinline__ int sweep_ring_body(const int task, const int lane, int4* ring, int2* racc,
                                                 const NraSweepTask* __restrict__ tasks,
                                                 const NraDevRead* __restrict__ reads,
                                                 const NraDevRegion* __restrict__ regions,
@@ -569,9 +620,11 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
                                                 uint8_t* __restrict__ cand_flag,
                                                 int32_t* __restrict__ qs, const int s_begin, const int s_end,
                                                 const bool load, const bool store, const int relax_c,
-                                                int32_t* __restrict__ redo)
+                                                int32_t* __restrict__ redo, const int sat_steps = -1)
 {
     static_assert(DIR == 1 || !COMB, "only a forward sweep meets unit boundaries");
+    constexpr bool SAT = NRA_SAT_EXIT != 0 && QUANTA && COMB;     // the saturation exit (below); sat_steps < 0: off
+    constexpr int SAT_NEVER = 0x7fffffff;
     constexpr int SC = TAINT ? 4 : 2;     // origin-bit scheme: doubled scores; TAINT: 4 * score + 2 * taint + origin
     constexpr int W = HALF ? 32 : 64;
     const int hoff = HALF ? lane & 32 : 0;
@@ -728,8 +781,38 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
         pcnt = sx % m;
     }
     if (TAINT && sx == s_relax && sx < s1) sweep_relax_switch<R>(Hq, Hq2, E, E2, v_o2 - v_o1);
+    // The saturation exit (SAT).  The wave is a deterministic machine whose only input, the column tables
+    // lane W - 1 hands out, has period m between the columns |L| and ncols.  If its state at the top of step b + m is
+    // the state at the top of step b (the `base`) bit for bit -- registers, ring places, boundary accumulators, the
+    // running maximum among them --, every later state repeats with period m, and every repeat count still to leave
+    // gets the value of the last emission: the sweep ends here (behind the loop).  A base is the state this part
+    // loaded (still in `qs`) or, every sat_steps steps, a checkpoint stored there (the slot is free between this
+    // part's load and its store), and with them the last base there is, ncols - 2 m, so that a sweep whose state
+    // repeats at all leaves somewhere.  Bases, all wave-uniform: lane W - 1 inside the repeat (b >= |L| + (W - 1) m), an
+    // emission in (b, b + m] (b + m > the step of the first one), every column held or handed out in both windows
+    // below ncols (b + 2 m <= ncols), and the compare inside this part with a step left to skip.
+    int sat_evt = SAT_NEVER, sat_skip = 0;                  // the step of the next event; steps skipped on exit
+    bool sat_cmp = false;                                   // the next event compares (else: stores a checkpoint)
+    const int sat_every = sat_steps > 0 ? imax(sat_steps, 64) : 0;
+    const int sat_hi = imin(ncols - 2 * m, s1 - 1 - m);     // the last base worth having
+    auto sat_next = [&](int from) {                         // the first base at or behind step `from` (> s0)
+        int b = SAT_NEVER;
+        if (sat_every > 0) {
+            b = s0 + imax(1, (from - s0 + sat_every - 1) / sat_every) * sat_every;
+            if (ncols - 2 * m >= from && ncols - 2 * m < b) b = ncols - 2 * m;
+        }
+        return b <= sat_hi ? b : SAT_NEVER;
+    };
+    if (SAT && sat_steps >= 0) {
+        const int sat_lo = imax(flank, jfirst + 1 - m) + (W - 1) * m;
+        if (load && sx == s0 && s0 >= sat_lo && s0 <= sat_hi) { sat_evt = s0 + m; sat_cmp = true; }
+        else sat_evt = sat_next(imax(sat_lo, sx + 1));
+    }
+    // (the events sit between runs of the step loop, not in it: the loop is the one of a body without the check)
+    for (int s_from = sx;;) {
+      const int s_to = SAT ? imin(s1, sat_evt) : s1;
 #pragma unroll 1
-    for (int step = sx; step < s1; ++step) {
+    for (int step = s_from; step < s_to; ++step) {
         // lane W - 1 hands out column step + skew.  (Both halves sweep the same template: the column tables repeat
         // with period 32 across the wave, and a full-wave rotation keeps them so.)
         if ((step & (W - 1)) == 0) feed = column_table(step + skew + nx);
@@ -795,6 +878,39 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
             if (++pcnt == m) pcnt = 0;
         }
     }
+      if (!SAT || s_to >= s1) break;
+      if (sat_cmp) {
+          if (qstate_equal<R>(qs, Hq, Hq2, E, E2, Hup_prev, M, ring, racc, lane)) { sat_skip = nsteps - s_to; break; }
+          sat_evt = sat_next(s_to);
+          sat_cmp = false;
+      } else {
+          qstate_store<R, true>(qs, Hq, Hq2, E, E2, Hup_prev, M, ring, racc, out_a, out_b, lane);
+          sat_evt = s_to + m; sat_cmp = true;
+      }
+      s_from = s_to;
+    }
+    if (SAT && sat_skip > 0) {
+        // the exit: the pending outputs as `flush` writes them, then the last emission -- it sits in lane W - 1 of each
+        // pair, the outputs rotate on emissions only -- for every repeat count from kcur on, through the same per-read
+        // window filter, W candidates per store: this family keeps writing every candidate (NRA_LEAN_CLEARS).  The
+        // repeated value raised redo[task] when it was emitted, if it is tainted.
+        const int va = __builtin_amdgcn_ds_bpermute((hoff | (W - 1)) << 2, out_a);
+        const int vb = __builtin_amdgcn_ds_bpermute((hoff | (W - 1)) << 2, out_b);
+        if (n_out > 0) flush(n_out);
+        for (int k = kcur + hl; k <= tk.kmax && half_on; k += W) {
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                if (s2 == 1 && !has_b) break;
+                const int lo_k = s2 ? kmin_b : kmin_a, hi_k = s2 ? kmax_b : kmax_a;
+                if (k < lo_k || k > hi_k) continue;
+                const uint32_t idx = (s2 ? coff_b : coff_a) + (uint32_t)(k - lo_k);
+                const int v = s2 ? vb : va;
+                cand_score[idx] = v >> 2;
+                cand_flag[idx] = (uint8_t)(v & 3);
+            }
+        }
+        return sat_skip;
+    }
     if (QUANTA && store) {
         qstate_store<R>(qs, Hq, Hq2, E, E2, Hup_prev, M, ring, racc, out_a, out_b, lane);
     } else if (DIR == 0) {
@@ -809,6 +925,7 @@ __device__ __forceinline__ void sweep_ring_body(const int task, const int lane, 
     } else if (COMB && n_out > 0) {
         flush(n_out);
     }
+    return 0;
 }
 
 // relax_c, redo: TAINT -- the margin c of the relaxed steps, and the per-task flags the sweep sets where a relaxed cell
@@ -903,14 +1020,19 @@ __global__ __launch_bounds__(WAVE) void k_sweep_ring32(int n_tasks, const NraSwe
 // (waves per SIMD as the forward sweep alone: without the hint the merged body takes 226 registers at R = 15 where
 // k_sweep_ring's forward sweep takes 156; with it 168 and a few spilled values in the prologues -- the R side's
 // constants while the state is loaded --, none in a step loop)
-constexpr int ringq_waves(int R)
+// (A hint the kernel cannot meet is no target at all: the half-wave body at R = 5, asked for 6 waves, sits at 126
+// registers, two below the fourth wave's limit, and drifted to 130 - 132 with the saturation events around its step loop;
+// asked for the 4 it can have it takes 124.  tools/ringq_registers.py compares every instantiation with the body without
+// the events.)
+constexpr int ringq_waves(int R, bool half)
 {
+    if (half && R == 5) return 4;
     const int w = 512 / (9 * R + 30);
     return w < 1 ? 1 : (w > 8 ? 8 : w);
 }
 
 template <int R, bool HAS_N, bool HALF, bool TAINT>                  // relax_c, redo: TAINT as in k_sweep_ring
-__global__ __launch_bounds__(WAVE, ringq_waves(R)) void k_sweep_ringq(int n_quanta, const uint32_t* __restrict__ qlist, int qsteps, int n_tasks,
+__global__ __launch_bounds__(WAVE, ringq_waves(R, HALF)) void k_sweep_ringq(int n_quanta, const uint32_t* __restrict__ qlist, int qsteps, int n_tasks,
                                                       int32_t* ticket, int32_t* arrivals, int32_t* giveup,
                                                       int32_t* __restrict__ qstate,
                                                       const NraSweepTask* __restrict__ tasks,
@@ -926,7 +1048,8 @@ __global__ __launch_bounds__(WAVE, ringq_waves(R)) void k_sweep_ringq(int n_quan
                                                       int32_t* __restrict__ snap,
                                                       int32_t* __restrict__ read_a,
                                                       int32_t* __restrict__ cand_score,
-                                                      uint8_t* __restrict__ cand_flag, int relax_c, int32_t* __restrict__ redo)
+                                                      uint8_t* __restrict__ cand_flag, int relax_c, int32_t* __restrict__ redo,
+                                                      int sat_steps, int32_t* sat_count)
 {
     __shared__ int4 ring[SWEEP_RING_D * 64];
     __shared__ int2 racc[64];
@@ -955,12 +1078,16 @@ __global__ __launch_bounds__(WAVE, ringq_waves(R)) void k_sweep_ringq(int n_quan
     int32_t* mine = arrivals + 2 * (size_t)task + dir;
     const int32_t* rev = arrivals + 2 * (size_t)task;
     if (load || comb) {
+        bool finished = false;
         for (unsigned spins = 0;; ++spins) {
-            int ok = 0;
-            if (lane == 0)
-                ok = (!load || __hip_atomic_load(mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= part) &&
-                     (!comb || __hip_atomic_load(rev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= need_rev);
-            if (__builtin_amdgcn_readfirstlane(ok)) break;
+            int ok = 0;                                     // 2: the sweep is over (NRA_Q_FINISHED)
+            if (lane == 0) {
+                const int before = load ? __hip_atomic_load(mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+                ok = before >= NRA_Q_FINISHED ? 2
+                   : before >= part && (!comb || __hip_atomic_load(rev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= need_rev);
+            }
+            ok = __builtin_amdgcn_readfirstlane(ok);
+            if (ok) { finished = ok == 2; break; }
             __builtin_amdgcn_s_sleep(64);
             if ((spins & 15) == 15) {
                 int failed = 0;
@@ -972,18 +1099,32 @@ __global__ __launch_bounds__(WAVE, ringq_waves(R)) void k_sweep_ringq(int n_quan
                 }
             }
         }
+        // the sweep left through the saturation exit in an earlier part: nothing to load, no arrival to add
+        if (finished) return;
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     }
     // a slot per forward sweep, then -- where a reverse sweep has more than one part -- one per reverse sweep
     int32_t* __restrict__ qs = qstate + ((size_t)(dir ? 0 : n_tasks) + (size_t)task) * (NRA_QSTATE_INTS(R) * 64);
 #define NRA_Q_ARGS task, lane, ring, racc, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin_arr, kmax_arr, coff, snap, read_a, cand_score, cand_flag, qs, s_begin, s_end, load, store, relax_c, redo
+    int skipped = 0;                                        // wave-uniform: steps the saturation exit left out
     if (!dir) sweep_ring_body<R, HAS_N, HALF, 0, false, true, TAINT>(NRA_Q_ARGS);
     else if (!comb) sweep_ring_body<R, HAS_N, HALF, 1, false, true, TAINT>(NRA_Q_ARGS);
-    else sweep_ring_body<R, HAS_N, HALF, 1, true, true, TAINT>(NRA_Q_ARGS);
+    else skipped = sweep_ring_body<R, HAS_N, HALF, 1, true, true, TAINT>(NRA_Q_ARGS, sat_steps);
 #undef NRA_Q_ARGS
     // everything this wave stored -- the wave state at the cut, or the R side's snapshot and A -- before the arrival
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    if (lane == 0) __hip_atomic_fetch_add(mine, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0) {
+        if (skipped > 0) {
+            // the sweep is over: a value no count of parts reaches tells its later parts to leave (the poll above)
+            __hip_atomic_store(mine, NRA_Q_FINISHED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_add(sat_count, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            // (the steps in 64 bits: 8192 sweeps of a few hundred thousand steps each would pass 2^31)
+            __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(sat_count + 2), (unsigned long long)skipped, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+        } else {
+            __hip_atomic_fetch_add(mine, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------
@@ -1602,10 +1743,11 @@ int launch_sweep_ringq(int R, int has_n, hipStream_t st, int n_quanta, const uin
                        const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
                        const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
                        const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                       int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo)
+                       int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo,
+                       int sat_steps, int32_t* sat_count)
 {
     if (n_quanta <= 0) return 0;
-#define ARGS n_quanta, qlist, qsteps, n_tasks, ticket, arrivals, giveup, qstate, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag, relax_c, redo
+#define ARGS n_quanta, qlist, qsteps, n_tasks, ticket, arrivals, giveup, qstate, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag, relax_c, redo, sat_steps, sat_count
 #define CASE(r)                                                                                                          \
     case r:                                                                                                              \
         if constexpr (HALF && r > NRA_RING32_MAX_R) return (int)hipErrorInvalidValue;                                   \
@@ -1674,12 +1816,13 @@ extern "C" int nra_launch_sweep_ringq(int R, int has_n, int half, hipStream_t st
                                       const NraSweepTask* tasks, const NraDevRead* reads, const NraDevRegion* regions,
                                       const uint8_t* pool, const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
                                       const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                      int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo)
+                                      int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo,
+                                      int sat_steps, int32_t* sat_count)
 {
     return (half ? launch_sweep_ringq<true> : launch_sweep_ringq<false>)(R, has_n, st, n_quanta, qlist, qsteps, n_tasks, ticket, arrivals,
                                                                           giveup, qstate, tasks, reads, regions, pool, q2bit, qnmask,
                                                                           sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag,
-                                                                          relax_c, redo);
+                                                                          relax_c, redo, sat_steps, sat_count);
 }
 #endif
 
