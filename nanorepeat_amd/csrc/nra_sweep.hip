@@ -125,6 +125,99 @@ __device__ __forceinline__ void sweep_snapshot_lane(const int (&Hq)[R], const in
     for (int i = 0; i < N4; ++i) p4[i] = make_int4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
 }
 
+// ------------------------------------------------------------------------------------
+// fragments the sweep bodies share
+// ------------------------------------------------------------------------------------
+// The score constants of a sweep whose cells hold SC * score (+ payload bits in the low ones): WIDE = plain int32
+// cells without a bias, otherwise the two biased int16 halves of a register.
+template <int SC, bool WIDE>
+struct SweepScores {
+    static constexpr int BIASW = WIDE ? 0 : BIAS;
+    static constexpr int P1 = WIDE ? 1 : 0x00010001;
+    int o1;
+    int v_floor;                          // max(H,0) - o1 (even: the payload bits are free)
+    int v_o1, v_e1, v_o2, v_e2;
+    int NEG1, NEG2;                       // "minus infinity", biased once / twice
+    int s_match, s_mis;                   // substitution scores + o1 (the diagonal is read from Hq = H - o1): all in [0, 127]
+    int tbl_hi;                           // selector 4: padding row, 5: N in the read
+    int tbl_mis4, tbl_ambi4;
+    __device__ __forceinline__ explicit SweepScores(const NraScoreParams& sp)
+    {
+        o1 = SC * sp.open1;
+        const int o2 = SC * sp.open2;
+        v_floor = (BIASW - o1) * P1;
+        v_o1 = o1 * P1; v_e1 = SC * sp.ext1 * P1; v_o2 = o2 * P1; v_e2 = SC * sp.ext2 * P1;
+        NEG1 = WIDE ? -(1 << 28) : NEGB * P1;
+        NEG2 = WIDE ? -(1 << 28) : 2 * NEGB * P1;
+        s_match = SC * sp.match + o1; s_mis = o1 - SC * sp.mismatch;
+        const int s_ambi = o1 - SC * sp.ambi;
+        tbl_hi = s_mis | (s_ambi << 8);
+        tbl_mis4 = s_mis * 0x01010101; tbl_ambi4 = s_ambi * 0x01010101;
+    }
+};
+
+// the substitution table (+ flags) of template column `col` of the LDS-ring sweeps; padding outside the template
+template <int DIR, class Scores>
+__device__ __forceinline__ int sweep_column_table(const Scores& sc, const uint8_t* __restrict__ piece, int ncols, int flank, int col)
+{
+    int t = sc.tbl_mis4;
+    if (col >= 0 && col < ncols) {
+        const int code = piece[col];
+        t = code < 4 ? sc.tbl_mis4 + ((sc.s_match - sc.s_mis) << (8 * code)) : sc.tbl_ambi4;
+        if (DIR == 0 && col == flank - 1) t |= FLAG_SNAPSHOT;
+        if (DIR == 1 && col + 1 >= flank) t |= FLAG_INREP;         // origin bit of an alignment starting at the NEXT column
+    }
+    return t;
+}
+
+// One emission: Score(k) and the flank verdict of one read from the boundary accumulators S and B of its last row
+// (wide, or half s2 of the packed pair) and A + 1 = a1, as (score << 2) | verdict, score -1 below min_dp_score.
+template <bool WIDE>
+__device__ __forceinline__ int sweep_emit(int accS, int accB, int s2, int a1, int min_score)
+{
+    constexpr int BIASW = WIDE ? 0 : BIAS;
+    const int B = (WIDE ? accB : (s2 ? half_hi(accB) : half_lo(accB))) - BIASW;
+    const int S = (WIDE ? accS : (s2 ? half_hi(accS) : half_lo(accS))) - 2 * BIASW;
+    const int lo = min_score > 1 ? min_score : 1;
+    // packed 2*score + origin bit; an alignment inside R starts at a column >= |L|
+    const int V = imax(imax(S, B), a1);
+    const int best = V >> 1;
+    int flag = 1;
+    if (V & 1) flag = 0;                                                  // an optimal alignment starts at >= |L|
+    else if ((B >> 1) >= best) flag = ((S >> 1) >= best) ? 2 : 0;         // one ends inside L+unit^k
+    return ((best >= lo ? best : -1) << 2) | flag;
+}
+
+// The candidate store.  Score(k) and the flank verdict leave through lane 63, one boundary column at a time.  They
+// are collected in a lane-indexed register -- rotated one lane down per boundary, the newest value in lane 63 -- and
+// written 64 candidates at a time, one coalesced line per read.
+struct SweepCands {                       // a pair's windows of repeat counts and where each read's candidates start
+    bool has_b;
+    int kmin_a, kmax_a, kmin_b, kmax_b;
+    uint32_t coff_a, coff_b;
+    __device__ __forceinline__ SweepCands(int ra, int rb, bool has_b_, const int32_t* __restrict__ kmin_arr,
+                                          const int32_t* __restrict__ kmax_arr, const uint32_t* __restrict__ coff)
+        : has_b(has_b_), kmin_a(kmin_arr[ra]), kmax_a(kmax_arr[ra]), kmin_b(kmin_arr[rb]), kmax_b(kmax_arr[rb]),
+          coff_a(coff[ra]), coff_b(coff[rb]) {}
+};
+// lane l holds k = kcur - 64 + l; the oldest n_valid values sit in lanes [64 - n_valid, 64); each read has its own window
+__device__ __forceinline__ void sweep_flush(const SweepCands& c, int n_valid, int kcur, int lane, int out_a, int out_b,
+                                            int32_t* __restrict__ cand_score, uint8_t* __restrict__ cand_flag)
+{
+    const int k = kcur - 64 + lane;
+    if (lane < 64 - n_valid) return;
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+        if (s2 == 1 && !c.has_b) break;
+        const int lo_k = s2 ? c.kmin_b : c.kmin_a, hi_k = s2 ? c.kmax_b : c.kmax_a;
+        if (k < lo_k || k > hi_k) continue;
+        const uint32_t idx = (s2 ? c.coff_b : c.coff_a) + (uint32_t)(k - lo_k);
+        const int v = s2 ? out_b : out_a;
+        cand_score[idx] = v >> 2;                           // (score << 2) | verdict; -1: below min_dp_score
+        cand_flag[idx] = (uint8_t)(v & 3);
+    }
+}
+
 // CHAIN = the WIDE sweeps: reads longer than one register block (3072 bases) are swept as consecutive row
 // blocks of 64*R rows by one wave, ONE read per wave in plain int32 cells (2*score + origin bit: no range
 // limit worth naming), the last cell of a block leaving its per-column hand-off in a scratch strip that
@@ -162,43 +255,16 @@ __device__ __forceinline__ void sweep_dpp_task(int task, const NraSweepTask* __r
     const int ncols = DIR == 0 ? flank : flank + m * tk.kmax;
     // boundary column of k = kmin (>= 0: flank >= 1); the reverse sweep has one: R[0]
     const int jfirst = DIR == 0 ? flank - 1 : flank + m * tk.kmin - 1;
-    const int kmin_a = kmin_arr[ra], kmax_a = kmax_arr[ra];
-    const int kmin_b = kmin_arr[rb], kmax_b = kmax_arr[rb];
-    const uint32_t coff_a = coff[ra], coff_b = coff[rb];
+    const SweepCands cands(ra, rb, has_b, kmin_arr, kmax_arr, coff);
     int32_t* __restrict__ snap_task = snap + tk.snap_off;
+    const SweepScores<SC, W> sc(sp);
+    constexpr int P1 = SweepScores<SC, W>::P1;
 
-    const int o1 = SC * sp.open1, o2 = SC * sp.open2;
-    const int P1 = W ? 1 : 0x00010001;
-    const int v_floor = (BIASW - o1) * P1;                  // max(H,0) - o1 (even: the origin bit is free)
-    const int v_o1 = o1 * P1, v_e1 = SC * sp.ext1 * P1, v_o2 = o2 * P1, v_e2 = SC * sp.ext2 * P1;
-    const int NEG1 = W ? -(1 << 28) : NEGB * P1;            // "minus infinity", biased once / twice
-    const int NEG2 = W ? -(1 << 28) : 2 * NEGB * P1;
-    // substitution scores + o1 (the diagonal is read from Hq = H - o1): all in [0, 127]
-    const int s_match = SC * sp.match + o1, s_mis = o1 - SC * sp.mismatch, s_ambi = o1 - SC * sp.ambi;
-    const int tbl_hi = s_mis | (s_ambi << 8);               // selector 4: padding row, 5: N in the read
-    const int tbl_mis4 = s_mis * 0x01010101, tbl_ambi4 = s_ambi * 0x01010101;
-
-    // Score(k) and the flank verdict leave through lane 63, one boundary column at a time.  They
-    // are collected in a lane-indexed register -- rotated one lane down per boundary, the newest value in
-    // lane 63 -- and written 64 candidates at a time, one coalesced line per read.
+    // the outputs (sweep_flush): lane 63 produces one value per boundary
     int out_a = 0, out_b = 0;
     int n_out = 0;                                          // wave-uniform: boundaries collected
     int kcur = tk.kmin;                                     // wave-uniform: k of the next boundary to leave
-    auto flush = [&](int n_valid) {
-        // lane l holds k = kcur - 64 + l; the oldest n_valid values sit in lanes [64 - n_valid, 64)
-        const int k = kcur - 64 + lane;
-        if (lane < 64 - n_valid) return;
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            if (s2 == 1 && !has_b) break;
-            const int lo_k = s2 ? kmin_b : kmin_a, hi_k = s2 ? kmax_b : kmax_a;
-            if (k < lo_k || k > hi_k) continue;
-            const uint32_t idx = (s2 ? coff_b : coff_a) + (uint32_t)(k - lo_k);
-            const int v = s2 ? out_b : out_a;
-            cand_score[idx] = v >> 2;                       // (score << 2) | verdict; -1: below min_dp_score
-            cand_flag[idx] = (uint8_t)(v & 3);
-        }
-    };
+    auto flush = [&](int n_valid) { sweep_flush(cands, n_valid, kcur, lane, out_a, out_b, cand_score, cand_flag); };
 
     // CHAIN: row blocks of 64*R, one after the other in this wave; the strip belongs to the wave (blockIdx)
     const int n_blk = CHAIN ? (imax(rda.qlen, rdb.qlen) + 64 * R - 1) / (64 * R) : 1;
@@ -237,10 +303,10 @@ __device__ __forceinline__ void sweep_dpp_task(int task, const NraSweepTask* __r
                     const int al = w / R, ai = w - al * R;
                     const int32_t* __restrict__ p = snap_task + ((size_t)ablk * 3 * R + ai) * 64 + al;
                     const int vh = p[0], ve = p[R * 64], ve2 = p[2 * R * 64];
-                    h[s] = (W ? vh : (s ? half_hi(vh) : half_lo(vh))) + 2 * o1;    // Hq carries -o1 on either side
+                    h[s] = (W ? vh : (s ? half_hi(vh) : half_lo(vh))) + 2 * sc.o1;    // Hq carries -o1 on either side
                     e[s] = (W ? ve : (s ? half_hi(ve) : half_lo(ve))) + q1;
                     e2[s] = (W ? ve2 : (s ? half_hi(ve2) : half_lo(ve2))) + q2;
-                } else { h[s] = BIASW + o1 - SC; e[s] = BIASW - SC; e2[s] = BIASW - SC; }
+                } else { h[s] = BIASW + sc.o1 - SC; e[s] = BIASW - SC; e2[s] = BIASW - SC; }
             }
             Hbo[i] = W ? h[0] : pack2(h[0], h[1]);
             Ebo[i] = W ? e[0] : pack2(e[0], e[1]);
@@ -250,7 +316,7 @@ __device__ __forceinline__ void sweep_dpp_task(int task, const NraSweepTask* __r
 
     int Hq[R], Hq2[R], E[R], E2[R];
 #pragma unroll
-    for (int i = 0; i < R; ++i) { Hq[i] = v_floor; Hq2[i] = NEG1; E[i] = NEG1; E2[i] = NEG1; }
+    for (int i = 0; i < R; ++i) { Hq[i] = sc.v_floor; Hq2[i] = sc.NEG1; E[i] = sc.NEG1; E2[i] = sc.NEG1; }
 
     // Every lane hosts TWO virtual systolic cells -- A = its first RA rows, B = the other RB --
     // one template column apart (cell v works on column t - v, lane l hosts cells 2l and 2l+1).
@@ -258,33 +324,33 @@ __device__ __forceinline__ void sweep_dpp_task(int task, const NraSweepTask* __r
     // step carries two independent dependency chains per wave: the sweeps run with only a few
     // waves per SIMD and need the instruction-level parallelism.
     constexpr int RA = (R + 1) / 2, RB = R - RA;
-    int HbotA = v_floor, FoutA = NEG1, F2outA = NEG1, HupA_prev = v_floor, MA = BIASW * P1;
-    int HbotB = v_floor, FoutB = NEG1, F2outB = NEG1, HupB_prev = v_floor, MB = BIASW * P1;
-    int accS_A = NEG2, accB_A = NEG1, accS_B = NEG2, accB_B = NEG1;
-    int ttA = tbl_mis4, ttB = tbl_mis4;                   // padding column: everything mismatches
+    int HbotA = sc.v_floor, FoutA = sc.NEG1, F2outA = sc.NEG1, HupA_prev = sc.v_floor, MA = BIASW * P1;
+    int HbotB = sc.v_floor, FoutB = sc.NEG1, F2outB = sc.NEG1, HupB_prev = sc.v_floor, MB = BIASW * P1;
+    int accS_A = sc.NEG2, accB_A = sc.NEG1, accS_B = sc.NEG2, accB_B = sc.NEG1;
+    int ttA = sc.tbl_mis4, ttB = sc.tbl_mis4;                   // padding column: everything mismatches
     n_out = 0; kcur = tk.kmin;
 
     // One flat step loop (128 cells deep; a chunk loop around a 64-step loop costs registers: the
     // compiler keeps the row arrays twice).  Every 64 steps the lanes fetch the next 64 columns.
     const int nsteps = ncols + 127;                       // cell 127 finishes the last column at step ncols + 126
-    int feed = tbl_mis4;
+    int feed = sc.tbl_mis4;
     // what enters cell 0 at each column: constants for the first row block, else the strip
-    int inH = v_floor, inF = NEG1, inF2 = NEG1, inS = NEG2, inB = NEG1;
+    int inH = sc.v_floor, inF = sc.NEG1, inF2 = sc.NEG1, inS = sc.NEG2, inB = sc.NEG1;
 #pragma unroll 1   // two steps per trip would turn the hand-offs into renames but cost ~14 registers
     for (int step = 0; step < nsteps; ++step) {
         {
             if ((step & 63) == 0) {
                 const int col = step + lane;
-                feed = tbl_mis4;
+                feed = sc.tbl_mis4;
                 if (col < ncols) {
                     const int code = piece[col];
-                    feed = code < 4 ? tbl_mis4 + ((s_match - s_mis) << (8 * code)) : tbl_ambi4;
+                    feed = code < 4 ? sc.tbl_mis4 + ((sc.s_match - sc.s_mis) << (8 * code)) : sc.tbl_ambi4;
                     if (col >= jfirst && (col - jfirst) % m == 0) feed |= FLAG_BOUNDARY;
                     if (DIR == 0 && col == flank - 1) feed |= FLAG_SNAPSHOT;
                     if (DIR == 1 && col >= flank) feed |= FLAG_INREP;
                 }
                 if (CHAIN) {
-                    inH = v_floor; inF = NEG1; inF2 = NEG1; inS = NEG2; inB = NEG1;
+                    inH = sc.v_floor; inF = sc.NEG1; inF2 = sc.NEG1; inS = sc.NEG2; inB = sc.NEG1;
                     if (!first_blk && col < ncols) {
                         inH = cin[col]; inF = cin[chain_cap + col]; inF2 = cin[2 * chain_cap + col];
                         inS = cin[3 * chain_cap + col]; inB = cin[4 * chain_cap + col];
@@ -292,13 +358,13 @@ __device__ __forceinline__ void sweep_dpp_task(int task, const NraSweepTask* __r
                 }
             }
             // inputs of cell A: cell B of the lane above, as it stood after the previous step
-            const int hupA = dpp_shr1(CHAIN ? inH : v_floor, HbotB);
-            int FA = dpp_shr1(CHAIN ? inF : NEG1, FoutB);
-            int F2A = dpp_shr1(CHAIN ? inF2 : NEG1, F2outB);
+            const int hupA = dpp_shr1(CHAIN ? inH : sc.v_floor, HbotB);
+            int FA = dpp_shr1(CHAIN ? inF : sc.NEG1, FoutB);
+            int F2A = dpp_shr1(CHAIN ? inF2 : sc.NEG1, F2outB);
             const int ttA_new = dpp_shr1(feed, ttB);      // lane 0 takes the next template column
             feed = dpp_rol1(feed);
-            const int accS_Ain = dpp_shr1(CHAIN ? inS : NEG2, accS_B);
-            const int accB_Ain = dpp_shr1(CHAIN ? inB : NEG1, accB_B);
+            const int accS_Ain = dpp_shr1(CHAIN ? inS : sc.NEG2, accS_B);
+            const int accB_Ain = dpp_shr1(CHAIN ? inB : sc.NEG1, accB_B);
             if (CHAIN) {
                 inH = dpp_rol1(inH); inF = dpp_rol1(inF); inF2 = dpp_rol1(inF2);
                 inS = dpp_rol1(inS); inB = dpp_rol1(inB);
@@ -310,14 +376,14 @@ __device__ __forceinline__ void sweep_dpp_task(int task, const NraSweepTask* __r
             const int accS_Bin = accS_A, accB_Bin = accB_A;
 
             // the empty alignment a path may start from at this column: score 0, origin bit from the flag
-            const int floorA = DIR == 1 ? (int)((((unsigned)ttA_new >> 15) & (unsigned)P1) | (unsigned)v_floor) : v_floor;
-            const int floorB = DIR == 1 ? (int)((((unsigned)ttB_new >> 15) & (unsigned)P1) | (unsigned)v_floor) : v_floor;
-            sweep_cell<0, RA, R, W>(Hq, Hq2, E, E2, qc, HupA_prev, FA, F2A, MA, ttA_new & 0x7f7f7f7f, tbl_hi,
-                                    floorA, v_e1, v_e2, v_o1, v_o2);
+            const int floorA = DIR == 1 ? (int)((((unsigned)ttA_new >> 15) & (unsigned)P1) | (unsigned)sc.v_floor) : sc.v_floor;
+            const int floorB = DIR == 1 ? (int)((((unsigned)ttB_new >> 15) & (unsigned)P1) | (unsigned)sc.v_floor) : sc.v_floor;
+            sweep_cell<0, RA, R, W>(Hq, Hq2, E, E2, qc, HupA_prev, FA, F2A, MA, ttA_new & 0x7f7f7f7f, sc.tbl_hi,
+                                    floorA, sc.v_e1, sc.v_e2, sc.v_o1, sc.v_o2);
             HupA_prev = hupA; HbotA = Hq[RA - 1]; FoutA = FA; F2outA = F2A;
             if (RB > 0) {
-                sweep_cell<RA, RB, R, W>(Hq, Hq2, E, E2, qc, HupB_prev, FB, F2B, MB, ttB_new & 0x7f7f7f7f, tbl_hi,
-                                         floorB, v_e1, v_e2, v_o1, v_o2);
+                sweep_cell<RA, RB, R, W>(Hq, Hq2, E, E2, qc, HupB_prev, FB, F2B, MB, ttB_new & 0x7f7f7f7f, sc.tbl_hi,
+                                         floorB, sc.v_e1, sc.v_e2, sc.v_o1, sc.v_o2);
                 HbotB = Hq[R - 1];
             } else {
                 HbotB = hupB;                             // empty cell: hand everything through
@@ -327,7 +393,7 @@ __device__ __forceinline__ void sweep_dpp_task(int task, const NraSweepTask* __r
 
             const bool atA = (ttA & FLAG_BOUNDARY) != 0, atB = (ttB & FLAG_BOUNDARY) != 0;
             const unsigned long long at_mask = __builtin_amdgcn_ballot_w64(atA || atB);
-            int tSA = NEG2, tSB = NEG2;
+            int tSA = sc.NEG2, tSB = sc.NEG2;
             if constexpr (DIR != 0) {
                 if (at_mask != 0) {
                     tSA = sweep_combine<0, RA, R, W>(Hq, E, E2, Hbo, Ebo, E2bo, tSA);
@@ -648,31 +714,14 @@ __device__ __forceinline__ int sweep_ring_body(const int task, const int lane, i
     const int kmin_b = kmin_arr[rb], kmax_b = kmax_arr[rb];
     const uint32_t coff_a = coff[ra], coff_b = coff[rb];
     int32_t* __restrict__ snap_task = snap + tk.snap_off;
-
-    const int o1 = SC * sp.open1, o2 = SC * sp.open2;
-    const int P1 = 0x00010001;
-    const int v_floor = (BIAS - o1) * P1;
-    const int v_o1 = o1 * P1, v_e1 = SC * sp.ext1 * P1, v_o2 = o2 * P1, v_e2 = SC * sp.ext2 * P1;
-    const int NEG1 = NEGB * P1, NEG2 = 2 * NEGB * P1;
-    const int s_match = SC * sp.match + o1, s_mis = o1 - SC * sp.mismatch, s_ambi = o1 - SC * sp.ambi;
-    const int tbl_hi = s_mis | (s_ambi << 8);
-    const int tbl_mis4 = s_mis * 0x01010101, tbl_ambi4 = s_ambi * 0x01010101;
+    const SweepScores<SC, false> sc(sp);
+    constexpr int P1 = SweepScores<SC, false>::P1;
     // the taint scheme: the steps [0, s_relax) run the relaxed cell; T2 = the taint bit of both halves
     const int s_relax = TAINT ? sweep_relax_steps(flank, relax_c) : 0;
     const int T2 = 2 * P1;
     constexpr int SH = TAINT ? 2 : 1;     // score = state >> SH
 
-    // the substitution table (+ flags) of template column `col`; padding outside the template
-    auto column_table = [&](int col) {
-        int t = tbl_mis4;
-        if (col >= 0 && col < ncols) {
-            const int code = piece[col];
-            t = code < 4 ? tbl_mis4 + ((s_match - s_mis) << (8 * code)) : tbl_ambi4;
-            if (DIR == 0 && col == flank - 1) t |= FLAG_SNAPSHOT;
-            if (DIR == 1 && col + 1 >= flank) t |= FLAG_INREP;     // origin bit of an alignment starting at the NEXT column
-        }
-        return t;
-    };
+    auto column_table = [&](int col) { return sweep_column_table<DIR>(sc, piece, ncols, flank, col); };
 
     // outputs: lane W - 1 of a pair produces one value per boundary; the pair keeps its last W in a lane-indexed register
     // (rotated within the pair) and writes them W candidates at a time
@@ -720,10 +769,10 @@ __device__ __forceinline__ int sweep_ring_body(const int task, const int lane, i
                     const int32_t* __restrict__ p = HALF ? snap_task + (size_t)(hoff + al) * NRA_SNAP_LANE_STRIDE(R) + ai
                                                          : snap_task + (size_t)ai * 64 + al;
                     const int vh = p[0], ve = p[PL], ve2 = p[2 * PL];
-                    h[s] = (s ? half_hi(vh) : half_lo(vh)) + 2 * o1;
+                    h[s] = (s ? half_hi(vh) : half_lo(vh)) + 2 * sc.o1;
                     e[s] = (s ? half_hi(ve) : half_lo(ve)) + q1;
                     e2[s] = (s ? half_hi(ve2) : half_lo(ve2)) + q2;
-                } else { h[s] = BIAS + o1 - SC; e[s] = BIAS - SC; e2[s] = BIAS - SC; }
+                } else { h[s] = BIAS + sc.o1 - SC; e[s] = BIAS - SC; e2[s] = BIAS - SC; }
             }
             Hbo[i] = PARK ? agpr_put(pack2(h[0], h[1])) : pack2(h[0], h[1]);
             Ebo[i] = PARK ? agpr_put(pack2(e[0], e[1])) : pack2(e[0], e[1]);
@@ -732,17 +781,17 @@ __device__ __forceinline__ int sweep_ring_body(const int task, const int lane, i
     }
     int Hq[R], Hq2[R], E[R], E2[R];
 #pragma unroll
-    for (int i = 0; i < R; ++i) { Hq[i] = s_relax > 0 ? v_floor | T2 : v_floor; Hq2[i] = NEG1; E[i] = NEG1; E2[i] = NEG1; }
+    for (int i = 0; i < R; ++i) { Hq[i] = s_relax > 0 ? sc.v_floor | T2 : sc.v_floor; Hq2[i] = sc.NEG1; E[i] = sc.NEG1; E2[i] = sc.NEG1; }
 
     // ring: padding columns everywhere, then the first lane's first `skew` columns
 #pragma unroll
-    for (int s = 0; s < SWEEP_RING_D; ++s) ring[s * 64 + lane] = make_int4(v_floor, NEG1, NEG1, tbl_mis4);
-    racc[lane] = make_int2(NEG2, NEG1);
-    if (hl < skew) ring[hl * 64 + hoff] = make_int4(v_floor, NEG1, NEG1, column_table(hl));
+    for (int s = 0; s < SWEEP_RING_D; ++s) ring[s * 64 + lane] = make_int4(sc.v_floor, sc.NEG1, sc.NEG1, sc.tbl_mis4);
+    racc[lane] = make_int2(sc.NEG2, sc.NEG1);
+    if (hl < skew) ring[hl * 64 + hoff] = make_int4(sc.v_floor, sc.NEG1, sc.NEG1, column_table(hl));
     ring_order();
 
-    int Hup_prev = s_relax > 0 ? v_floor | T2 : v_floor, M = BIAS * P1;      // (tainted, as Hq: the diagonal into row 0)
-    int feed = tbl_mis4;
+    int Hup_prev = s_relax > 0 ? sc.v_floor | T2 : sc.v_floor, M = BIAS * P1;      // (tainted, as Hq: the diagonal into row 0)
+    int feed = sc.tbl_mis4;
     const int nsteps = ncols + (W - 1) * skew;              // lane W - 1 finishes the last column at step ncols - 1 + (W - 1)*skew
     const int nx = (hl + 1) & (W - 1);
     const int wr = hoff | nx;
@@ -764,23 +813,23 @@ __device__ __forceinline__ int sweep_ring_body(const int task, const int lane, i
         // the relaxed steps: columns of the anchor far from the junction (no boundary, snapshot or table flag among
         // them: s_relax <= flank - 64); one gap state per direction, F in both places of the hand-off
         sx = s1 < s_relax ? s1 : s_relax;
-        const int flr = BIAS * P1 | T2, hfl = flr - v_o1, v_er = SC * imin(sp.ext1, sp.ext2) * P1;
+        const int flr = BIAS * P1 | T2, hfl = flr - sc.v_o1, v_er = SC * imin(sp.ext1, sp.ext2) * P1;
 #pragma unroll 1
         for (int step = s0; step < sx; ++step) {
             if ((step & (W - 1)) == 0) feed = column_table(step + skew + nx);
             const int4 in = ring[slot * 64 + lane];
             int F = pmaxi(in.y, flr);
-            sweep_cell_relaxed<R>(Hq, E, qc, Hup_prev, F, M, in.w, tbl_hi, flr, v_er, v_o1);
+            sweep_cell_relaxed<R>(Hq, E, qc, Hup_prev, F, M, in.w, sc.tbl_hi, flr, v_er, sc.v_o1);
             Hup_prev = pmaxi(in.x, hfl);
             ring[slot * 64 + wr] = make_int4(Hq[R - 1], F, F, in.w);
-            if (hl == W - 1) ring[slot * 64 + hoff] = make_int4(v_floor, NEG1, NEG1, feed);
+            if (hl == W - 1) ring[slot * 64 + hoff] = make_int4(sc.v_floor, sc.NEG1, sc.NEG1, feed);
             ring_order();
             feed = dpp_rol1(feed);
             if (++slot == skew) slot = 0;
         }
         pcnt = sx % m;
     }
-    if (TAINT && sx == s_relax && sx < s1) sweep_relax_switch<R>(Hq, Hq2, E, E2, v_o2 - v_o1);
+    if (TAINT && sx == s_relax && sx < s1) sweep_relax_switch<R>(Hq, Hq2, E, E2, sc.v_o2 - sc.v_o1);
     // The saturation exit (SAT).  The wave is a deterministic machine whose only input, the column tables
     // lane W - 1 hands out, has period m between the columns |L| and ncols.  If its state at the top of step b + m is
     // the state at the top of step b (the `base`) bit for bit -- registers, ring places, boundary accumulators, the
@@ -822,10 +871,10 @@ __device__ __forceinline__ int sweep_ring_body(const int task, const int lane, i
         // lane's first row is at the floor already, but for a pair's first lane, which takes constants: one max each
         const int fl = DIR == 1 ? (int)((((unsigned)tt >> 15) & (unsigned)P1) | (unsigned)(BIAS * P1)) : BIAS * P1;
         int F = pmaxi(in.y, fl), F2 = in.z;
-        sweep_cell<0, R, R, false, true>(Hq, Hq2, E, E2, qc, Hup_prev, F, F2, M, tt & 0x7f7f7f7f, tbl_hi, fl, v_e1, v_e2, v_o1, v_o2);
-        Hup_prev = pmaxi(in.x, fl - v_o1);
+        sweep_cell<0, R, R, false, true>(Hq, Hq2, E, E2, qc, Hup_prev, F, F2, M, tt & 0x7f7f7f7f, sc.tbl_hi, fl, sc.v_e1, sc.v_e2, sc.v_o1, sc.v_o2);
+        Hup_prev = pmaxi(in.x, fl - sc.v_o1);
         ring[slot * 64 + wr] = make_int4(Hq[R - 1], F, F2, tt);
-        if (hl == W - 1) ring[slot * 64 + hoff] = make_int4(v_floor, NEG1, NEG1, feed);
+        if (hl == W - 1) ring[slot * 64 + hoff] = make_int4(sc.v_floor, sc.NEG1, sc.NEG1, feed);
         ring_order();                                       // the next steps' loads stay behind these stores
         feed = dpp_rol1(feed);
         if (++slot == skew) slot = 0;
@@ -838,11 +887,11 @@ __device__ __forceinline__ int sweep_ring_body(const int task, const int lane, i
             }
         } else if constexpr (COMB) {
             if (pcnt == phase && step >= jfirst) {          // every lane is on a unit boundary: wave-uniform
-                const int tS = sweep_combine<0, R, R, false, PARK>(Hq, E, E2, Hbo, Ebo, E2bo, NEG2);
+                const int tS = sweep_combine<0, R, R, false, PARK>(Hq, E, E2, Hbo, Ebo, E2bo, sc.NEG2);
                 const int2 acc = racc[lane];
                 const int accS = pmaxi(acc.x, tS), accB = pmaxi(acc.y, M);
                 racc[wr] = make_int2(accS, accB);
-                if (hl == W - 1) racc[hoff] = make_int2(NEG2, NEG1);
+                if (hl == W - 1) racc[hoff] = make_int2(sc.NEG2, sc.NEG1);
                 ring_order();
                 if (bidx >= W - 1 && kcur <= tk.kmax) {     // lane W - 1 of each pair is on the boundary of k = kcur
                     int va = 0, vb = 0;
@@ -1128,42 +1177,138 @@ __global__ __launch_bounds__(WAVE, ringq_waves(R, HALF)) void k_sweep_ringq(int 
 }
 
 // ------------------------------------------------------------------------------------
-// k_sweep_ringchain: the LDS-ring sweep for reads of more than NRA_RING_CHAIN_MIN_ROWS rows.
+// The chained LDS-ring sweeps: reads of more than NRA_RING_CHAIN_MIN_ROWS rows as row blocks of 64*R rows.
 //
 // k_sweep_ring keeps all rows of a read pair in the registers of one wave: from 28 rows per lane on that is one
-// wave per SIMD.  Here the rows are swept as consecutive blocks of 64*R rows (R = NRA_RING_CHAIN_R) by the same
-// wave, which then fits three to a SIMD: what lane 63 leaves per column -- H of the block's last row, the two
-// vertical-gap states and, on boundary columns, the S and B accumulators -- goes to a scratch strip that the
-// next block's lane 0 picks up (lane 63 feeds lane 0's ring slot anyway: it hands out the strip's values
-// together with the template column).  W = false: two reads per wave in packed int16 (doubled scores up to
-// 27000); W = true: one read per wave in int32 cells, any length.  A launch has one wave per strip and walks its
-// tasks with a wave-uniform grid stride.
-template <int R, bool HAS_N, int DIR, bool W>
-__global__ __launch_bounds__(WAVE) void k_sweep_ringchain(int n_tasks, const NraSweepTask* __restrict__ tasks,
-                                                          const NraDevRead* __restrict__ reads,
-                                                          const NraDevRegion* __restrict__ regions,
-                                                          const uint8_t* __restrict__ pool,
-                                                          const uint32_t* __restrict__ q2bit,
-                                                          const uint32_t* __restrict__ qnmask,
-                                                          NraScoreParams sp,
-                                                          const int32_t* __restrict__ kmin_arr,
-                                                          const int32_t* __restrict__ kmax_arr,
-                                                          const uint32_t* __restrict__ coff,
-                                                          int32_t* __restrict__ snap,
-                                                          int32_t* __restrict__ read_a,
-                                                          int32_t* __restrict__ cand_score,
-                                                          uint8_t* __restrict__ cand_flag,
-                                                          int32_t* chain_buf, int chain_cap)
+// wave per SIMD.  Here the rows are swept as consecutive blocks of 64*R rows, which fit three waves to a SIMD: what
+// lane 63 leaves per column -- H of the block's last row, the two vertical-gap states and, on boundary columns, the
+// S and B accumulators -- goes to a strip that the next block's lane 0 picks up (lane 63 feeds lane 0's ring slot
+// anyway: it hands out the strip's values together with the template column).  W = false: two reads per wave in
+// packed int16 (doubled scores up to 27000); W = true: one read per wave in int32 cells, any length.
+//
+// sweep_rowblock_body is the sweep of ONE row block.  Two kernels run it: k_sweep_ringchain, the blocks of a task one
+// after the other in one wave, and k_sweep_ringmt, every block a wave of its own.  They differ in the hand-off between
+// two blocks only, the body's `Link`:
+//   bool fetch(col, at_boundary, h, f, f2, s, b)   what the block above left at column `col` (each lane its own; col < 0:
+//                                                  nothing, the arguments stay as they are; s and b only at_boundary);
+//                                                  wave-uniform control flow, false when the launch has failed
+//   void publish(plane, col, v)                    plane 0..4 (H, F, F2, S, B) of column `col` for the block below
+// ------------------------------------------------------------------------------------
+typedef unsigned long long nra_u64;
+typedef __attribute__((address_space(1))) nra_u64 nra_gu64;
+typedef __attribute__((address_space(1))) int nra_gi32;
+
+// The serial hand-off: five planes of plain int32 per strip, two strips per wave used in turn (a block reads the one
+// the block before wrote).  Writer and reader are the same wave, so every value is there when it is asked for.
+struct SweepStripLink {
+    volatile int32_t* cin;
+    volatile int32_t* cout;
+    int chain_cap;
+    __device__ __forceinline__ bool fetch(int col, bool at_boundary, int& h, int& f, int& f2, int& s, int& b) const
+    {
+        if (col >= 0) {
+            h = cin[col]; f = cin[chain_cap + col]; f2 = cin[2 * chain_cap + col];
+            if (at_boundary) { s = cin[3 * chain_cap + col]; b = cin[4 * chain_cap + col]; }
+        }
+        return true;
+    }
+    __device__ __forceinline__ void publish(int plane, int col, int v) const { cout[plane * chain_cap + col] = v; }
+};
+
+// The concurrent hand-off (cdna_hip_programming.md Guideline 16, R2: the data is the flag): what lane 63 of block b
+// leaves per column is stored as 8-byte granules {epoch, value}, ONE agent-scope (sc1, write-through) store each, into
+// the strip between the two blocks; block b+1 loads the granules of the 64 columns it is about to hand to its
+// lane 0 with agent-scope (sc1) loads and polls until every tag carries this launch's epoch.  No fence, no flag;
+// the strips are zeroed once when the batch is created and every launch has an epoch of its own (never 0), so a
+// granule of an earlier launch or run never passes.  Spins sleep (s_sleep), are bounded, and watch a launch-wide
+// error word: a wave that gives up sets it, the others leave, the host reports NRA_E_DEVICE.
+//
+// Polls (2 - 3 us each: an s_sleep and 3 - 5 agent-scope loads) before a waiting wave gives up: ~2.5 s, three orders above
+// the longest legitimate wait (64 * (skew + 1) steps of the block above, a millisecond or two).  A hang guard, not a
+// path: the argument that no wave waits for ever (tickets, at k_sweep_ringmt: a producer holds a smaller ticket than its
+// consumer, so it is running or done) assumes that a wave, once started, stays resident until it ends -- true as long as
+// nothing preempts the queue (no CWSR / time-slicing against another process on the device); if that ever fails the guard
+// turns a hang into NRA_E_DEVICE from nra_batch_sync / nra_batch1d_fetch.
+#define NRA_MT_SPIN_LIMIT (1u << 20)
+struct SweepGranuleLink {
+    const nra_gu64* cin;
+    nra_gu64* cout;
+    int chain_cap;
+    uint32_t epoch;
+    nra_u64 tag;                          // epoch << 32
+    nra_gi32* err;
+    __device__ __forceinline__ bool fetch(int col, bool at_boundary, int& h, int& f, int& f2, int& s, int& b) const
+    {
+        const bool mine = col >= 0;
+        const nra_gu64* g = cin + (mine ? col : 0);
+        for (unsigned spins = 0;; ++spins) {
+            bool ok = true;
+            if (mine) {
+                const nra_u64 x0 = __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const nra_u64 x1 = __hip_atomic_load(g + chain_cap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const nra_u64 x2 = __hip_atomic_load(g + 2 * (size_t)chain_cap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                ok = (x0 >> 32) == epoch && (x1 >> 32) == epoch && (x2 >> 32) == epoch;
+                h = (int)(unsigned)x0; f = (int)(unsigned)x1; f2 = (int)(unsigned)x2;
+                if (at_boundary) {
+                    const nra_u64 x3 = __hip_atomic_load(g + 3 * (size_t)chain_cap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const nra_u64 x4 = __hip_atomic_load(g + 4 * (size_t)chain_cap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    ok = ok && (x3 >> 32) == epoch && (x4 >> 32) == epoch;
+                    s = (int)(unsigned)x3; b = (int)(unsigned)x4;
+                }
+            }
+            if (__builtin_amdgcn_ballot_w64(!ok) == 0) return true;
+            __builtin_amdgcn_s_sleep(32);
+            if ((spins & 15) == 15) {
+                int failed = 0;
+                if (threadIdx.x == 0) failed = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (__builtin_amdgcn_readfirstlane(failed) != 0) return false;
+                if (spins >= NRA_MT_SPIN_LIMIT) {
+                    if (threadIdx.x == 0) __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    return false;
+                }
+            }
+        }
+    }
+    __device__ __forceinline__ void publish(int plane, int col, int v) const
+    {
+        __hip_atomic_store(cout + (size_t)plane * chain_cap + col, tag | (nra_u64)(unsigned)v, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+
+// the maximum over the wave of a packed running maximum
+template <bool W>
+__device__ __forceinline__ int sweep_wave_max(int M)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) M = mx2<W>(M, __shfl_xor(M, off, 64));
+    return M;
+}
+
+// Row block `blk` of `n_blk` of task tk.  Returns whether the launch is still good (false: a fetch gave up); a reverse
+// sweep leaves the packed maximum over the block's cells in M_out, each lane its own.
+template <int R, bool HAS_N, int DIR, bool W, class Link>
+__device__ __forceinline__ bool sweep_rowblock_body(const NraSweepTask& tk, const int blk, const int n_blk, int4* ring, int2* racc,
+                                                    const NraDevRead* __restrict__ reads,
+                                                    const NraDevRegion* __restrict__ regions,
+                                                    const uint8_t* __restrict__ pool,
+                                                    const uint32_t* __restrict__ q2bit,
+                                                    const uint32_t* __restrict__ qnmask,
+                                                    const NraScoreParams& sp,
+                                                    const int32_t* __restrict__ kmin_arr,
+                                                    const int32_t* __restrict__ kmax_arr,
+                                                    const uint32_t* __restrict__ coff,
+                                                    int32_t* __restrict__ snap,
+                                                    const int32_t* read_a,
+                                                    int32_t* __restrict__ cand_score,
+                                                    uint8_t* __restrict__ cand_flag, Link& link, int& M_out)
 {
     constexpr int SC = 2;
     constexpr int BIASW = W ? 0 : BIAS;
-    __shared__ int4 ring[SWEEP_RING_D * 64];
-    __shared__ int2 racc[64];
+    constexpr int P1 = SweepScores<SC, W>::P1;
     const int lane = threadIdx.x;
     const int wr = (lane + 1) & 63;
-    volatile int32_t* strip = chain_buf + (size_t)blockIdx.x * 10 * chain_cap;
-  for (int task = blockIdx.x; task < n_tasks; task += gridDim.x) {
-    const NraSweepTask tk = tasks[task];
+    const bool first_blk = blk == 0, last_blk = blk == n_blk - 1;
     const bool has_b = !W && tk.read_b >= 0;
     const int ra = tk.read_a, rb = has_b ? tk.read_b : tk.read_a;
     const NraDevRead rda = reads[ra], rdb = reads[rb];
@@ -1174,62 +1319,31 @@ __global__ __launch_bounds__(WAVE) void k_sweep_ringchain(int n_tasks, const Nra
     const int ncols = DIR ? flank + m * tk.kmax : flank;
     const int jfirst = DIR ? flank + m * tk.kmin - 1 : flank - 1;
     const int skew = DIR ? m : 1;
-    const int kmin_a = kmin_arr[ra], kmax_a = kmax_arr[ra];
-    const int kmin_b = kmin_arr[rb], kmax_b = kmax_arr[rb];
-    const uint32_t coff_a = coff[ra], coff_b = coff[rb];
+    const SweepCands cands(ra, rb, has_b, kmin_arr, kmax_arr, coff);
     int32_t* __restrict__ snap_task = snap + tk.snap_off;
+    const SweepScores<SC, W> sc(sp);
+    const int v_floor = sc.v_floor, NEG1 = sc.NEG1, NEG2 = sc.NEG2;
 
-    const int o1 = SC * sp.open1, o2 = SC * sp.open2;
-    const int P1 = W ? 1 : 0x00010001;
-    const int v_floor = (BIASW - o1) * P1;
-    const int v_o1 = o1 * P1, v_e1 = SC * sp.ext1 * P1, v_o2 = o2 * P1, v_e2 = SC * sp.ext2 * P1;
-    const int NEG1 = W ? -(1 << 28) : NEGB * P1;
-    const int NEG2 = W ? -(1 << 28) : 2 * NEGB * P1;
-    const int s_match = SC * sp.match + o1, s_mis = o1 - SC * sp.mismatch, s_ambi = o1 - SC * sp.ambi;
-    const int tbl_hi = s_mis | (s_ambi << 8);
-    const int tbl_mis4 = s_mis * 0x01010101, tbl_ambi4 = s_ambi * 0x01010101;
-
-    auto column_table = [&](int col) {
-        int t = tbl_mis4;
-        if (col >= 0 && col < ncols) {
-            const int code = piece[col];
-            t = code < 4 ? tbl_mis4 + ((s_match - s_mis) << (8 * code)) : tbl_ambi4;
-            if (DIR == 0 && col == flank - 1) t |= FLAG_SNAPSHOT;
-            if (DIR == 1 && col + 1 >= flank) t |= FLAG_INREP;     // origin bit of an alignment starting at the NEXT column
-        }
-        return t;
+    // What enters row 0 of this block at template column `col` (each lane its own column): constants for the first
+    // block and outside the template, else what the block above has left in the link.
+    auto fetch = [&](int col, int& h, int& f, int& f2, int& s, int& b) -> bool {
+        h = v_floor; f = NEG1; f2 = NEG1; s = NEG2; b = NEG1;
+        if (first_blk) return true;
+        const bool mine = col >= 0 && col < ncols;
+        const bool at_boundary = DIR == 1 && mine && col >= jfirst && (col - jfirst) % m == 0;
+        return link.fetch(mine ? col : -1, at_boundary, h, f, f2, s, b);
     };
+
+    auto column_table = [&](int col) { return sweep_column_table<DIR>(sc, piece, ncols, flank, col); };
 
     int out_a = 0, out_b = 0;
     int n_out = 0, kcur = tk.kmin;                          // wave-uniform
-    auto flush = [&](int n_valid) {
-        const int k = kcur - 64 + lane;
-        if (lane < 64 - n_valid) return;
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            if (s2 == 1 && !has_b) break;
-            const int lo_k = s2 ? kmin_b : kmin_a, hi_k = s2 ? kmax_b : kmax_a;
-            if (k < lo_k || k > hi_k) continue;
-            const uint32_t idx = (s2 ? coff_b : coff_a) + (uint32_t)(k - lo_k);
-            const int v = s2 ? out_b : out_a;
-            cand_score[idx] = v >> 2;
-            cand_flag[idx] = (uint8_t)(v & 3);
-        }
-    };
-    const int a_of_a = DIR ? read_a[ra] : 0, a_of_b = DIR ? read_a[rb] : 0;
-    int a_all = BIASW * P1;                                  // reverse sweep: maximum over the cells of every block
+    auto flush = [&](int n_valid) { sweep_flush(cands, n_valid, kcur, lane, out_a, out_b, cand_score, cand_flag); };
+    // A (best alignment inside R, doubled) of the two reads: wave-uniform, kept in scalar registers
+    const int a_of_a = DIR ? __builtin_amdgcn_readfirstlane(read_a[ra]) : 0, a_of_b = DIR ? __builtin_amdgcn_readfirstlane(read_a[rb]) : 0;
 
-    const int n_blk = (imax(rda.qlen, rdb.qlen) + 64 * R - 1) / (64 * R);
     const int nsteps = ncols + 63 * skew;
-  for (int blk = 0; blk < n_blk; ++blk) {
     const int row_base = blk * 64 * R;
-    const bool first_blk = blk == 0, last_blk = blk == n_blk - 1;
-    volatile int32_t* cin = strip + ((blk + 1) & 1) * 5 * chain_cap;
-    volatile int32_t* cout = strip + (blk & 1) * 5 * chain_cap;
-    // what enters row 0 of this block at template column `col`: constants for the first block, else the strip
-    auto strip_in = [&](int col, int which, int dflt) {
-        return (!first_blk && col >= 0 && col < ncols) ? (int)cin[which * chain_cap + col] : dflt;
-    };
 
     int qc[R];
 #pragma unroll
@@ -1255,10 +1369,10 @@ __global__ __launch_bounds__(WAVE) void k_sweep_ringchain(int n_tasks, const Nra
                     const int al = w / R, ai = w - al * R;
                     const int32_t* __restrict__ p = snap_task + ((size_t)ablk * 3 * R + ai) * 64 + al;
                     const int vh = p[0], ve = p[R * 64], ve2 = p[2 * R * 64];
-                    h[s] = (W ? vh : (s ? half_hi(vh) : half_lo(vh))) + 2 * o1;
+                    h[s] = (W ? vh : (s ? half_hi(vh) : half_lo(vh))) + 2 * sc.o1;
                     e[s] = (W ? ve : (s ? half_hi(ve) : half_lo(ve))) + q1;
                     e2[s] = (W ? ve2 : (s ? half_hi(ve2) : half_lo(ve2))) + q2;
-                } else { h[s] = BIASW + o1 - SC; e[s] = BIASW - SC; e2[s] = BIASW - SC; }
+                } else { h[s] = BIASW + sc.o1 - SC; e[s] = BIASW - SC; e2[s] = BIASW - SC; }
             }
             Hbo[i] = W ? h[0] : pack2(h[0], h[1]);
             Ebo[i] = W ? e[0] : pack2(e[0], e[1]);
@@ -1269,133 +1383,140 @@ __global__ __launch_bounds__(WAVE) void k_sweep_ringchain(int n_tasks, const Nra
 #pragma unroll
     for (int i = 0; i < R; ++i) { Hq[i] = v_floor; Hq2[i] = NEG1; E[i] = NEG1; E2[i] = NEG1; }
 
-    // ring: padding columns everywhere, then lane 0's first `skew` columns and first boundary
+    // ring: padding columns everywhere, then lane 0's first `skew` columns (and, when the first boundary is one
+    // of them, its accumulators; a later first boundary gets them from lane 63 one boundary phase ahead, below)
 #pragma unroll
-    for (int s = 0; s < SWEEP_RING_D; ++s) ring[s * 64 + lane] = make_int4(v_floor, NEG1, NEG1, tbl_mis4);
+    for (int s = 0; s < SWEEP_RING_D; ++s) ring[s * 64 + lane] = make_int4(v_floor, NEG1, NEG1, sc.tbl_mis4);
     racc[lane] = make_int2(NEG2, NEG1);
-    if (lane < skew)
-        ring[lane * 64] = make_int4(strip_in(lane, 0, v_floor), strip_in(lane, 1, NEG1), strip_in(lane, 2, NEG1), column_table(lane));
-    if (DIR == 1 && lane == 0) racc[0] = make_int2(strip_in(jfirst, 3, NEG2), strip_in(jfirst, 4, NEG1));
+    int feed = sc.tbl_mis4, sH, sF, sF2, sS, sB;   // what lane 63 hands to lane 0
+    if (!fetch(lane < skew ? lane : -1, sH, sF, sF2, sS, sB)) return false;
+    if (lane < skew) ring[lane * 64] = make_int4(sH, sF, sF2, column_table(lane));
+    if (DIR == 1 && lane == jfirst && jfirst < skew) racc[0] = make_int2(sS, sB);
     ring_order();
 
     int Hup_prev = v_floor, M = BIASW * P1;
-    int feed = tbl_mis4, sH = v_floor, sF = NEG1, sF2 = NEG1, sS = NEG2, sB = NEG1;   // what lane 63 hands to lane 0
     int slot = 0;
     int phase = jfirst % m, pcnt = 0, bidx = 0;
-    n_out = 0; kcur = tk.kmin;
 #pragma unroll 1
     for (int step = 0; step < nsteps; ++step) {
         if ((step & 63) == 0) {                                            // columns step + skew + (0..63)
             const int col = step + skew + wr;
             feed = column_table(col);
-            sH = strip_in(col, 0, v_floor); sF = strip_in(col, 1, NEG1); sF2 = strip_in(col, 2, NEG1);
-            if (DIR == 1) { sS = strip_in(col, 3, NEG2); sB = strip_in(col, 4, NEG1); }
+            if (!fetch(col, sH, sF, sF2, sS, sB)) return false;
         }
         const int4 in = ring[slot * 64 + lane];
         const int tt = in.w;
         const int fl = DIR == 1 ? (int)((((unsigned)tt >> 15) & (unsigned)P1) | (unsigned)(BIASW * P1)) : BIASW * P1;   // as in k_sweep_ring
         int F = mx2<W>(in.y, fl), F2 = in.z;
-        sweep_cell<0, R, R, W, true>(Hq, Hq2, E, E2, qc, Hup_prev, F, F2, M, tt & 0x7f7f7f7f, tbl_hi, fl, v_e1, v_e2, v_o1, v_o2);
-        Hup_prev = mx2<W>(in.x, fl - v_o1);
+        sweep_cell<0, R, R, W, true>(Hq, Hq2, E, E2, qc, Hup_prev, F, F2, M, tt & 0x7f7f7f7f, sc.tbl_hi, fl, sc.v_e1, sc.v_e2, sc.v_o1, sc.v_o2);
+        Hup_prev = mx2<W>(in.x, fl - sc.v_o1);
         ring[slot * 64 + wr] = make_int4(Hq[R - 1], F, F2, tt);
         if (lane == 63) ring[slot * 64] = make_int4(sH, sF, sF2, feed);
         ring_order();                                       // the next steps' loads stay behind these stores
         const int c63 = step - 63 * skew;                                  // the column lane 63 has just finished
-        if (lane == 63 && !last_blk && c63 >= 0) {
-            cout[c63] = Hq[R - 1]; cout[chain_cap + c63] = F; cout[2 * chain_cap + c63] = F2;
-        }
+        if (lane == 63 && !last_blk && c63 >= 0) { link.publish(0, c63, Hq[R - 1]); link.publish(1, c63, F); link.publish(2, c63, F2); }
         feed = dpp_rol1(feed); sH = dpp_rol1(sH); sF = dpp_rol1(sF); sF2 = dpp_rol1(sF2);
         if (++slot == skew) slot = 0;
 
         if constexpr (DIR == 0) {
             if (tt & FLAG_SNAPSHOT) sweep_snapshot<0, R, R>(Hq, E, E2, snap_task + (size_t)blk * 3 * R * 64, lane);
         } else {
-            const bool boundary = pcnt == phase && step >= jfirst;         // wave-uniform: every lane on a unit boundary
-            if (boundary) {
-                const int tS = sweep_combine<0, R, R, W>(Hq, E, E2, Hbo, Ebo, E2bo, NEG2);
-                const int2 acc = racc[lane];
-                const int accS = mx2<W>(acc.x, tS), accB = mx2<W>(acc.y, M);
-                racc[wr] = make_int2(accS, accB);
-                if (lane == 63) {
-                    racc[0] = make_int2(sS, sB);                           // of column step + skew: lane 0's next boundary
-                    if (!last_blk && c63 >= 0) { cout[3 * chain_cap + c63] = accS; cout[4 * chain_cap + c63] = accB; }
-                }
-                ring_order();
-                if (last_blk && bidx >= 63 && kcur <= tk.kmax) {           // lane 63 is on the boundary of k = kcur
-                    int va = 0, vb = 0;
+            if (pcnt == phase) {                                           // wave-uniform
+                if (step >= jfirst) {                                      // every lane on a unit boundary
+                    const int tS = sweep_combine<0, R, R, W>(Hq, E, E2, Hbo, Ebo, E2bo, NEG2);
+                    const int2 acc = racc[lane];
+                    const int accS = mx2<W>(acc.x, tS), accB = mx2<W>(acc.y, M);
+                    racc[wr] = make_int2(accS, accB);
                     if (lane == 63) {
-#pragma unroll
-                        for (int s2 = 0; s2 < (W ? 1 : 2); ++s2) {
-                            const int B = (W ? accB : (s2 ? half_hi(accB) : half_lo(accB))) - BIASW;
-                            const int S = (W ? accS : (s2 ? half_hi(accS) : half_lo(accS))) - 2 * BIASW;
-                            const int lo = sp.min_score > 1 ? sp.min_score : 1;
-                            const int V = imax(imax(S, B), (s2 ? a_of_b : a_of_a) + 1);
-                            const int best = V >> 1;
-                            int flag = 1;
-                            if (V & 1) flag = 0;
-                            else if ((B >> 1) >= best) flag = ((S >> 1) >= best) ? 2 : 0;
-                            const int v = ((best >= lo ? best : -1) << 2) | flag;
-                            if (s2) vb = v; else va = v;
-                        }
+                        racc[0] = make_int2(sS, sB);                       // of column step + skew: lane 0's next boundary
+                        if (!last_blk && c63 >= 0) { link.publish(3, c63, accS); link.publish(4, c63, accB); }
                     }
-                    out_a = dpp_rol1(out_a); out_b = dpp_rol1(out_b);
-                    if (lane == 63) { out_a = va; out_b = vb; }
-                    ++kcur; ++n_out;
-                    if (n_out == 64) { flush(64); n_out = 0; }
+                    ring_order();
+                    if (last_blk && bidx >= 63 && kcur <= tk.kmax) {       // lane 63 is on the boundary of k = kcur
+                        int va = 0, vb = 0;
+                        if (lane == 63) {
+                            va = sweep_emit<W>(accS, accB, 0, a_of_a + 1, sp.min_score);
+                            if (!W) vb = sweep_emit<W>(accS, accB, 1, a_of_b + 1, sp.min_score);
+                        }
+                        out_a = dpp_rol1(out_a); out_b = dpp_rol1(out_b);
+                        if (lane == 63) { out_a = va; out_b = vb; }
+                        ++kcur; ++n_out;
+                        if (n_out == 64) { flush(64); n_out = 0; }
+                    }
+                    ++bidx;
+                } else if (step + m >= jfirst) {                           // one boundary phase before lane 0's first boundary
+                    if (lane == 63) racc[0] = make_int2(sS, sB);           // of column step + skew = jfirst
+                    ring_order();
                 }
-                ++bidx;
             }
             sS = dpp_rol1(sS); sB = dpp_rol1(sB);
             if (++pcnt == m) pcnt = 0;
         }
     }
-    if (DIR == 0) a_all = mx2<W>(a_all, M);
+    if (DIR == 0) M_out = M;
     else if (last_blk && n_out > 0) flush(n_out);
-  }   // row blocks
-    if (DIR == 0) {
-        // A = best alignment inside R (doubled) = the maximum over every cell of the sweep
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) a_all = mx2<W>(a_all, __shfl_xor(a_all, off, 64));
-        if (lane == 0) {
-            read_a[ra] = (W ? a_all : half_lo(a_all)) - BIASW;
-            if (has_b) read_a[rb] = half_hi(a_all) - BIASW;
-        }
-    }
-  }   // tasks
+    return true;
 }
 
-// ------------------------------------------------------------------------------------
-// k_sweep_ringmt: the chained LDS-ring sweep with the row blocks of a read as CONCURRENT waves.
+// k_sweep_ringchain: the row blocks of a task one after the other in ONE wave, under NRA_F_SERIAL_CHAIN and when a
+// read alone would need more strips than the concurrent form has.  A launch has one wave per strip pair and walks its
+// tasks with a wave-uniform grid stride.
+template <int R, bool HAS_N, int DIR, bool W>
+__global__ __launch_bounds__(WAVE) void k_sweep_ringchain(int n_tasks, const NraSweepTask* __restrict__ tasks,
+                                                          const NraDevRead* __restrict__ reads,
+                                                          const NraDevRegion* __restrict__ regions,
+                                                          const uint8_t* __restrict__ pool,
+                                                          const uint32_t* __restrict__ q2bit,
+                                                          const uint32_t* __restrict__ qnmask,
+                                                          NraScoreParams sp,
+                                                          const int32_t* __restrict__ kmin_arr,
+                                                          const int32_t* __restrict__ kmax_arr,
+                                                          const uint32_t* __restrict__ coff,
+                                                          int32_t* __restrict__ snap,
+                                                          int32_t* __restrict__ read_a,
+                                                          int32_t* __restrict__ cand_score,
+                                                          uint8_t* __restrict__ cand_flag,
+                                                          int32_t* chain_buf, int chain_cap)
+{
+    constexpr int BIASW = W ? 0 : BIAS;
+    __shared__ int4 ring[SWEEP_RING_D * 64];
+    __shared__ int2 racc[64];
+    volatile int32_t* strip = chain_buf + (size_t)blockIdx.x * 10 * chain_cap;
+    for (int task = blockIdx.x; task < n_tasks; task += gridDim.x) {
+        const NraSweepTask tk = tasks[task];
+        const bool has_b = !W && tk.read_b >= 0;
+        const int ra = tk.read_a, rb = has_b ? tk.read_b : tk.read_a;
+        const int n_blk = (imax(reads[ra].qlen, reads[rb].qlen) + 64 * R - 1) / (64 * R);
+        int a_all = BIASW * (W ? 1 : 0x00010001);           // reverse sweep: maximum over the cells of every block
+        for (int blk = 0; blk < n_blk; ++blk) {
+            SweepStripLink link{strip + ((blk + 1) & 1) * 5 * chain_cap, strip + (blk & 1) * 5 * chain_cap, chain_cap};
+            int M = 0;
+            sweep_rowblock_body<R, HAS_N, DIR, W>(tk, blk, n_blk, ring, racc, reads, regions, pool, q2bit, qnmask, sp, kmin_arr,
+                                                  kmax_arr, coff, snap, read_a, cand_score, cand_flag, link, M);
+            if (DIR == 0) a_all = mx2<W>(a_all, M);
+        }
+        if (DIR == 0) {
+            // A = best alignment inside R (doubled) = the maximum over every cell of the sweep
+            a_all = sweep_wave_max<W>(a_all);
+            if (threadIdx.x == 0) {
+                read_a[ra] = (W ? a_all : half_lo(a_all)) - BIASW;
+                if (has_b) read_a[rb] = half_hi(a_all) - BIASW;
+            }
+        }
+    }
+}
+
+// k_sweep_ringmt: the row blocks of a read as CONCURRENT waves.
 //
 // k_sweep_ringchain runs the blocks of a task one after the other in one wave: a batch of few long reads (2000
 // cores of 3.7 kb = 1000 tasks of three blocks) then has one wave per SIMD.  Here a wave is one (task, row block):
 // block b+1 starts as soon as block b has published the columns it needs and follows 64 * (skew + 1) steps behind,
 // so the blocks of a read overlap and the launch has (blocks per read) times the waves.
 //
-// Hand-off (cdna_hip_programming.md Guideline 16, R2: the data is the flag): what lane 63 of block b leaves per
-// column -- H of the block's last row, the two vertical-gap states and, on boundary columns, the S and B
-// accumulators -- is stored as 8-byte granules {epoch, value}, ONE agent-scope (sc1, write-through) store each, into
-// the strip between the two blocks; block b+1 loads the granules of the 64 columns it is about to hand to its
-// lane 0 with agent-scope (sc1) loads and polls until every tag carries this launch's epoch.  No fence, no flag;
-// the strips are zeroed once when the batch is created and every launch has an epoch of its own (never 0), so a
-// granule of an earlier launch or run never passes.
-//
 // No deadlock, whatever the dispatch order: a wave takes its (task, block) by TICKET -- one atomic add when it
 // starts -- and the block list is ordered so that a producer precedes its consumer (all blocks 0, then all blocks 1,
 // ...).  Whoever holds a ticket runs; every smaller ticket was taken by a wave that has started, so the producer a
-// wave waits for is running or done and never waits for a larger ticket.  Spins sleep (s_sleep), are bounded, and
-// watch a launch-wide error word: a wave that gives up sets it, the others leave, the host reports NRA_E_DEVICE.
-typedef unsigned long long nra_u64;
-typedef __attribute__((address_space(1))) nra_u64 nra_gu64;
-typedef __attribute__((address_space(1))) int nra_gi32;
-// Polls (2 - 3 us each: an s_sleep and 3 - 5 agent-scope loads) before a waiting wave gives up: ~2.5 s, three orders above
-// the longest legitimate wait (64 * (skew + 1) steps of the block above, a millisecond or two).  A hang guard, not a
-// path: the argument that no wave waits for ever (tickets: a producer holds a smaller ticket than its consumer, so it
-// is running or done) assumes that a wave, once started, stays resident until it ends -- true as long as nothing
-// preempts the queue (no CWSR / time-slicing against another process on the device); if that ever fails the guard
-// turns a hang into NRA_E_DEVICE from nra_batch_sync / nra_batch1d_fetch.
-#define NRA_MT_SPIN_LIMIT (1u << 20)
-
+// wave waits for is running or done and never waits for a larger ticket.  (The waits themselves: SweepGranuleLink.)
 template <int R, bool HAS_N, int DIR, bool W>
 __global__ __launch_bounds__(WAVE, 3) void k_sweep_ringmt(int n_blocks, const NraChainBlock* __restrict__ blocks,
                                                        int32_t* ticket, const NraSweepTask* __restrict__ tasks,
@@ -1414,255 +1535,33 @@ __global__ __launch_bounds__(WAVE, 3) void k_sweep_ringmt(int n_blocks, const Nr
                                                        uint8_t* __restrict__ cand_flag,
                                                        nra_u64* strips, int chain_cap, uint32_t epoch, int32_t* error)
 {
-    constexpr int SC = 2;
     constexpr int BIASW = W ? 0 : BIAS;
     __shared__ int4 ring[SWEEP_RING_D * 64];
     __shared__ int2 racc[64];
     const int lane = threadIdx.x;
-    const int wr = (lane + 1) & 63;
     int my = 0;
     if (lane == 0) my = atomicAdd(ticket, 1);
     my = __builtin_amdgcn_readfirstlane(my);
     if (my >= n_blocks) return;
     const NraChainBlock cb = blocks[my];
     const NraSweepTask tk = tasks[cb.task];
-    const int blk = cb.blk;
-    const bool first_blk = blk == 0, last_blk = blk == cb.nblk - 1;
-    nra_gu64* cin = (nra_gu64*)(strips + (size_t)(first_blk ? 0 : cb.strip_in) * 5 * (size_t)chain_cap);
-    nra_gu64* cout = (nra_gu64*)(strips + (size_t)(last_blk ? 0 : cb.strip_out) * 5 * (size_t)chain_cap);
-    nra_gi32* err = (nra_gi32*)error;
-    const nra_u64 tag = (nra_u64)epoch << 32;
-
-    const bool has_b = !W && tk.read_b >= 0;
-    const int ra = tk.read_a, rb = has_b ? tk.read_b : tk.read_a;
-    const NraDevRead rda = reads[ra], rdb = reads[rb];
-    const NraDevRegion rg = regions[rda.region];
-    const int m = rg.m1;
-    const int flank = DIR ? rg.l1 : rg.l3;
-    const uint8_t* __restrict__ piece = pool + (DIR ? rg.p1_off : rg.pr_off);
-    const int ncols = DIR ? flank + m * tk.kmax : flank;
-    const int jfirst = DIR ? flank + m * tk.kmin - 1 : flank - 1;
-    const int skew = DIR ? m : 1;
-    const int kmin_a = kmin_arr[ra], kmax_a = kmax_arr[ra];
-    const int kmin_b = kmin_arr[rb], kmax_b = kmax_arr[rb];
-    const uint32_t coff_a = coff[ra], coff_b = coff[rb];
-    int32_t* __restrict__ snap_task = snap + tk.snap_off;
-
-    const int o1 = SC * sp.open1, o2 = SC * sp.open2;
-    const int P1 = W ? 1 : 0x00010001;
-    const int v_floor = (BIASW - o1) * P1;
-    const int v_o1 = o1 * P1, v_e1 = SC * sp.ext1 * P1, v_o2 = o2 * P1, v_e2 = SC * sp.ext2 * P1;
-    const int NEG1 = W ? -(1 << 28) : NEGB * P1;
-    const int NEG2 = W ? -(1 << 28) : 2 * NEGB * P1;
-    const int s_match = SC * sp.match + o1, s_mis = o1 - SC * sp.mismatch, s_ambi = o1 - SC * sp.ambi;
-    const int tbl_hi = s_mis | (s_ambi << 8);
-    const int tbl_mis4 = s_mis * 0x01010101, tbl_ambi4 = s_ambi * 0x01010101;
-
-    auto column_table = [&](int col) {
-        int t = tbl_mis4;
-        if (col >= 0 && col < ncols) {
-            const int code = piece[col];
-            t = code < 4 ? tbl_mis4 + ((s_match - s_mis) << (8 * code)) : tbl_ambi4;
-            if (DIR == 0 && col == flank - 1) t |= FLAG_SNAPSHOT;
-            if (DIR == 1 && col + 1 >= flank) t |= FLAG_INREP;     // origin bit of an alignment starting at the NEXT column
-        }
-        return t;
-    };
-
-    // What enters row 0 of this block at template column `col` (each lane its own column): constants for the
-    // first block and outside the template, else the granules the block above has published -- polled until they
-    // carry this launch's epoch.  Wave-uniform control flow; returns false when the launch has failed.
-    auto fetch = [&](int col, int& h, int& f, int& f2, int& s2, int& b2) -> bool {
-        h = v_floor; f = NEG1; f2 = NEG1; s2 = NEG2; b2 = NEG1;
-        const bool mine = !first_blk && col >= 0 && col < ncols;
-        const bool at_boundary = DIR == 1 && mine && col >= jfirst && (col - jfirst) % m == 0;
-        if (first_blk) return true;
-        const nra_gu64* g = cin + (mine ? col : 0);
-        for (unsigned spins = 0;; ++spins) {
-            bool ok = true;
-            if (mine) {
-                const nra_u64 x0 = __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const nra_u64 x1 = __hip_atomic_load(g + chain_cap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const nra_u64 x2 = __hip_atomic_load(g + 2 * (size_t)chain_cap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                ok = (x0 >> 32) == epoch && (x1 >> 32) == epoch && (x2 >> 32) == epoch;
-                h = (int)(unsigned)x0; f = (int)(unsigned)x1; f2 = (int)(unsigned)x2;
-                if (at_boundary) {
-                    const nra_u64 x3 = __hip_atomic_load(g + 3 * (size_t)chain_cap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const nra_u64 x4 = __hip_atomic_load(g + 4 * (size_t)chain_cap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    ok = ok && (x3 >> 32) == epoch && (x4 >> 32) == epoch;
-                    s2 = (int)(unsigned)x3; b2 = (int)(unsigned)x4;
-                }
-            }
-            if (__builtin_amdgcn_ballot_w64(!ok) == 0) return true;
-            __builtin_amdgcn_s_sleep(32);
-            if ((spins & 15) == 15) {
-                int failed = 0;
-                if (lane == 0) failed = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (__builtin_amdgcn_readfirstlane(failed) != 0) return false;
-                if (spins >= NRA_MT_SPIN_LIMIT) {
-                    if (lane == 0) __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    return false;
-                }
-            }
-        }
-    };
-    auto publish = [&](int plane, int col, int v) {
-        __hip_atomic_store(cout + (size_t)plane * chain_cap + col, tag | (nra_u64)(unsigned)v, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    };
-
-    int out_a = 0, out_b = 0;
-    int n_out = 0, kcur = tk.kmin;                          // wave-uniform
-    auto flush = [&](int n_valid) {
-        const int k = kcur - 64 + lane;
-        if (lane < 64 - n_valid) return;
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            if (s2 == 1 && !has_b) break;
-            const int lo_k = s2 ? kmin_b : kmin_a, hi_k = s2 ? kmax_b : kmax_a;
-            if (k < lo_k || k > hi_k) continue;
-            const uint32_t idx = (s2 ? coff_b : coff_a) + (uint32_t)(k - lo_k);
-            const int v = s2 ? out_b : out_a;
-            cand_score[idx] = v >> 2;
-            cand_flag[idx] = (uint8_t)(v & 3);
-        }
-    };
-    const int a_of_a = DIR ? read_a[ra] : 0, a_of_b = DIR ? read_a[rb] : 0;
-
-    const int nsteps = ncols + 63 * skew;
-    const int row_base = blk * 64 * R;
-
-    int qc[R];
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-        const int gi = row_base + lane * R + i;
-        const int ca = sweep_query_sel<HAS_N>(rda, q2bit, qnmask, gi, DIR == 0);
-        const int cb2 = W ? 0x0c : sweep_query_sel<HAS_N>(rdb, q2bit, qnmask, gi, DIR == 0);
-        qc[i] = ca | (0x0c << 8) | (cb2 << 16) | (0x0c << 24);
-    }
-    int Hbo[DIR ? R : 1], Ebo[DIR ? R : 1], E2bo[DIR ? R : 1];
-    if (DIR) {
-        const int q1 = SC * (sp.open1 - sp.ext1), q2 = SC * (sp.open2 - sp.ext2);
-#pragma unroll
-        for (int i = 0; i < R; ++i) {
-            const int r = row_base + lane * R + i;
-            int h[2], e[2], e2[2];
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const int a = (s ? rdb.qlen : rda.qlen) - 2 - r;
-                if (a >= 0) {
-                    const int ablk = a / (64 * R);
-                    const int w = a - ablk * 64 * R;
-                    const int al = w / R, ai = w - al * R;
-                    const int32_t* __restrict__ p = snap_task + ((size_t)ablk * 3 * R + ai) * 64 + al;
-                    const int vh = p[0], ve = p[R * 64], ve2 = p[2 * R * 64];
-                    h[s] = (W ? vh : (s ? half_hi(vh) : half_lo(vh))) + 2 * o1;
-                    e[s] = (W ? ve : (s ? half_hi(ve) : half_lo(ve))) + q1;
-                    e2[s] = (W ? ve2 : (s ? half_hi(ve2) : half_lo(ve2))) + q2;
-                } else { h[s] = BIASW + o1 - SC; e[s] = BIASW - SC; e2[s] = BIASW - SC; }
-            }
-            Hbo[i] = W ? h[0] : pack2(h[0], h[1]);
-            Ebo[i] = W ? e[0] : pack2(e[0], e[1]);
-            E2bo[i] = W ? e2[0] : pack2(e2[0], e2[1]);
-        }
-    }
-    int Hq[R], Hq2[R], E[R], E2[R];
-#pragma unroll
-    for (int i = 0; i < R; ++i) { Hq[i] = v_floor; Hq2[i] = NEG1; E[i] = NEG1; E2[i] = NEG1; }
-
-    // ring: padding columns everywhere, then lane 0's first `skew` columns (and, when the first boundary is one
-    // of them, its accumulators; a later first boundary gets them from lane 63 one boundary phase ahead, below)
-#pragma unroll
-    for (int s = 0; s < SWEEP_RING_D; ++s) ring[s * 64 + lane] = make_int4(v_floor, NEG1, NEG1, tbl_mis4);
-    racc[lane] = make_int2(NEG2, NEG1);
-    int feed = tbl_mis4, sH, sF, sF2, sS, sB;   // what lane 63 hands to lane 0
-    if (!fetch(lane < skew ? lane : -1, sH, sF, sF2, sS, sB)) return;
-    if (lane < skew) ring[lane * 64] = make_int4(sH, sF, sF2, column_table(lane));
-    if (DIR == 1 && lane == jfirst && jfirst < skew) racc[0] = make_int2(sS, sB);
-    ring_order();
-
-    int Hup_prev = v_floor, M = BIASW * P1;
-    int slot = 0;
-    int phase = jfirst % m, pcnt = 0, bidx = 0;
-#pragma unroll 1
-    for (int step = 0; step < nsteps; ++step) {
-        if ((step & 63) == 0) {                                            // columns step + skew + (0..63)
-            const int col = step + skew + wr;
-            feed = column_table(col);
-            if (!fetch(col, sH, sF, sF2, sS, sB)) return;
-        }
-        const int4 in = ring[slot * 64 + lane];
-        const int tt = in.w;
-        const int fl = DIR == 1 ? (int)((((unsigned)tt >> 15) & (unsigned)P1) | (unsigned)(BIASW * P1)) : BIASW * P1;   // as in k_sweep_ring
-        int F = mx2<W>(in.y, fl), F2 = in.z;
-        sweep_cell<0, R, R, W, true>(Hq, Hq2, E, E2, qc, Hup_prev, F, F2, M, tt & 0x7f7f7f7f, tbl_hi, fl, v_e1, v_e2, v_o1, v_o2);
-        Hup_prev = mx2<W>(in.x, fl - v_o1);
-        ring[slot * 64 + wr] = make_int4(Hq[R - 1], F, F2, tt);
-        if (lane == 63) ring[slot * 64] = make_int4(sH, sF, sF2, feed);
-        ring_order();                                       // the next steps' loads stay behind these stores
-        const int c63 = step - 63 * skew;                                  // the column lane 63 has just finished
-        if (lane == 63 && !last_blk && c63 >= 0) { publish(0, c63, Hq[R - 1]); publish(1, c63, F); publish(2, c63, F2); }
-        feed = dpp_rol1(feed); sH = dpp_rol1(sH); sF = dpp_rol1(sF); sF2 = dpp_rol1(sF2);
-        if (++slot == skew) slot = 0;
-
-        if constexpr (DIR == 0) {
-            if (tt & FLAG_SNAPSHOT) sweep_snapshot<0, R, R>(Hq, E, E2, snap_task + (size_t)blk * 3 * R * 64, lane);
-        } else {
-            if (pcnt == phase) {                                           // wave-uniform
-                if (step >= jfirst) {                                      // every lane on a unit boundary
-                    const int tS = sweep_combine<0, R, R, W>(Hq, E, E2, Hbo, Ebo, E2bo, NEG2);
-                    const int2 acc = racc[lane];
-                    const int accS = mx2<W>(acc.x, tS), accB = mx2<W>(acc.y, M);
-                    racc[wr] = make_int2(accS, accB);
-                    if (lane == 63) {
-                        racc[0] = make_int2(sS, sB);                       // of column step + skew: lane 0's next boundary
-                        if (!last_blk && c63 >= 0) { publish(3, c63, accS); publish(4, c63, accB); }
-                    }
-                    ring_order();
-                    if (last_blk && bidx >= 63 && kcur <= tk.kmax) {       // lane 63 is on the boundary of k = kcur
-                        int va = 0, vb = 0;
-                        if (lane == 63) {
-#pragma unroll
-                            for (int s2 = 0; s2 < (W ? 1 : 2); ++s2) {
-                                const int B = (W ? accB : (s2 ? half_hi(accB) : half_lo(accB))) - BIASW;
-                                const int S = (W ? accS : (s2 ? half_hi(accS) : half_lo(accS))) - 2 * BIASW;
-                                const int lo = sp.min_score > 1 ? sp.min_score : 1;
-                                const int V = imax(imax(S, B), (s2 ? a_of_b : a_of_a) + 1);
-                                const int best = V >> 1;
-                                int flag = 1;
-                                if (V & 1) flag = 0;
-                                else if ((B >> 1) >= best) flag = ((S >> 1) >= best) ? 2 : 0;
-                                const int v = ((best >= lo ? best : -1) << 2) | flag;
-                                if (s2) vb = v; else va = v;
-                            }
-                        }
-                        out_a = dpp_rol1(out_a); out_b = dpp_rol1(out_b);
-                        if (lane == 63) { out_a = va; out_b = vb; }
-                        ++kcur; ++n_out;
-                        if (n_out == 64) { flush(64); n_out = 0; }
-                    }
-                    ++bidx;
-                } else if (step + m >= jfirst) {                           // one boundary phase before lane 0's first boundary
-                    if (lane == 63) racc[0] = make_int2(sS, sB);           // of column step + skew = jfirst
-                    ring_order();
-                }
-            }
-            sS = dpp_rol1(sS); sB = dpp_rol1(sB);
-            if (++pcnt == m) pcnt = 0;
-        }
-    }
+    const bool first_blk = cb.blk == 0, last_blk = cb.blk == cb.nblk - 1;
+    SweepGranuleLink link{(const nra_gu64*)(strips + (size_t)(first_blk ? 0 : cb.strip_in) * 5 * (size_t)chain_cap),
+                          (nra_gu64*)(strips + (size_t)(last_blk ? 0 : cb.strip_out) * 5 * (size_t)chain_cap), chain_cap, epoch,
+                          (nra_u64)epoch << 32, (nra_gi32*)error};
+    int M = 0;
+    if (!sweep_rowblock_body<R, HAS_N, DIR, W>(tk, cb.blk, cb.nblk, ring, racc, reads, regions, pool, q2bit, qnmask, sp, kmin_arr,
+                                               kmax_arr, coff, snap, read_a, cand_score, cand_flag, link, M))
+        return;
     if (DIR == 0) {
         // A = best alignment inside R (doubled) = the maximum over every cell of every block: the blocks are waves
         // of their own, so each adds its maximum to the read's word (zeroed before the launch; A >= 0)
-        int a_all = M;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) a_all = mx2<W>(a_all, __shfl_xor(a_all, off, 64));
+        const bool has_b = !W && tk.read_b >= 0;
+        const int a_all = sweep_wave_max<W>(M);
         if (lane == 0) {
-            atomicMax(&read_a[ra], (W ? a_all : half_lo(a_all)) - BIASW);
-            if (has_b) atomicMax(&read_a[rb], half_hi(a_all) - BIASW);
+            atomicMax(&read_a[tk.read_a], (W ? a_all : half_lo(a_all)) - BIASW);
+            if (has_b) atomicMax(&read_a[tk.read_b], half_hi(a_all) - BIASW);
         }
-    } else if (last_blk && n_out > 0) {
-        flush(n_out);
     }
 }
 

@@ -1186,6 +1186,49 @@ def test_1d_row_block_chaining_small_blocks(capi, oracle):
         assert np.array_equal(g[k], o[k]), k
 
 
+def first_boundary_cases():
+    """(region, reads, kmin, kmax) of test_first_boundary_hand_off_of_both_chained_forms: per unit of 2, 5 and 8 bases a
+    left anchor of 1, m, m + 1 and 40 bases with kmin = 0, then kmin = 3 and a window of fewer than 64 repeat counts; three
+    reads each -- the host pairs the two longest (four and three 128-row blocks) and leaves the third alone (three
+    blocks) --, in every other case one of them with an N."""
+    rng = np.random.default_rng(77)
+    cases = []
+    for u in ("AT", "TATTG", "ACGTTGCA"):
+        m = len(u)
+        for la, win in ((1, 0), (m, 0), (m + 1, 0), (40, 0), (1, 3), (40, 3), (m + 1, "narrow")):
+            L, R = synth.rand_seq(rng, la), synth.rand_seq(rng, 130)
+            kt = [(n - la - 120) // m for n in (450, 350, 300)]
+            reads = [synth.apply_errors(rng, L + u * k + R[:120], "ont_q20") for k in kt]
+            if len(cases) % 2:
+                reads[len(cases) % 3] = reads[len(cases) % 3][:200] + "N" + reads[len(cases) % 3][201:]
+            assert [(len(r) + 127) // 128 for r in reads] == [4, 3, 3] and len(reads[1]) > len(reads[2]), [len(r) for r in reads]
+            if win == "narrow":
+                kmin, kmax = [k - 4 for k in kt], [k + 4 for k in kt]
+                assert max(kmax[:2]) - min(kmin[:2]) + 1 < 64        # the pair sweeps the union of its two windows
+            else:
+                kmin, kmax = [win] * 3, [max(kt) + 12] * 3
+            cases.append(((L, u, R), reads, kmin, kmax))
+    return cases
+
+
+def test_first_boundary_hand_off_of_both_chained_forms(capi, oracle):
+    """Lane 0's first boundary accumulators in a row block that is not the first: taken when the block starts if the
+    first unit boundary jfirst = |L| + m * kmin - 1 is among lane 0's first `skew` = m columns (kmin = 0 and |L| <= m),
+    else handed out by lane 63 one boundary phase ahead.  One scheme for the blocks of a read as concurrent waves and as
+    one wave (F_SERIAL_CHAIN), in 128-row blocks: both equal the oracle, the concurrent form also on a second run of
+    the same batch (fresh epochs)."""
+    keys = ("best_score", "sum_k", "n_ties", "status", "cand_score")
+    for i, (region, reads, kmin, kmax) in enumerate(first_boundary_cases()):
+        o = oracle.round3_1d([region], reads, kmin, kmax)
+        for flags, runs in ((capi.F_TEST_CHAIN, 2), (capi.F_TEST_CHAIN | capi.F_SERIAL_CHAIN, 1)):
+            with capi.Batch.create_1d([region], reads, kmin, kmax, flags=flags) as b:
+                for run in range(runs):
+                    b.run(); b.sync()
+                    g = b.fetch()
+                    for k in keys:
+                        assert np.array_equal(g[k], o[k]), (i, len(region[0]), region[1], kmin, flags, run, k)
+
+
 def test_1d_long_reads_over_one_register_block(capi, oracle):
     """Reads of 3.3-7.9 kb (beyond the 3072 rows a wave holds in registers): 1536-row chained blocks."""
     rng = np.random.default_rng(31)
