@@ -708,6 +708,56 @@ int nra_allele_split(int device, int32_t n_groups, const int64_t* group_off, int
                      int64_t site_cap, int32_t* sites, int64_t* site_off, int64_t sym_cap, uint8_t* site_sym,
                      int64_t* sym_off, int64_t* stats);
 
+/* ---- flank haplotypes: reads phased by the variants of the repeat's flanks (no counterpart in the reference)
+ *
+ * Integer arithmetic only: the outputs are a function of the group, bit for bit, and permuting the rows of a group
+ * permutes the per-row outputs and changes nothing else.
+ * Group: one per region.  Two backbone sides, bL (tL bases) and bR (tR bases), A C G T only, either may be empty, both
+ * written from the repeat outward.  The group has tL + tR columns: column o of the left side is column o, column o of
+ * the right side is column tL + o; o is the offset from the repeat.
+ * Row: one per read, up to two segments sL and sR, coded as consensus tracts (A C G T -> 0..3, any other byte -> 4), also
+ * written from the repeat outward.  An absent segment and an empty one are the same thing.
+ *   Alignment of a segment s (n >= 1 bases) to its side b (t columns): the start is pinned, the end is free.  Unit cost,
+ *   D[0][j] = j, D[i][0] = i and the recurrence of the consensus contract (code 4 mismatches every base).
+ *   e = min over 0 <= j <= t of D[n][j], j* = the smallest j that attains it.  Traceback from (n, j*) to (0, 0) with the
+ *   consensus priority: diagonal, insertion, deletion.  A column j < j* gets the code of the base aligned to it (0..4) or
+ *   5, deleted; a column j >= j* gets 6, not covered; insertions leave no mark.  If e > max_dist the side is left out:
+ *   every column 6, dist = -1, end = 0.  An absent side has dist = -2, end = 0 and every column 6.
+ *   Band: classes c in {1, 2, 4, 8, 16}, h = 32 c - 1, the band holds the diagonals j - i in [-h, h] (the device adds
+ *   h + 1, which changes nothing below).  A path from (0, 0) that leaves the band costs more than h, so every cell of row
+ *   n with a true value <= h has that value in the band and every other cell a value > h: a banded e <= min(h, max_dist)
+ *   is the true e with the true j*, and every traceback decision is the full matrix's (the argument of the consensus
+ *   contract).  A side starts in the smallest class with h >= min(max_dist, n / 32 + 8) and is
+ *   aligned in the next wider band until that holds or h >= max_dist says it is left out.  0 <= max_dist <= 500 (the
+ *   widest band proves 511).
+ *   Sites.  Per column, n[c] = the rows that show base c, cov = the rows whose code there is <= 5; a = the most voted
+ *   base, b = the second (ties: the smaller code).  A column at side offset o is a site iff o >= skip and
+ *   n[b] >= min_count and 100 n[b] >= min_share_pct (n[a] + n[b]) and 2 (n[a] + n[b]) >= cov.  Substitution sites only,
+ *   listed by column; of more than max_sites those with the largest n[b] stay (ties: the smaller column).
+ *   Haplotypes and verdict: steps 3 and 4 of the allele split above, word for word, over the rows with at least one
+ *   aligned side ("shows a base" treats the codes 4, 5 and 6 alike).  A row without an aligned side has label -1 and
+ *   takes part in nothing.  phased = 1 iff both haplotypes have min_count rows and min_sites sites are supported;
+ *   haplotype 0 is the larger one.  DESIGN.md section 25. */
+
+#define NRA_FLANK_MAX_DIST    500    /* largest max_dist of nra_flank_phase */
+
+/* Group g = rows [group_off[g], group_off[g+1]); segment `side` (0 left, 1 right) of row r = bytes [seg_off[2 r + side],
+ * seg_off[2 r + side + 1]) of `segs`; side `side` of group g = bytes [bb_off[2 g + side], bb_off[2 g + side + 1]) of
+ * `backbones` (a side or a segment of more than 200 000 bases: NRA_E_RANGE; a backbone byte other than A, C, G, T in
+ * either case: NRA_E_ARG).  0 <= max_dist <= 500, skip >= 0 (negative: NRA_E_ARG), the other thresholds as for
+ * nra_allele_split (below range NRA_E_ARG, above NRA_E_RANGE).  Writes label[r] (-1, 0, 1, 2 undecided),
+ * dist[2 r + side] and end[2 r + side] = j*; group_res[8 g ..] = phased, rows in haplotype 0, in 1, undecided, rows with
+ * label -1, n_sites, n_supported, iterations; site records, site_sym ([site][row]), their offsets and capacities as for
+ * nra_allele_split, the column of a record being the group column (tL and above: the right side); stats[] (16 counters
+ * in the layout of NRA_SPLIT_N_STATS, per aligned side) if not NULL.  Arguments are checked before the device is
+ * touched. */
+int nra_flank_phase(int device, int32_t n_groups, const int64_t* group_off, int32_t n_rows, const char* segs,
+                    const int64_t* seg_off, const char* backbones, const int64_t* bb_off, int32_t max_dist, int32_t skip,
+                    int32_t min_count, int32_t min_share_pct, int32_t min_purity_pct, int32_t min_sites,
+                    int32_t max_sites, int32_t max_iter, int32_t* label, int32_t* dist, int32_t* end,
+                    int32_t* group_res, int64_t site_cap, int32_t* sites, int64_t* site_off, int64_t sym_cap,
+                    uint8_t* site_sym, int64_t* sym_off, int64_t* stats);
+
 /* ---- motif runs: which motifs a tract is made of, how many units of each, and where (no counterpart in the reference)
  *
  * A motif set is M motifs u_0 .. u_{M-1}, 1 <= M <= 8, each uppercase ACGT of p_m = 1..32 bases, with S = sum of p_m <=

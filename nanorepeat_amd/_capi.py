@@ -38,7 +38,7 @@ EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count
            "nra_screen_create", "nra_screen_reads", "nra_screen_stats", "nra_screen_destroy",
            "nra_screen_set_motifs", "nra_screen_reads_partial",
            "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts", "nra_mixture_fit", "nra_mixture_bootstrap",
-           "nra_tract_consensus", "nra_allele_split", "nra_tract_segments", "nra_tract_periods")
+           "nra_tract_consensus", "nra_allele_split", "nra_flank_phase", "nra_tract_segments", "nra_tract_periods")
 
 
 E_RANGE = -3      # NRA_E_RANGE
@@ -205,6 +205,10 @@ def load():
     lib.nra_allele_split.restype = C.c_int
     lib.nra_allele_split.argtypes = [C.c_int, C.c_int32, pi64, C.c_int32, C.c_char_p, pi64, C.c_char_p, pi64] + \
                                     [C.c_int32] * 7 + [pi32, pi32, pi32, C.c_int64, pi32, pi64, C.c_int64, p8, pi64, pi64]
+    lib.nra_flank_phase.restype = C.c_int
+    lib.nra_flank_phase.argtypes = [C.c_int, C.c_int32, pi64, C.c_int32, C.c_char_p, pi64, C.c_char_p, pi64] + \
+                                   [C.c_int32] * 8 + [pi32, pi32, pi32, pi32, C.c_int64, pi32, pi64, C.c_int64, p8, pi64,
+                                                      pi64]
     lib.nra_tract_consensus.restype = C.c_int
     lib.nra_tract_consensus.argtypes = [C.c_int, C.c_int32, pi64, C.c_int32, C.c_char_p, pi64, C.c_int32, C.c_int32,
                                         C.c_int64, C.c_char_p, pi32, pi64, pi32, pi64]
@@ -952,6 +956,61 @@ def allele_split(groups, backbones, device=0, **thresholds):
                          for g in range(ng)],
                stats={k: int(v) for k, v in zip(SPLIT_STATS, stats)})
     for q, name in enumerate(SPLIT_RES):
+        out[name] = res[:, q].copy()
+    return out
+
+
+FLANK_MAX_DIST = 500      # NRA_FLANK_MAX_DIST: the largest, and the default, max_dist of nra_flank_phase
+FLANK_DEFAULTS = dict(max_dist=FLANK_MAX_DIST, skip=20, min_count=3, min_share_pct=25, min_purity_pct=75, min_sites=2,
+                      max_sites=256, max_iter=16)
+FLANK_RES = ("phased", "n0", "n1", "undecided", "left_out", "n_sites", "n_supported", "iterations")
+FLANK_STATS = SPLIT_STATS[:15] + ("groups_phased",)
+
+
+def flank_phase(groups, backbones, device=0, **thresholds):
+    """nra_flank_phase: groups = per region a list of rows (left segment, right segment), backbones = per region
+    (left side, right side), everything written from the repeat outward; an empty or None segment is absent
+    (thresholds: FLANK_DEFAULTS) -> dict(label [int32 per row], dist, end [int32 [rows, 2]], sites [int32 [n_sites, 12]:
+    group column, symbol of haplotype 0, of 1, A C G T counts of 0, of 1, supported], site_sym [uint8 [n_sites, rows]]
+    per group, phased, n0, n1, undecided, left_out, n_sites, n_supported, iterations [int32 per group], stats)."""
+    lib = load()
+    unknown = set(thresholds) - set(FLANK_DEFAULTS)
+    if unknown:
+        raise TypeError(f"flank_phase: unknown threshold(s) {sorted(unknown)}")
+    p = dict(FLANK_DEFAULTS, **thresholds)
+    groups = [[(a or "", b or "") for a, b in g] for g in groups]
+    backbones = [(a or "", b or "") for a, b in backbones]
+    ng = len(groups)
+    if len(backbones) != ng:
+        raise ValueError("one pair of backbone sides per group")
+    sizes = np.array([len(g) for g in groups], np.int64)
+    goff = np.zeros(ng + 1, np.int64)
+    np.cumsum(sizes, out=goff[1:])
+    data, off = pack_reads([s for g in groups for row in g for s in row])
+    bdata, boff = pack_reads([s for bb in backbones for s in bb])
+    nr = int(goff[-1])
+    most = np.minimum(boff[2::2] - boff[:-1:2], max(1, min(int(p["max_sites"]), 4096)))
+    site_cap, sym_cap = int(most.sum()), int((most * sizes).sum())
+    label = np.zeros(max(nr, 1), np.int32)
+    dist, end = np.zeros((max(nr, 1), 2), np.int32), np.zeros((max(nr, 1), 2), np.int32)
+    res = np.zeros((ng, 8), np.int32)
+    sites = np.zeros((max(site_cap, 1), 12), np.int32)
+    sym = np.zeros(max(sym_cap, 1), np.uint8)
+    soff, yoff = np.zeros(ng + 1, np.int64), np.zeros(ng + 1, np.int64)
+    stats = np.zeros(16, np.int64)
+    _check(lib.nra_flank_phase(device, ng, _ptr(goff, C.c_int64), nr, data, _ptr(off, C.c_int64), bdata,
+                               _ptr(boff, C.c_int64), *(int(p[k]) for k in FLANK_DEFAULTS), _ptr(label, C.c_int32),
+                               _ptr(dist, C.c_int32), _ptr(end, C.c_int32), _ptr(res, C.c_int32), site_cap,
+                               _ptr(sites, C.c_int32), _ptr(soff, C.c_int64), sym_cap, _ptr(sym, C.c_uint8),
+                               _ptr(yoff, C.c_int64), _ptr(stats, C.c_int64)))
+    out = dict(label=[label[goff[g]:goff[g + 1]].copy() for g in range(ng)],
+               dist=[dist[goff[g]:goff[g + 1]].copy() for g in range(ng)],
+               end=[end[goff[g]:goff[g + 1]].copy() for g in range(ng)],
+               sites=[sites[soff[g]:soff[g + 1]].copy() for g in range(ng)],
+               site_sym=[sym[yoff[g]:yoff[g + 1]].reshape(int(soff[g + 1] - soff[g]), int(sizes[g])).copy()
+                         for g in range(ng)],
+               stats={k: int(v) for k, v in zip(FLANK_STATS, stats)})
+    for q, name in enumerate(FLANK_RES):
         out[name] = res[:, q].copy()
     return out
 

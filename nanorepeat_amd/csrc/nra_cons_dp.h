@@ -45,7 +45,11 @@ __device__ __forceinline__ uint32_t cons_byte(const uint4& v, int q)
 // The whole wave aligns s (n codes) to b (t codes) in band class C and leaves the pointers at pblk.  Returns the
 // distance when the band proves it and it is at most max_dist (kend = the band column of (n, t)), else NRA_CONS_WIDEN
 // (align again in the next class) or NRA_CONS_LEFT_OUT.  The caller fences before a lane reads the pointers.
-template <int C>
+// FREE_END (k_flank_align, nra_flank.hip): the start is pinned and the end is free.  The band is centred on diagonal 0,
+// j - i in [-h, h + 1] with h = 32 C - 1: a path from (0, 0) that leaves [-h, h] costs more than h, so a cell of row n
+// with a banded value <= h holds its true value and every other cell is > h either way.  The distance is the minimum of
+// row n, at the smallest column j* that attains it; kend is the band column of (n, j*), j* = n + kend - h.
+template <int C, bool FREE_END = false>
 __device__ __forceinline__ int cons_band_align(int n, int t, const uint8_t* __restrict__ s, const uint8_t* __restrict__ b,
                                                uint4* __restrict__ pblk, int lane, int max_dist, int& kend)
 {
@@ -56,11 +60,15 @@ __device__ __forceinline__ int cons_band_align(int n, int t, const uint8_t* __re
     __shared__ uint8_t sb[B + CONS_TILE];
     __shared__ uint8_t ss[CONS_TILE];
     const int delta = t - n, ad = delta < 0 ? -delta : delta;
-    const int extra = B - 1 - ad;
-    if (extra < 0) return NRA_CONS_WIDEN;     // the band does not hold both corners
+    const int extra = FREE_END ? B - 2 : B - 1 - ad;
+    if constexpr (FREE_END) {
+        if (-delta > extra >> 1) return (extra >> 1) >= max_dist ? NRA_CONS_LEFT_OUT : NRA_CONS_WIDEN;   // row n is below the band
+    } else {
+        if (extra < 0) return NRA_CONS_WIDEN; // the band does not hold both corners
+    }
     const int h = extra >> 1;
-    const int lo = imin(0, delta) - h;        // diagonal of band column 0
-    const int w = ad + 2 * h;                 // distances up to w are proven
+    const int lo = FREE_END ? -h : imin(0, delta) - h;       // diagonal of band column 0
+    const int w = FREE_END ? h : ad + 2 * h;  // distances up to w are proven
     const int k0 = lane * C;
 
     int D[C];
@@ -121,6 +129,26 @@ __device__ __forceinline__ int cons_band_align(int n, int t, const uint8_t* __re
             }
             if (i % R == 0 || i == n) pblk[(size_t)((i - 1) / R) * WAVE + lane] = make_uint4(a0, a1, a2, a3);
         }
+    }
+    if constexpr (FREE_END) {
+        // the smallest value of row n and the smallest column that attains it
+        const int jb = n + lo + k0;
+        int best = INF;
+#pragma unroll
+        for (int x = 0; x < C; ++x) best = imin(best, (unsigned)(jb + x) <= (unsigned)t ? D[x] : INF);
+        int vmin = best;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) vmin = imin(vmin, __shfl_xor(vmin, d));
+        int at = INF;
+#pragma unroll
+        for (int x = C - 1; x >= 0; --x) at = ((unsigned)(jb + x) <= (unsigned)t && D[x] == vmin) ? k0 + x : at;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) at = imin(at, __shfl_xor(at, d));
+        // every lane holds both results: say so, and the caller's walk on lane 0 stays in scalar registers
+        vmin = __builtin_amdgcn_readfirstlane(vmin);
+        kend = __builtin_amdgcn_readfirstlane(at);
+        if (vmin > imin(w, max_dist)) return w >= max_dist ? NRA_CONS_LEFT_OUT : NRA_CONS_WIDEN;
+        return vmin;
     }
     // D[n][t] is band column delta - lo
     kend = delta - lo;

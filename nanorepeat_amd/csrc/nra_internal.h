@@ -414,9 +414,37 @@ struct NraSplitParams {
     int32_t min_count, min_share_pct, min_purity_pct, min_sites, max_sites, max_iter;
 };
 
+// Flank haplotypes (nra_flank.hip, nra_flank_host.cpp): pileup rows of the reads' flank segments on
+// the two reference flanks of a region, by the band DP with a pinned start and a free end, site calls with a coverage
+// per column, and k_split_phase for the two haplotypes.  A group's device columns are its left side, padded to a
+// multiple of 16, then its right side: both sides of a row start on a 16-byte boundary, and the host maps the columns
+// back.
+#define NRA_FLANK_SYM_NONE 6                  // row byte: the segment does not cover the column (= NRA_SPLIT_SYM_NONE)
+
+// one (row, side) alignment of a launch: segment codes at byte `seq` (a multiple of 16, n codes), its side's codes at
+// byte `bb` (t codes), traceback pointers from uint4 `ptr`, the side's part of the row from byte `row` (a multiple of 16)
+struct NraFlankItem {
+    uint64_t seq;
+    uint64_t ptr;
+    uint64_t row;
+    uint64_t bb;
+    int32_t n, t;
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+
+// flank haplotypes (nra_flank.hip).  Alignment: workgroup i (one wave) aligns items[i] in band class c; a decided
+// segment leaves status[2 i] = its distance, status[2 i + 1] = j*, and the codes of the columns below j* in its row
+// (the rest of the row keeps the NRA_FLANK_SYM_NONE the host set); else status[2 i] = NRA_CONS_WIDEN or
+// NRA_CONS_LEFT_OUT.  Count: as nra_launch_split_count with the rows that cover the column in place of m_v, and no site
+// at a side offset below `skip`; lpad[g] = the device column of group g's right side
+int nra_launch_flank_align(hipStream_t st, int c, int n_items, const NraFlankItem* items, const uint8_t* seqs,
+                           const uint8_t* backbones, uint4* ptrs, uint8_t* rows, int32_t* status, int max_dist);
+int nra_launch_flank_count(hipStream_t st, int n_blocks, const NraSplitBlock* blocks, const NraSplitGroup* groups,
+                           const int32_t* lpad, const int64_t* rowtab, const uint8_t* rows, NraSplitParams prm, int skip,
+                           int32_t* col_nb, uint8_t* col_ab);
 
 // allele consensus (nra_consensus.hip).  Alignment: workgroup i (one wave) aligns items[i] in band class c (1, 2, 4, 8
 // or 16) and, when its banded distance d proves exact and d <= max_dist, adds its votes to the group's tables, 1 to

@@ -195,7 +195,8 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
                       min_motif_count=4, min_motif_share=0.1, partial_reads=False, mixture="sklearn",
                       allele_consensus=False, allele_split=False, motif_runs=False, segment_motifs=None,
                       switch_cost=None, read_alignments=False, discover_periods=False, in_repeat_reads=False,
-                      bootstrap=0, bootstrap_confidence=0.95, **engines):
+                      bootstrap=0, bootstrap_confidence=0.95, flank_phase=False, flank_len=3000, flank_skip=20,
+                      flank_min_sites=2, **engines):
     """The BAM command from files to files (nanoRepeat_bam.py:614-751): for every region of the BED
     file, reads from the alignment file -> `<out_prefix>.details/<chr>/<region>.*` ->
     `<out_prefix>.NanoRepeat_output.tsv`.  The reference forks up to 16 workers, one region each;
@@ -219,10 +220,13 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
     units it shows, and per region whether any such read shows more than the largest spanning read.  bootstrap=B > 0
     (with mixture="gpu") adds the bootstrap files (bootstrap.py): `<region>.bootstrap.tsv` and
     `<out_prefix>.NanoRepeat_bootstrap.tsv` with a bootstrap_confidence interval for every allele size and the share
-    of the B replicates that have the called number of alleles.
+    of the B replicates that have the called number of alleles.  flank_phase=True adds the flank haplotype files
+    (flank.py): the reads, one-anchor reads included when partial_reads is on, phased by the variants of the flank_len
+    reference bases on either side of the repeat (no site within flank_skip bases of it; flank_min_sites supported sites
+    for a verdict), the table size allele x haplotype, and per haplotype the most units its one-anchor reads show.
     `engines` may carry aligner / scorer / structure_engine / motif_engine / extension_engine / mixture_engine /
-    consensus_engine / split_engine / segment_engine / path_aligner / period_engine / bootstrap_engine stand-ins.
-    Returns the regions."""
+    consensus_engine / split_engine / segment_engine / path_aligner / period_engine / bootstrap_engine / flank_engine
+    stand-ins.  Returns the regions."""
     from . import bam as nr_bam, mixture as nr_mixture
     nr_mixture.check_engine_name(mixture)
     _check_bootstrap(bootstrap, mixture)
@@ -239,12 +243,13 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
             continue
         live.append(region)
         reads_of.append(nr_io.read_fastq(region.region_fq_file))
+    flank = _flank_options(flank_phase, flank_len, flank_skip, flank_min_sites, regions, ref_fasta_dict)
     _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
                         read_structure, _motif_options(discover_motifs, min_motif_count, min_motif_share),
                         partial_reads, mixture, allele_consensus, allele_split,
                         _run_options(motif_runs, segment_motifs, switch_cost), read_alignments, discover_periods,
-                        in_repeat_reads=in_repeat_reads, bootstrap=(bootstrap, bootstrap_confidence))
+                        in_repeat_reads=in_repeat_reads, bootstrap=(bootstrap, bootstrap_confidence), flank=flank)
     return regions
 
 
@@ -267,11 +272,23 @@ def _run_options(motif_runs, segment_motifs, switch_cost):
     return dict(segment_motifs=segment_motifs, switch_cost=switch_cost) if motif_runs else None
 
 
+def _flank_options(flank_phase, flank_len, flank_skip, flank_min_sites, regions, ref_fasta_dict):
+    """None, or the keywords of flank.flank_regions; sets every region's reference flanks."""
+    if not flank_phase:
+        return None
+    if flank_len < 1:
+        raise ValueError(f"flank_len must be >= 1, not {flank_len!r}")
+    from . import flank as nr_flank
+    for region in regions:
+        nr_flank.set_flank_sides(region, ref_fasta_dict, flank_len)
+    return dict(flank_len=flank_len, skip=flank_skip, min_sites=flank_min_sites)
+
+
 def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
                         read_structure=False, motif_options=None, partial_reads=False, mixture="sklearn",
                         allele_consensus=False, allele_split=False, run_options=None, read_alignments=False,
-                        discover_periods=False, in_repeat_reads=False, candidates=None, bootstrap=(0, 0.95)):
+                        discover_periods=False, in_repeat_reads=False, candidates=None, bootstrap=(0, 0.95), flank=None):
     """The commands' common tail: steps 1-4 for the regions with reads, then one TSV row per BED region; with
     read_structure, the structure of every read with a size and the two structure files; with motif_options (a dict
     of motifs.motif_regions keywords), the tandem motifs of every read with a core and the two motif files; with
@@ -287,10 +304,13 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
     with in_repeat_reads, the four extensions of every read without an anchor, the two in-repeat files and a NOTICE per
     region where such reads show more repeat units than any spanning read.  `candidates` (the FASTQ command, a dict of
     _place_candidates keywords): the one-anchor and in-repeat reads come from the screen's candidates too.  `bootstrap`
-    (replicates, confidence): with replicates > 0, the bootstrap of every region's phasing and the two bootstrap files."""
+    (replicates, confidence): with replicates > 0, the bootstrap of every region's phasing and the two bootstrap files.
+    With `flank` (a dict of flank.flank_regions keywords), the flank haplotypes of every region with reads (one-anchor
+    reads too when partial_reads is on), the two flank files and a NOTICE per region with an unspanned haplotype."""
     if in_repeat_reads:
         for region in live:
             region.keep_no_anchor_reads = True
+    flank_of, flank_reads = live, reads_of
     quantify_regions(live, reads_of, data_type, fast_mode, num_cpu, device, scoring,
                      engines.get("aligner"), engines.get("scorer"), keep_candidates=read_alignments and not no_details)
     phase_regions(live, data_type, ploidy, max_mutual_overlap, max_num_components, remove_noisy_reads, seed,
@@ -324,6 +344,7 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
                 regions, live, reads_of, data_type, num_cpu, device, scoring, engines.get("aligner"), in_repeat_reads,
                 **candidates)
         if partial_reads:
+            flank_of, flank_reads = of, of_reads
             partial.partial_regions(of, of_reads, device=device, scoring=scoring, engine=engines.get("extension_engine"))
             for region in of:
                 partial.write_partial_reads(region)
@@ -379,6 +400,13 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
             periods.write_read_periods(region)
         periods.write_period_summary(regions, out_prefix)
         periods.report_foreign_units(live)
+    if flank is not None:
+        from . import flank as nr_flank
+        nr_flank.flank_regions(flank_of, flank_reads, device=device, engine=engines.get("flank_engine"), **flank)
+        for region in flank_of:
+            nr_flank.write_flank_phase(region)
+        nr_flank.write_flank_summary(regions, out_prefix)
+        nr_flank.report_unspanned_haplotypes(flank_of)
     if no_details:
         import shutil
         shutil.rmtree(f"{out_prefix}.details", ignore_errors=True)
@@ -392,7 +420,8 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         min_motif_share=0.1, mixture="sklearn", allele_consensus=False, allele_split=False,
                         motif_runs=False, segment_motifs=None, switch_cost=None, read_alignments=False,
                         discover_periods=False, partial_reads=False, in_repeat_reads=False, motif_share_pct=5,
-                        bootstrap=0, bootstrap_confidence=0.95, **engines):
+                        bootstrap=0, bootstrap_confidence=0.95, flank_phase=False, flank_len=3000, flank_skip=20,
+                        flank_min_sites=2, **engines):
     """The FASTQ / FASTA command (nanoRepeat.py:109, `-t fastq|fasta`) from files to files, without a genome mapper:
     the reads each region sees are chosen by the anchor k-mer screen (screen.reads_by_region) instead of a
     genome-wide mapping and a BAM window, then the BAM command's steps run unchanged.  Every region's reference
@@ -409,10 +438,10 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
     23) offers the reads with one anchor only and the reads made of a region's motif (at least motif_share_pct % of
     their k-mer windows) as candidates, written to `<region>.partial_candidates.fastq`; they go through the anchor step
     apart from the region's reads and never reach the sizes or the phasing.  bootstrap=B > 0 (with mixture="gpu")
-    adds the bootstrap files, as for quantify_from_bam.
+    adds the bootstrap files and flank_phase=True the flank haplotype files, as for quantify_from_bam.
     `engines` may carry aligner / scorer / screener / structure_engine / motif_engine / extension_engine /
     mixture_engine / consensus_engine / split_engine / segment_engine / path_aligner / period_engine /
-    bootstrap_engine stand-ins.  Returns the regions."""
+    bootstrap_engine / flank_engine stand-ins.  Returns the regions."""
     from . import screen as nr_screen, mixture as nr_mixture
     nr_mixture.check_engine_name(mixture)
     _check_bootstrap(bootstrap, mixture)
@@ -447,6 +476,7 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
         if reads:
             live.append(region)
             reads_of.append({name: seq for name, (seq, _) in reads.items()})
+    flank = _flank_options(flank_phase, flank_len, flank_skip, flank_min_sites, regions, ref_fasta_dict)
     _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
                         read_structure, _motif_options(discover_motifs, min_motif_count, min_motif_share),
@@ -454,7 +484,7 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         run_options=_run_options(motif_runs, segment_motifs, switch_cost),
                         read_alignments=read_alignments, discover_periods=discover_periods,
                         partial_reads=partial_reads, in_repeat_reads=in_repeat_reads, candidates=candidates,
-                        bootstrap=(bootstrap, bootstrap_confidence))
+                        bootstrap=(bootstrap, bootstrap_confidence), flank=flank)
     return regions
 
 

@@ -476,6 +476,84 @@ def split_panel(reads_per_haplotype=8, anchor_len=1000, model="hifi", seed=6):
                 planted=[[tr if len(tr) == 2 else None for tr in alleles] for _, _, alleles in loci])
 
 
+def flank_panel(reads_per_haplotype=8, anchor_len=1000, flank_len=3000, flank_skip=20, model="hifi", seed=1):
+    """A small panel whose haplotypes differ in the flanks of the repeat, for the flank haplotypes (flank.py).  Every
+    region has at least `flank_len` + 800 reference bases on either side; haplotype 0 is the reference, haplotype 1
+    carries substitutions in both flanks, one of them nearer to the repeat than `flank_skip` (never a site).  Regions:
+    0 (BED CAG) two alleles of different size, 20 and 45 units, one per haplotype; 1 (TATTG) two alleles of equal size,
+    16 units, on different haplotypes; 2 (CGG) a spanned allele of 18 units on haplotype 0 (half as many reads again, so
+    that the spanned haplotype holds the most voted base of every site and the other one, none of whose rows covers both
+    sides, is linked through the second) and an allele longer than every read on haplotype 1, whose reads hold one anchor
+    only (`reads_per_haplotype` left-anchored and as many right-anchored, each with 120 to 200 units); 3 (AAAAG) a control with the same flanks on both haplotypes and two
+    size alleles, 12 and 30 units; 4 (GGCCTG) 10 and 25 units, where every other read reaches only 200 to 500 bases into
+    one flank.  Reads go through the `model` error channel, half reverse-complemented.  Its own random stream; the
+    default seed is one for which the contract's restatement puts every read on its planted haplotype (DESIGN.md section
+    25.3 counts the seeds that do).
+
+    Returns dict(ref, bed, regions, reads, truth) like panel() (truth = {name: (region, units)}), plus haplotype =
+    {name: 0 / 1, None in region 3}, kind = {name: "spanning" / "left" / "right"} and planted = [per region: (left
+    offsets, right offsets) of haplotype 1's substitutions]."""
+    rng = np.random.default_rng(seed)
+    loci = [("CAG", 20, ((20, "spanning"), (45, "spanning")), True),
+            ("TATTG", 16, ((16, "spanning"), (16, "spanning")), True),
+            ("CGG", 20, ((18, "spanning"), (400, "one")), True),
+            ("AAAAG", 15, ((12, "spanning"), (30, "spanning")), False),
+            ("GGCCTG", 10, ((10, "spanning"), (25, "spanning")), True)]
+    offsets = ((flank_skip // 4, 150, 420, 900, 1700, 2500), (flank_skip // 2, 90, 300, 800, 1400, 2200))
+    gap, extra = 1000, 800
+    parts, regions, at = [], [], 0
+    for unit, kref, _, _ in loci:
+        left, right = rand_seq(rng, flank_len + extra), rand_seq(rng, flank_len + extra)
+        start = at + gap + len(left)
+        regions.append(("chr1", start, start + len(unit) * kref, unit))
+        parts += [rand_seq(rng, gap), left, unit * kref, right]
+        at += gap + len(left) + len(unit) * kref + len(right)
+    parts.append(rand_seq(rng, gap))
+    chrom = "".join(parts)
+
+    def sub(seq, at):
+        return seq[:at] + "ACGT"[("ACGT".index(seq[at]) + 1 + at % 3) % 4] + seq[at + 1:]
+
+    raw, truth, haplotype, kind, planted = [], {}, {}, {}, []
+    reach = flank_len + 300
+    for g, ((unit, _, alleles, differ), (_, st, en, _)) in enumerate(zip(loci, regions)):
+        offs = tuple(tuple(o for o in side if o < flank_len) for side in offsets) if differ else ((), ())
+        planted.append(offs)
+        for h, (k, how) in enumerate(alleles):
+            left, right = chrom[st - reach:st], chrom[en:en + reach]
+            if h == 1:
+                for o in offs[0]:
+                    left = sub(left, len(left) - 1 - o)
+                for o in offs[1]:
+                    right = sub(right, o)
+            n_reads = 2 * reads_per_haplotype if how == "one" else reads_per_haplotype * 3 // 2 if g == 2 else \
+                reads_per_haplotype
+            for i in range(n_reads):
+                lo, ro = (int(rng.integers(anchor_len, reach + 1)) for _ in range(2))
+                if g == 4 and i % 2:
+                    short = int(rng.integers(200, 501))
+                    lo, ro = (short, ro) if i % 4 == 1 else (lo, short)
+                what = "spanning" if how == "spanning" else ("left", "right")[i % 2]
+                name = f"f{g}_{h}_{what}_{i:02d}"
+                shown = k if how == "spanning" else int(rng.integers(120, 201))
+                if what == "spanning":
+                    seq = left[len(left) - lo:] + unit * k + right[:ro]
+                elif what == "left":
+                    seq = left[len(left) - lo:] + unit * shown
+                else:
+                    seq = unit * shown + right[:ro]
+                raw.append((name, seq))
+                truth[name] = (g, k)
+                haplotype[name] = h if differ else None
+                kind[name] = what
+    seqs = apply_errors_batch(rng, [s for _, s in raw], model)
+    reads = [(name, revcomp(s) if rng.random() < 0.5 else s) for (name, _), s in zip(raw, seqs)]
+    order = rng.permutation(len(reads))
+    reads = [reads[i] for i in order]
+    return dict(ref={"chr1": chrom}, bed=[f"{c}\t{st}\t{en}\t{u}\n" for c, st, en, u in regions], regions=regions,
+                reads=reads, truth=truth, haplotype=haplotype, kind=kind, planted=planted)
+
+
 def primitive_unit(rng, m):
     """A random unit of m bases that is no power of a shorter word."""
     while True:
