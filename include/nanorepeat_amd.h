@@ -606,6 +606,55 @@ int nra_mixture_bootstrap(int device, int64_t n_x, const double* x, int64_t n_z,
                           const int32_t* idx, int32_t flags, int32_t* status, int32_t* order, int32_t* best_start,
                           double* lb, double* w, double* mu, double* var);
 
+/* ---- censored allele fit: spanning reads and lower bounds in one mixture likelihood (no counterpart in the reference)
+ *
+ * A problem is N values in the log domain y = ln(10 + size), the first n_exact of them exact observations, the other
+ * N - n_exact lower bounds (right-censored observations), and a known standard deviation tau.  A model (n, open) has n
+ * closed components N(nu_k, tau^2) with weights w_k and, when open = 1, one open component with weight w_o: density 0
+ * at every exact value and survival 1 at every bound (an allele no read spans).  Everything in float64, nothing
+ * contracted into an fma.  With u = z sqrt(1/2):
+ *   logS(z)   = log(0.5 erfc(u))             lambda(z) = sqrt(2/pi) exp(-u u) / erfc(u)      for u <= 0
+ *   logS(z)   = log(0.5 erfcx(u)) - u u      lambda(z) = sqrt(2/pi) / erfcx(u)               for u >  0
+ *   exact y:  log p(y, k) = (log w_k - log(2 pi tau^2) / 2) - (y - nu_k)^2 (1 / (2 tau^2)); the open component: none
+ *   bound c:  log p(c, k) = log w_k + logS((c - nu_k) (1 / tau));  the open component: log w_o
+ * One fit from the start means nu^0, with w = 1 / (n + open):
+ *   E-step: log p(y) by log-sum-exp over the components (maximum, sum of exp in component order, the open one last),
+ *   r = exp(log p(y, k) - log p(y)), lb = (sum of log p(y)) / N.
+ *   M-step: nk = sum r + 10 eps (eps = 2^-52), w = nk / N for every component; for a closed one with sum r > 1e-12,
+ *   nu_k = (sum over exact of r y + sum over bounds of r (nu_k + tau lambda(z))) / nk, else nu_k stays.
+ *   Stop after the M-step of the first E-step with |lb - lb of the E-step before| < tol (converged = 1), or after
+ *   max_iter E-steps (converged = 0).
+ * Outputs per fit: ll = lb N of its last E-step, n_iter = E-steps, converged, and w, nu of its last M-step.  A fit is a
+ * function of its problem and its start means alone: not of the other fits of the call, their order, the flags or the
+ * run.  The posteriors of a model are the r of one E-step from its w and nu.  DESIGN.md section 26. */
+
+#define NRA_CENS_F_STREAM        1   /* testing / comparison: every problem streams its values from memory */
+#define NRA_CENS_MAX_COMPONENTS  8   /* closed components of a model */
+#define NRA_CENS_MAX_N     1048576   /* values of a problem */
+#define NRA_CENS_MAX_ITER      500   /* largest max_iter */
+
+/* Problem p = prob_n[p] values from values[prob_off[p]] (of n_values in all), the first prob_n_exact[p] exact, with
+ * tau = prob_tau[p].  Fit f = (fit_n[f] closed components, fit_open[f] in {0, 1}) on problem fit_problem[f]; its start
+ * means are the next fit_n[f] entries of `starts`, fits in order.  Writes ll[f], n_iter[f], converged[f], nu[s + k] with
+ * s = fit_n[0] + ... + fit_n[f-1], and w[s + f' + k] with f' = fit_open[0] + ... + fit_open[f-1] (the open weight last).
+ * n outside 1..8, N > 1 048 576 or max_iter > 500 is NRA_E_RANGE; n_exact outside 1..N, a value, start or tau that is
+ * not finite, tau <= 0, open other than 0 or 1, open = 1 on a problem without a bound, max_iter < 1, tol negative or
+ * not finite, or an unknown flag is NRA_E_ARG.  Arguments are checked before the device is touched. */
+int nra_censored_fit(int device, int64_t n_values, const double* values, int32_t n_problems, const int64_t* prob_off,
+                     const int32_t* prob_n, const int32_t* prob_n_exact, const double* prob_tau, int32_t n_fits,
+                     const int32_t* fit_problem, const int32_t* fit_n, const int32_t* fit_open, const double* starts,
+                     int32_t max_iter, double tol, int32_t flags, double* ll, double* w, double* nu, int32_t* n_iter,
+                     int32_t* converged);
+
+/* Problems as above, one model each: (model_n[p], model_open[p]) with nu[s + k] and w[s + p' + k] laid out as the
+ * outputs of nra_censored_fit with problem p in the place of fit f (weights > 0 and finite, else NRA_E_ARG).  Writes
+ * the posteriors of value i of problem p at resp[R_p + i (n + open) + k], R_p = the entries of the problems before;
+ * resp holds n_resp entries (fewer than needed: NRA_E_RANGE).  The other errors as for nra_censored_fit. */
+int nra_censored_posteriors(int device, int64_t n_values, const double* values, int32_t n_problems,
+                            const int64_t* prob_off, const int32_t* prob_n, const int32_t* prob_n_exact,
+                            const double* prob_tau, const int32_t* model_n, const int32_t* model_open, const double* w,
+                            const double* nu, int64_t n_resp, double* resp);
+
 /* ---- allele consensus: one sequence per group of tracts (no counterpart in the reference) ----------------------------
  *
  * Integer arithmetic throughout: the outputs are a function of the group alone, bit for bit.

@@ -27,6 +27,7 @@ F_NO_QUANTA = 2048    # testing / comparison, 1D: reverse and forward sweeps as 
 F_QUANTA_2L = 4096    # accepted and ignored (round 4's first form of the quanta as two launches)
 F_SERIAL_CHAIN = 128  # testing / comparison, 1D: a long read's row blocks one after the other in one wave
 MIX_STREAM = 1        # testing / comparison, nra_mixture_fit: every problem streams its points from memory
+CENS_F_STREAM = 1     # testing / comparison, nra_censored_fit: every problem streams its values from memory
 MIX_ONE_CLASS = 2     # testing / comparison, nra_mixture_fit: no separate kernel for problems of up to 1024 points
 F_FULL_ANCHORS = 8192  # testing / comparison, 1D: the exact cell over every anchor column (no relaxed cells, no re-sweep)
 
@@ -38,7 +39,8 @@ EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count
            "nra_screen_create", "nra_screen_reads", "nra_screen_stats", "nra_screen_destroy",
            "nra_screen_set_motifs", "nra_screen_reads_partial",
            "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts", "nra_mixture_fit", "nra_mixture_bootstrap",
-           "nra_tract_consensus", "nra_allele_split", "nra_flank_phase", "nra_tract_segments", "nra_tract_periods")
+           "nra_tract_consensus", "nra_allele_split", "nra_flank_phase", "nra_tract_segments", "nra_tract_periods",
+           "nra_censored_fit", "nra_censored_posteriors")
 
 
 E_RANGE = -3      # NRA_E_RANGE
@@ -202,6 +204,12 @@ def load():
     lib.nra_mixture_fit.restype = C.c_int
     lib.nra_mixture_fit.argtypes = [C.c_int, C.c_int64, pf64, C.c_int32, pi64, pi32, pi32, C.c_int32, pi32, pi32, pi32,
                                     C.c_int32, pf64, pf64, pf64, pf64, pi32, pi32]
+    lib.nra_censored_fit.restype = C.c_int
+    lib.nra_censored_fit.argtypes = [C.c_int, C.c_int64, pf64, C.c_int32, pi64, pi32, pi32, pf64, C.c_int32, pi32, pi32,
+                                     pi32, pf64, C.c_int32, C.c_double, C.c_int32, pf64, pf64, pf64, pi32, pi32]
+    lib.nra_censored_posteriors.restype = C.c_int
+    lib.nra_censored_posteriors.argtypes = [C.c_int, C.c_int64, pf64, C.c_int32, pi64, pi32, pi32, pf64, pi32, pi32,
+                                            pf64, pf64, C.c_int64, pf64]
     lib.nra_allele_split.restype = C.c_int
     lib.nra_allele_split.argtypes = [C.c_int, C.c_int32, pi64, C.c_int32, C.c_char_p, pi64, C.c_char_p, pi64] + \
                                     [C.c_int32] * 7 + [pi32, pi32, pi32, C.c_int64, pi32, pi64, C.c_int64, p8, pi64, pi64]
@@ -812,6 +820,77 @@ def mixture_fit(samples, prob_off, prob_n, prob_d, fit_problem, fit_n, starts, f
                                _ptr(out["mu"], C.c_double), _ptr(out["var"], C.c_double),
                                _ptr(out["n_iter"], C.c_int32), _ptr(out["converged"], C.c_int32)))
     return out
+
+
+CENS_MAX_COMPONENTS = 8      # NRA_CENS_MAX_COMPONENTS
+CENS_MAX_ITER = 500          # NRA_CENS_MAX_ITER
+
+
+def _censored_problems(values, prob_off, prob_n, prob_n_exact, prob_tau):
+    y = np.ascontiguousarray(values, np.float64).ravel()
+    po = np.ascontiguousarray(prob_off, np.int64)
+    pn = np.ascontiguousarray(prob_n, np.int32)
+    pe = np.ascontiguousarray(prob_n_exact, np.int32)
+    pt = np.ascontiguousarray(prob_tau, np.float64)
+    if not (len(po) == len(pn) == len(pe) == len(pt)):
+        raise ValueError("one offset, value count, exact count and tau per problem")
+    return y, po, pn, pe, pt
+
+
+def censored_fit(values, prob_off, prob_n, prob_n_exact, prob_tau, fit_problem, fit_n, fit_open, starts, max_iter=500,
+                 tol=1e-9, flags=0, device=0):
+    """nra_censored_fit: problem p = prob_n[p] log-domain values from values[prob_off[p]], the first prob_n_exact[p]
+    exact, the others lower bounds, sd prob_tau[p]; fit f = fit_n[f] closed components (+ an open one where fit_open[f])
+    on problem fit_problem[f] from the next fit_n[f] means of `starts` -> dict(ll, n_iter, converged per fit; nu_off,
+    w_off = where a fit's means and weights begin; nu [closed components]; w [components, the open weight last])."""
+    lib = load()
+    y, po, pn, pe, pt = _censored_problems(values, prob_off, prob_n, prob_n_exact, prob_tau)
+    fp = np.ascontiguousarray(fit_problem, np.int32)
+    fn = np.ascontiguousarray(fit_n, np.int32)
+    fo = np.ascontiguousarray(fit_open, np.int32)
+    st = np.ascontiguousarray(starts, np.float64)
+    if not (len(fp) == len(fn) == len(fo)):
+        raise ValueError("one problem, order and open switch per fit")
+    if len(st) != int(np.maximum(fn, 0).sum()):
+        raise ValueError("one start mean per closed component of every fit")
+    nf = len(fn)
+    nu_off = np.zeros(nf + 1, np.int64)
+    np.cumsum(np.maximum(fn, 0), out=nu_off[1:])
+    w_off = np.zeros(nf + 1, np.int64)
+    np.cumsum(np.maximum(fn, 0) + np.clip(fo, 0, 1), out=w_off[1:])
+    out = dict(ll=np.zeros(nf), n_iter=np.zeros(nf, np.int32), converged=np.zeros(nf, np.int32), nu_off=nu_off,
+               w_off=w_off, nu=np.zeros(int(nu_off[-1])), w=np.zeros(int(w_off[-1])))
+    _check(lib.nra_censored_fit(device, len(y), _ptr(y, C.c_double), len(po), _ptr(po, C.c_int64), _ptr(pn, C.c_int32),
+                                _ptr(pe, C.c_int32), _ptr(pt, C.c_double), nf, _ptr(fp, C.c_int32), _ptr(fn, C.c_int32),
+                                _ptr(fo, C.c_int32), _ptr(st, C.c_double), int(max_iter), float(tol), flags,
+                                _ptr(out["ll"], C.c_double), _ptr(out["w"], C.c_double), _ptr(out["nu"], C.c_double),
+                                _ptr(out["n_iter"], C.c_int32), _ptr(out["converged"], C.c_int32)))
+    return out
+
+
+def censored_posteriors(values, prob_off, prob_n, prob_n_exact, prob_tau, model_n, model_open, w, nu, device=0):
+    """nra_censored_posteriors: one model (model_n[p] closed components, model_open[p]) per problem, its weights and
+    means laid out as censored_fit returns them -> a list with one [prob_n[p], n + open] array of posteriors per
+    problem (the open column last)."""
+    lib = load()
+    y, po, pn, pe, pt = _censored_problems(values, prob_off, prob_n, prob_n_exact, prob_tau)
+    mn = np.ascontiguousarray(model_n, np.int32)
+    mo = np.ascontiguousarray(model_open, np.int32)
+    ww = np.ascontiguousarray(w, np.float64)
+    mu = np.ascontiguousarray(nu, np.float64)
+    if not (len(mn) == len(mo) == len(po)):
+        raise ValueError("one model per problem")
+    nc = np.maximum(mn, 0).astype(np.int64) + np.clip(mo, 0, 1)
+    if len(mu) != int(np.maximum(mn, 0).sum()) or len(ww) != int(nc.sum()):
+        raise ValueError("one mean per closed component and one weight per component of every model")
+    r_off = np.zeros(len(po) + 1, np.int64)
+    np.cumsum(np.maximum(pn, 0).astype(np.int64) * nc, out=r_off[1:])
+    resp = np.zeros(int(r_off[-1]))
+    _check(lib.nra_censored_posteriors(device, len(y), _ptr(y, C.c_double), len(po), _ptr(po, C.c_int64),
+                                       _ptr(pn, C.c_int32), _ptr(pe, C.c_int32), _ptr(pt, C.c_double),
+                                       _ptr(mn, C.c_int32), _ptr(mo, C.c_int32), _ptr(ww, C.c_double),
+                                       _ptr(mu, C.c_double), len(resp), _ptr(resp, C.c_double)))
+    return [resp[r_off[p]:r_off[p + 1]].reshape(int(pn[p]), int(nc[p])) for p in range(len(po))]
 
 
 BOOT_DECIDED, BOOT_NEEDS_MORE = 0, 1      # NRA_BOOT_DECIDED, NRA_BOOT_NEEDS_MORE

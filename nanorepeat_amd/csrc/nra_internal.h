@@ -344,6 +344,19 @@ struct NraBootProblem {
     int32_t m, d, first_n, n_cap, max_n, pad;
 };
 
+// Censored allele fit (nra_censored.hip, nra_censored_host.cpp): one wavefront per fit.  A problem
+// of up to 64 * NRA_CENS_KREG values keeps them in registers, a larger one streams them.
+#define NRA_CENS_KREG 8
+
+// one fit, or one model of the posteriors: its problem's n_points values from double `off` of the value buffer (the
+// first n_exact exact), tau, n closed components and `open`; its means (start and result) from entry `nu_off`, its
+// n + open weights from entry `w_off`, its posteriors (k_censored_resp) from entry `resp_off`
+struct NraCensFit {
+    int64_t off, nu_off, w_off, resp_off;
+    double tau;
+    int32_t n_points, n_exact, n, open;
+};
+
 // Allele consensus (nra_consensus.hip, nra_consensus_host.cpp): banded unit-cost alignment of every tract of a group to
 // the group's backbone, one wave per tract, votes into the group's tables, then a new backbone per group (DESIGN.md
 // section 18).  Band class c: a lane owns c consecutive diagonals, the band holds 64 c.
@@ -489,6 +502,16 @@ int nra_launch_mixture_boot(hipStream_t st, int d, int kreg, int n, const int32_
                             const NraBootProblem* probs, const double* x, const double* z, const int32_t* idx,
                             const int32_t* starts, int32_t* status, int32_t* order, int32_t* best_start, double* lb,
                             double* w, double* mu, double* var);
+
+// censored allele fit (nra_censored.hip).  Fit: workgroup b (one wave) fits fits[ids[b]] from the means at starts[nu_off
+// ..]; kreg is NRA_CENS_KREG (every problem of the launch has n_points <= 64 * kreg) or 0 = streaming.  Writes ll[f],
+// iter[2 f] = E-steps, iter[2 f + 1] = converged, nu[nu_off + k], w[w_off + k].  Resp: workgroup b (one wave) writes
+// the n_points x (n + open) posteriors of models[b] from w and nu
+int nra_launch_censored_fit(hipStream_t st, int kreg, int n, const int32_t* ids, const NraCensFit* fits,
+                            const double* values, const double* starts, int max_iter, double tol, double* ll, double* w,
+                            double* nu, int32_t* iter);
+int nra_launch_censored_resp(hipStream_t st, int n, const NraCensFit* models, const double* values, const double* w,
+                             const double* nu, double* resp);
 
 // copies between pageable host memory and the device through the calling thread's pinned stage (nra_host.cpp);
 // they return a hipError_t

@@ -196,7 +196,8 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
                       allele_consensus=False, allele_split=False, motif_runs=False, segment_motifs=None,
                       switch_cost=None, read_alignments=False, discover_periods=False, in_repeat_reads=False,
                       bootstrap=0, bootstrap_confidence=0.95, flank_phase=False, flank_len=3000, flank_skip=20,
-                      flank_min_sites=2, **engines):
+                      flank_min_sites=2, censored_fit=False, censored_error_rate=None, censored_max_alleles=6,
+                      **engines):
     """The BAM command from files to files (nanoRepeat_bam.py:614-751): for every region of the BED
     file, reads from the alignment file -> `<out_prefix>.details/<chr>/<region>.*` ->
     `<out_prefix>.NanoRepeat_output.tsv`.  The reference forks up to 16 workers, one region each;
@@ -224,12 +225,18 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
     (flank.py): the reads, one-anchor reads included when partial_reads is on, phased by the variants of the flank_len
     reference bases on either side of the repeat (no site within flank_skip bases of it; flank_min_sites supported sites
     for a verdict), the table size allele x haplotype, and per haplotype the most units its one-anchor reads show.
+    censored_fit=True (with partial_reads and / or in_repeat_reads, else ValueError) adds the censored allele fit
+    (censored.py): the spanning reads' sizes and the bounds of the one-anchor and in-repeat reads in one mixture
+    likelihood, with an open allele where no read spans one; censored_error_rate is its sd in the log domain (None: the
+    data type's error rate) and censored_max_alleles the largest number of closed alleles it tries.
     `engines` may carry aligner / scorer / structure_engine / motif_engine / extension_engine / mixture_engine /
-    consensus_engine / split_engine / segment_engine / path_aligner / period_engine / bootstrap_engine / flank_engine
-    stand-ins.  Returns the regions."""
+    consensus_engine / split_engine / segment_engine / path_aligner / period_engine / bootstrap_engine / flank_engine /
+    censored_engine stand-ins.  Returns the regions."""
     from . import bam as nr_bam, mixture as nr_mixture
     nr_mixture.check_engine_name(mixture)
     _check_bootstrap(bootstrap, mixture)
+    censored = _censored_options(censored_fit, censored_error_rate, censored_max_alleles, partial_reads,
+                                 in_repeat_reads)
     regions = nr_io.read_repeat_region_file(repeat_region_bed, no_details)
     ref_fasta_dict = nr_io.fasta_file2dict(ref_fasta)
     live, reads_of = [], []
@@ -249,7 +256,8 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
                         read_structure, _motif_options(discover_motifs, min_motif_count, min_motif_share),
                         partial_reads, mixture, allele_consensus, allele_split,
                         _run_options(motif_runs, segment_motifs, switch_cost), read_alignments, discover_periods,
-                        in_repeat_reads=in_repeat_reads, bootstrap=(bootstrap, bootstrap_confidence), flank=flank)
+                        in_repeat_reads=in_repeat_reads, bootstrap=(bootstrap, bootstrap_confidence), flank=flank,
+                        censored=censored)
     return regions
 
 
@@ -284,11 +292,27 @@ def _flank_options(flank_phase, flank_len, flank_skip, flank_min_sites, regions,
     return dict(flank_len=flank_len, skip=flank_skip, min_sites=flank_min_sites)
 
 
+def _censored_options(censored_fit, error_rate, max_alleles, partial_reads, in_repeat_reads):
+    """None, or the keywords of censored.censored_regions."""
+    if not censored_fit:
+        return None
+    if not (partial_reads or in_repeat_reads):
+        raise ValueError("censored_fit=True needs partial_reads=True and / or in_repeat_reads=True: they size the reads "
+                         "it adds to the fit")
+    if error_rate is not None and not (error_rate > 0 and error_rate < float("inf")):
+        raise ValueError(f"censored_error_rate must be finite and > 0, not {error_rate!r}")
+    if not 1 <= max_alleles <= 8:
+        raise ValueError(f"censored_max_alleles must be in 1..8, not {max_alleles!r}")
+    return dict(error_rate=error_rate, max_alleles=max_alleles, use_partial=bool(partial_reads),
+                use_in_repeat=bool(in_repeat_reads))
+
+
 def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
                         read_structure=False, motif_options=None, partial_reads=False, mixture="sklearn",
                         allele_consensus=False, allele_split=False, run_options=None, read_alignments=False,
-                        discover_periods=False, in_repeat_reads=False, candidates=None, bootstrap=(0, 0.95), flank=None):
+                        discover_periods=False, in_repeat_reads=False, candidates=None, bootstrap=(0, 0.95), flank=None,
+                        censored=None):
     """The commands' common tail: steps 1-4 for the regions with reads, then one TSV row per BED region; with
     read_structure, the structure of every read with a size and the two structure files; with motif_options (a dict
     of motifs.motif_regions keywords), the tandem motifs of every read with a core and the two motif files; with
@@ -306,7 +330,9 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
     _place_candidates keywords): the one-anchor and in-repeat reads come from the screen's candidates too.  `bootstrap`
     (replicates, confidence): with replicates > 0, the bootstrap of every region's phasing and the two bootstrap files.
     With `flank` (a dict of flank.flank_regions keywords), the flank haplotypes of every region with reads (one-anchor
-    reads too when partial_reads is on), the two flank files and a NOTICE per region with an unspanned haplotype."""
+    reads too when partial_reads is on), the two flank files and a NOTICE per region with an unspanned haplotype.
+    With `censored` (a dict of censored.censored_regions keywords), after the one-anchor and in-repeat reads: the
+    censored allele fit of every region with reads or candidates, its three files and one NOTICE."""
     if in_repeat_reads:
         for region in live:
             region.keep_no_anchor_reads = True
@@ -357,6 +383,15 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
                 partial.write_in_repeat_reads(region)
             partial.write_in_repeat_summary(regions, out_prefix, shared, unscreened)
             partial.report_exceeding_in_repeat_reads(of)
+        if censored is not None:
+            from . import censored as nr_censored
+            nr_censored.censored_regions(of, data_type, engine=engines.get("censored_engine"), device=device,
+                                         **censored)
+            for region in of:
+                nr_censored.write_censored_fit(region)
+                nr_censored.write_censored_reads(region)
+            nr_censored.write_censored_summary(regions, out_prefix)
+            nr_censored.report_censored_calls(of)
     if allele_consensus:
         from . import consensus
         consensus.consensus_regions(live, device=device, engine=engines.get("consensus_engine"),
@@ -421,7 +456,8 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         motif_runs=False, segment_motifs=None, switch_cost=None, read_alignments=False,
                         discover_periods=False, partial_reads=False, in_repeat_reads=False, motif_share_pct=5,
                         bootstrap=0, bootstrap_confidence=0.95, flank_phase=False, flank_len=3000, flank_skip=20,
-                        flank_min_sites=2, **engines):
+                        flank_min_sites=2, censored_fit=False, censored_error_rate=None, censored_max_alleles=6,
+                        **engines):
     """The FASTQ / FASTA command (nanoRepeat.py:109, `-t fastq|fasta`) from files to files, without a genome mapper:
     the reads each region sees are chosen by the anchor k-mer screen (screen.reads_by_region) instead of a
     genome-wide mapping and a BAM window, then the BAM command's steps run unchanged.  Every region's reference
@@ -438,13 +474,16 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
     23) offers the reads with one anchor only and the reads made of a region's motif (at least motif_share_pct % of
     their k-mer windows) as candidates, written to `<region>.partial_candidates.fastq`; they go through the anchor step
     apart from the region's reads and never reach the sizes or the phasing.  bootstrap=B > 0 (with mixture="gpu")
-    adds the bootstrap files and flank_phase=True the flank haplotype files, as for quantify_from_bam.
+    adds the bootstrap files, flank_phase=True the flank haplotype files and censored_fit=True the censored allele fit,
+    as for quantify_from_bam.
     `engines` may carry aligner / scorer / screener / structure_engine / motif_engine / extension_engine /
     mixture_engine / consensus_engine / split_engine / segment_engine / path_aligner / period_engine /
-    bootstrap_engine / flank_engine stand-ins.  Returns the regions."""
+    bootstrap_engine / flank_engine / censored_engine stand-ins.  Returns the regions."""
     from . import screen as nr_screen, mixture as nr_mixture
     nr_mixture.check_engine_name(mixture)
     _check_bootstrap(bootstrap, mixture)
+    censored = _censored_options(censored_fit, censored_error_rate, censored_max_alleles, partial_reads,
+                                 in_repeat_reads)
     regions = nr_io.read_repeat_region_file(repeat_region_bed, no_details)
     ref_fasta_dict = nr_io.fasta_file2dict(ref_fasta)
     screened = []
@@ -484,7 +523,7 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         run_options=_run_options(motif_runs, segment_motifs, switch_cost),
                         read_alignments=read_alignments, discover_periods=discover_periods,
                         partial_reads=partial_reads, in_repeat_reads=in_repeat_reads, candidates=candidates,
-                        bootstrap=(bootstrap, bootstrap_confidence), flank=flank)
+                        bootstrap=(bootstrap, bootstrap_confidence), flank=flank, censored=censored)
     return regions
 
 
