@@ -60,7 +60,12 @@ int32_t nro_align(const uint8_t* q, int32_t qlen, const uint8_t* t, int32_t tlen
 
 /* Same alignment with traceback: writes a minimap2-style --eqx CIGAR ("12=1X3I...")
  * into cigar (capacity cap, NUL terminated) and the extents.  Returns score, or -1 if
- * cap is too small.  O(qlen*tlen) memory: small cases only. */
+ * cap is too small.  O(qlen*tlen) memory: small cases only.
+ * Which of the co-optimal paths: it ends in the best cell (the maximum packed value, then the
+ * smallest column, then the smallest row); at H the first input that holds the value wins, in the
+ * order d, E, F, E2, F2; d continues at (i-1, j-1) when H there >= fresh(j), else the path starts
+ * at this cell; a gap state extends on a tie with opening.  '=' where the two codes are equal (N
+ * against N included), 'X' otherwise.  tests/path_check.py checks such a record independently. */
 int32_t nro_align_cigar(const uint8_t* q, int32_t qlen, const uint8_t* t, int32_t tlen,
                         const nro_scoring_t* sc, int mode, int32_t wa, int32_t wb,
                         char* cigar, int32_t cap,

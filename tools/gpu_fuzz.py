@@ -1,9 +1,11 @@
 """Differential fuzzing of the HIP path against the CPU oracle: random regions, motifs, flank
 lengths, windows, scoring parameters, N bases and adversarial reads (missing flanks, junction
-indels, junk).  Usage: python tools/gpu_fuzz.py [n_rounds] [seed]"""
+indels, junk); alignment paths (CIGAR) also against the independent check of tests/path_check.py.
+Usage: python tools/gpu_fuzz.py [n_rounds] [seed]"""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, '.')
+sys.path.insert(1, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests'))      # path_check.py (fuzz_cigar)
 from nanorepeat_amd import _capi as A, synth
 from oracle import oracle as O
 
@@ -167,6 +169,61 @@ def fuzz_pairs(rng):
     return None
 
 
+CIGAR_FIELDS = ("score", "cigar", "tstart", "tend", "qstart", "qend")
+TRACE_BLOCK_ROWS = (64, 128, 192, 256, 384, 512, 768, 1024, 1536)      # the heights k_trace_fill_mt is built for
+
+
+def fuzz_cigar(rng):
+    """nra_align_pairs_cigar and nra_align_paths (also in row blocks of a random built height) on 1 - 6 repeat-shaped or
+    random pairs, queries up to 700 bases and targets up to 900, N and lower case, an empty sequence now and then: all six
+    fields against the oracle's traceback, and the device's record through the independent path check."""
+    from path_check import PathError, check_path
+    seqs, pq, pt = [], [], []
+    for i in range(int(rng.integers(1, 7))):
+        if rng.random() < 0.6:
+            unit = synth.rand_unit(rng, int(rng.integers(1, 7)))
+            L, R = synth.rand_seq(rng, int(rng.integers(5, 200))), synth.rand_seq(rng, int(rng.integers(5, 200)))
+            room = (900 - len(L) - len(R)) // len(unit)
+            k, kq = int(rng.integers(0, min(room, 80) + 1)), int(rng.integers(0, min(room, 80) + 1))
+            t = L + unit * k + R
+            q = L[len(L) - int(rng.integers(0, min(len(L), 100) + 1)):] + unit * kq + R[:int(rng.integers(0, min(len(R), 100) + 1))]
+        else:
+            t = synth.rand_seq(rng, int(rng.choice([1, 30, 63, 64, 65, 300, 900])))
+            a = int(rng.integers(0, len(t)))
+            q = t[a:a + int(rng.choice([1, 25, 64, 65, 300, 700]))] if rng.random() < 0.8 else synth.rand_seq(rng, int(rng.integers(1, 700)))
+        q = synth.apply_errors(rng, q, [(0, 0, 0), "hifi", "ont"][int(rng.integers(0, 3))])[:700]
+        if rng.random() < 0.05: q = ""
+        if rng.random() < 0.05: t = ""
+        seqs += [mangle(rng, t), mangle(rng, q)]
+        pq.append(2 * i + 1); pt.append(2 * i)
+    sc = rand_scoring(rng)
+    lo = max(1, sc.get("min_dp_score", 80))
+    osc, gsc = O.default_scoring(**sc), A.default_scoring(**sc)
+    want = [O.align_cigar(seqs[a], seqs[b], sc=osc) if seqs[a] and seqs[b] else dict(score=0) for a, b in zip(pq, pt)]
+    rows = int(rng.choice(TRACE_BLOCK_ROWS))
+    for entry, env in (("pairs_cigar", None), ("paths", None), ("paths", str(rows))):
+        try:
+            if env is not None: os.environ["NRA_TEST_TRACE_BLOCK_ROWS"] = env
+            g = (A.align_pairs_cigar if entry == "pairs_cigar" else A.align_paths)(seqs, pq, pt, sc=gsc)
+        finally:
+            os.environ.pop("NRA_TEST_TRACE_BLOCK_ROWS", None)
+        for i, o in enumerate(want):
+            got = dict(score=int(g["score"][i]), cigar=g["cigar"][i], **{k: int(g[k][i]) for k in CIGAR_FIELDS[2:]})
+            report = dict(kind="cigar", entry=entry, block_rows=env, pair=i, q=seqs[pq[i]], t=seqs[pt[i]], sc=sc)
+            if o["score"] < lo:                                          # no record: score -1, empty CIGAR
+                if (got["score"], got["cigar"]) != (-1, ""):
+                    return dict(report, key="record below the threshold", got=[got[k] for k in CIGAR_FIELDS], want=[-1, ""])
+                continue
+            for k in CIGAR_FIELDS:
+                if got[k] != o[k]:
+                    return dict(report, key=k, got=[got[k] for k in CIGAR_FIELDS], want=[o[k] for k in CIGAR_FIELDS])
+            try:
+                check_path(seqs[pq[i]], seqs[pt[i]], got, osc, optimum=o["score"])
+            except PathError as e:
+                return dict(report, key="path check: " + str(e), got=[got[k] for k in CIGAR_FIELDS], want=[o[k] for k in CIGAR_FIELDS])
+    return None
+
+
 def fuzz_2d(rng):
     u1 = synth.rand_unit(rng, int(rng.integers(1, 6))); u2 = synth.rand_unit(rng, int(rng.integers(1, 6)))
     # (flanks of 74 bases and more: their first |flank| - 10 >= 64 columns are swept in packed cells)
@@ -300,7 +357,7 @@ if __name__ == "__main__":
         hist_c[relax_c] = hist_c.get(relax_c, 0) + 1
         if relax_c is None: os.environ.pop("NRA_RELAX_C", None)
         else: os.environ["NRA_RELAX_C"] = relax_c
-        for f in (fuzz_1d, fuzz_1d_multi, fuzz_1d_blocks, fuzz_2d, fuzz_2d_grid, fuzz_pairs):
+        for f in (fuzz_1d, fuzz_1d_multi, fuzz_1d_blocks, fuzz_2d, fuzz_2d_grid, fuzz_pairs, fuzz_cigar):
             r = f(rng)
             if r is not None:
                 bad += 1
