@@ -364,6 +364,14 @@ int  nra_batch1d_saturation(nra_batch_t* b, int64_t* sweeps, int64_t* steps, int
  * measurements).  *scores: cand_score and the flank verdicts -- 0 where every bucket's forward sweeps write them for every
  * candidate; *extents: cand_tstart / cand_tend -- 0 where the selection kernel sets them to -1 on its way */
 int  nra_batch1d_clears(nra_batch_t* b, int32_t* scores, int32_t* extents);
+/* 1D: the plan nra_batch1d_create would make for these inputs on a device of `simds` SIMDs (1024 on MI355X), as text, on
+ * the host (no device needed; additive, ABI 4; for tests and measurements).  One `key value` per line: the plan's scalars,
+ * one line per bucket, and for every array its length and a 64-bit FNV-1a hash over its values.  Writes at most cap bytes
+ * (0-terminated) to buf and returns the bytes the whole text needs, or a negative NRA_E_* like the create call. */
+int64_t nra_plan1d_digest(const nra_region_t* regions, int32_t n_regions,
+                          int32_t n_reads, const char* seqs, const int64_t* seq_off,
+                          const int32_t* read_region, const int32_t* kmin, const int32_t* kmax,
+                          const nra_scoring_t* sc, int32_t flags, int32_t simds, char* buf, int64_t cap);
 int  nra_batch2d_fetch(nra_batch_t* b, int8_t* read_strand,
                        int32_t* cell_score, int32_t* cell_wscore,
                        int32_t* best_wscore, int64_t* sum_k1, int64_t* sum_k2,

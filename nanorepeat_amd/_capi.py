@@ -35,7 +35,7 @@ F_FULL_ANCHORS = 8192  # testing / comparison, 1D: the exact cell over every anc
 EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count",
            "nra_default_scoring", "nra_release_cached_memory", "nra_round3_1d", "nra_joint_2d", "nra_align_pairs", "nra_align_pairs_cigar", "nra_align_paths", "nra_batch1d_create",
            "nra_batch2d_create", "nra_batch2d_create_reads", "nra_batch2d_set_cells", "nra_joint_grid_cells", "nra_batch2d_set_grid", "nra_batch2d_invalidate", "nra_batch2d_sweep_flanks", "nra_batch2d_refine", "nra_batch_run", "nra_batch_sync", "nra_batch_stats",
-           "nra_batch1d_fetch", "nra_batch1d_resweeps", "nra_batch1d_saturation", "nra_batch1d_clears", "nra_batch2d_fetch", "nra_batch_destroy",
+           "nra_batch1d_fetch", "nra_batch1d_resweeps", "nra_batch1d_saturation", "nra_batch1d_clears", "nra_plan1d_digest", "nra_batch2d_fetch", "nra_batch_destroy",
            "nra_screen_create", "nra_screen_reads", "nra_screen_stats", "nra_screen_destroy",
            "nra_screen_set_motifs", "nra_screen_reads_partial",
            "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts", "nra_mixture_fit", "nra_mixture_bootstrap",
@@ -170,6 +170,8 @@ def load():
     lib.nra_batch1d_saturation.argtypes = [vp, pi64, pi64, pi64, pi64]
     lib.nra_batch1d_clears.restype = C.c_int
     lib.nra_batch1d_clears.argtypes = [vp, pi32, pi32]
+    lib.nra_plan1d_digest.restype = C.c_int64
+    lib.nra_plan1d_digest.argtypes = lib.nra_batch1d_create.argtypes[1:-1] + [C.c_int32, C.c_char_p, C.c_int64]
     lib.nra_batch1d_fetch.argtypes = [vp, pi32, pi64, pi32, p8, pi32, pi32, pi32]
     lib.nra_batch2d_fetch.restype = C.c_int
     lib.nra_batch2d_fetch.argtypes = [vp, pi8, pi32, pi32, pi32, pi64, pi64, pi32, p8]
@@ -326,6 +328,25 @@ def round3_1d(regions, reads, kmin, kmax, read_region=None, sc=None, flags=0, de
                              _ptr(out["cand_tstart"], C.c_int32) if pc else None,
                              _ptr(out["cand_tend"], C.c_int32) if pc else None))
     return out
+
+
+def plan1d_digest(regions, reads, kmin, kmax, read_region=None, sc=None, flags=0, simds=1024):
+    """nra_plan1d_digest: the plan nra_batch1d_create would make on a device of `simds` SIMDs, as text (no device needed)."""
+    lib = load()
+    sc = sc or default_scoring()
+    seqs, off = pack_reads(reads)
+    kmin = np.ascontiguousarray(kmin, np.int32)
+    kmax = np.ascontiguousarray(kmax, np.int32)
+    rr = None if read_region is None else np.ascontiguousarray(read_region, np.int32)
+    regs, keep = _regions(regions)
+    args = (regs, len(regions), len(reads), seqs, _ptr(off, C.c_int64), _ptr(rr, C.c_int32),
+            _ptr(kmin, C.c_int32), _ptr(kmax, C.c_int32), C.byref(sc), flags, simds)
+    need = lib.nra_plan1d_digest(*args, None, 0)
+    if need < 0:
+        _check(int(need))
+    buf = C.create_string_buffer(int(need))
+    _check(min(0, int(lib.nra_plan1d_digest(*args, buf, need))))
+    return buf.value.decode()
 
 
 def prepared_round3_1d(regions, reads, kmin, kmax, read_region=None, sc=None, flags=0, device=0):

@@ -32,7 +32,7 @@ KERNELS = (("nra_kernels.hip", (1, 2, 3, 4)),
            ("nra_bootstrap.hip", (37,)),
            ("nra_flank.hip", (38,)),
            ("nra_censored.hip", (39,)))
-HOSTS = ("nra_host.cpp", "nra_screen_host.cpp", "nra_structure_host.cpp", "nra_motif_host.cpp", "nra_extend_host.cpp",
+HOSTS = ("nra_host.cpp", "nra_plan1d.cpp", "nra_screen_host.cpp", "nra_structure_host.cpp", "nra_motif_host.cpp", "nra_extend_host.cpp",
          "nra_mixture_host.cpp", "nra_consensus_host.cpp", "nra_split_host.cpp", "nra_segment_host.cpp",
          "nra_period_host.cpp", "nra_bootstrap_host.cpp", "nra_flank_host.cpp", "nra_censored_host.cpp")
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))

@@ -7,6 +7,7 @@
 // No CPU fallback exists: without a HIP device every compute entry point fails.
 #include "nanorepeat_amd.h"
 #include "nra_internal.h"
+#include "nra_plan1d.h"
 
 #include <algorithm>
 #include <atomic>
@@ -60,32 +61,6 @@ static const bool g_debug_phases = g_debug || getenv("NRA_DEBUG_PHASES") != null
         }                                                                                        \
     } while (0)
 
-// NRA_DEBUG: wall time of the host phases of a create call
-struct PhaseClock {
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    void mark(const char* what)
-    {
-        if (!g_debug_phases) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[nra]   %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
-        t = now;
-    }
-};
-
-const int kRList[] = {
-#define X(r) r,
-    NRA_R_LIST(X)
-#undef X
-};
-const int kNumR = (int)(sizeof(kRList) / sizeof(kRList[0]));
-
-int rows_for_qlen(int qlen)   // index into kRList, -1 if too long
-{
-    for (int i = 0; i < kNumR; ++i)
-        if (64 * kRList[i] >= qlen) return i;
-    return -1;
-}
-
 // ASCII -> code table for the bulk encoder (same mapping as encode_base)
 struct BaseCodeTable {
     uint8_t v[256];
@@ -98,17 +73,6 @@ struct BaseCodeTable {
     uint8_t operator[](uint8_t c) const { return v[c]; }
 };
 static const BaseCodeTable kBaseCode;
-
-inline uint8_t encode_base(char c)
-{
-    switch (c) {
-    case 'A': case 'a': return 0;
-    case 'C': case 'c': return 1;
-    case 'G': case 'g': return 2;
-    case 'T': case 't': case 'U': case 'u': return 3;
-    default: return NRA_CODE_N;
-    }
-}
 
 // Device memory of one call or batch: hipMalloc costs ~0.3 ms per call, a batch has ~25 buffers, so
 // they are carved out of a few large chunks.  While an Arena is "current" on this thread, DevBuf
@@ -397,43 +361,6 @@ struct JointGroup {
     size_t pre_off = 0, tail_off = 0;
 };
 
-struct Bucket {
-    int R = 0;
-    bool chain = false;        // reads longer than one register block: chained row blocks
-    bool wide = false;         // chained: int32 cells, one read per wave (else packed int16, two reads per wave)
-    bool half = false;         // k_sweep_ring32: two read pairs per wave, 32 lanes each (R = rows per lane of a half; a ring bucket)
-    int payload_R = 0;         // chained: row block of the extents kernel (NRA_CHAIN_R / NRA_CHAIN_R_TEST)
-    size_t strip_off = 0;      // chained: this bucket's scratch strips in chain_sweep (int32 index)
-    int n_strips = 0;
-    bool mt = false;           // chained LDS-ring sweeps with the row blocks of a read as concurrent waves (k_sweep_ringmt)
-    std::vector<std::pair<size_t, int>> mt_groups;   // launches: (first entry of chain_blocks, number of blocks)
-    int n_pair = 0;            // pk16 tasks (1D score / 2D strand probe)
-    size_t pair_off = 0;       // offset into pair_tasks
-    int n_queue = 0;           // payload tasks prebuilt on the host (ALL_EXTENTS / 2D cells)
-    size_t queue_off = 0;      // offset into queue_tasks (also the base of the tie queue)
-    size_t queue_cap = 0;      // capacity of this bucket's queue region
-    int n_sweep = 0;           // junction-decomposition tasks (pairs of reads)
-    size_t sweep_off = 0;
-    bool ring = false;         // k_sweep_ring (LDS hand-off) instead of k_sweep_pk16 (DPP hand-off)
-    bool quanta = false;       // ... and its reverse and forward sweeps as ONE launch of quanta taken by ticket (k_sweep_ringq)
-    bool taint = false;        // ... with the relaxed cell over the anchor columns far from the junction, and the exact re-sweep
-                               // of the tasks it flags
-    int64_t q_fwd_steps = 0;   // ... the steps of its forward sweeps (nra_batch1d_saturation)
-    size_t q_off = 0, q_task_off = 0, q_state_off = 0;      // into q_list, q_words' arrivals (2 a task), q_state (int32, 2 slots a task)
-    int n_quanta = 0, q_steps = 0;                            // entries of q_list; steps of a part
-    int n_jbwd = 0;            // 2D decomposition: reverse sweeps (one per read)
-    size_t jbwd_off = 0;
-    int n_jlpk = 0, n_jrpk = 0;    // ... packed sweeps of the payload-free columns of L / rev(R) (one per pair of reads)
-    size_t jlpk_off = 0, jrpk_off = 0;
-    int n_comb = 0;            // 2D, junction at the end of mid: combine tasks (one per read)
-    size_t comb_off = 0;
-    int n_probe = 0;           // 2D, chained reads: strand-probe payload tasks (two per read)
-    size_t probe_off = 0;
-    int64_t cells_pair = 0;    // executed cells per run, pk16
-    int64_t cells_queue = 0;   // executed cells per run, prebuilt payload queue
-    int64_t cells_sweep = 0;   // executed cells per run, both sweeps
-};
-
 NraScoreParams to_params(const nra_scoring_t& sc)
 {
     NraScoreParams p;
@@ -452,28 +379,6 @@ bool scoring_ok(const nra_scoring_t* sc)
     if (sc->gap_open1 + sc->gap_ext1 > 1024 || sc->gap_open2 + sc->gap_ext2 > 1024) return false;
     if (sc->sc_ambi < 0 || sc->sc_ambi > 64) return false;
     return true;
-}
-
-// Largest alignment score a read of qlen bases can reach, against what a cell format holds:
-// int32 cells keep the score in their upper 16 bits; the packed int16 kernels keep value + 8192
-// (brute force), two biased values added (chained sweep: 2 x 8192 + score), or the same with
-// doubled scores (origin-bit sweep).
-const int64_t kScoreCapI32 = 32000, kScoreCapPk16 = 24000, kScoreCapBit = 13500;
-inline int64_t max_score(const nra_scoring_t* sc, int64_t qlen) { return (int64_t)sc->match * qlen; }
-
-// A rows-per-lane bucket with few reads would run as its own under-filled launches: fold it into the
-// next non-empty instantiation within `span` more rows per lane (the extra rows are padding).
-void fold_small_buckets(std::vector<std::vector<int32_t>>& by_bucket, size_t min_reads, int span)
-{
-    for (int bi = 0; bi + 1 < kNumR; ++bi) {
-        if (by_bucket[bi].empty() || by_bucket[bi].size() >= min_reads) continue;
-        int up = -1;
-        for (int bj = bi + 1; bj < kNumR && kRList[bj] <= kRList[bi] + span; ++bj)
-            if (!by_bucket[bj].empty()) { up = bj; break; }
-        if (up < 0) continue;
-        by_bucket[up].insert(by_bucket[up].end(), by_bucket[bi].begin(), by_bucket[bi].end());
-        by_bucket[bi].clear();
-    }
 }
 
 // SIMDs of a device (4 per compute unit; 1024 on MI355X)
@@ -501,22 +406,8 @@ uint32_t next_epoch()
     return e;
 }
 
-// Scratch strips of a chained launch: one per wave, `bytes_per_strip` each (a few values per template column).  As
-// many as there are tasks, at most `most`, and no more than fit the budget: a very wide template (up to
-// NRA_MAX_TLEN_WIDE columns: 160 - 190 MB per strip) gets fewer waves, never none.
-int chain_strips(size_t n_tasks, int most, size_t bytes_per_strip, size_t budget = NRA_CHAIN_SCRATCH_BUDGET)
-{
-    const size_t fit = std::max<size_t>(1, budget / std::max<size_t>(bytes_per_strip, 1));
-    return (int)std::max<size_t>(1, std::min(std::min<size_t>(n_tasks, (size_t)most), fit));
-}
-
-// executed cells of one wave sweep with 64 cells in flight (k_score_pk16, payload, joint kernels):
-// 64*R rows x (ceil((tlen+63)/64)*64) columns
-int64_t sweep_cells(int R, int tlen) { return (int64_t)64 * R * (((int64_t)tlen + 126) / 64 * 64); }
 // k_joint_sweep (reverse and tail sweeps): the step loop stops when the lane of the read's last row has taken the last column
 int64_t joint_cells(int R, int ncols, int qlen) { return (int64_t)64 * R * ((int64_t)ncols + std::min(63, std::max(qlen - 1, 0) / R)); }
-// k_sweep_pk16: two virtual cells per lane, 128 in flight, the step loop stops with the last column
-int64_t sweep128_cells(int R, int ncols) { return (int64_t)64 * R * ((int64_t)ncols + 127); }
 
 }  // namespace
 
@@ -891,16 +782,6 @@ int pack_reads(int32_t n_reads, const char* seqs, const int64_t* seq_off, const 
     return NRA_OK;
 }
 
-uint32_t pool_append(std::vector<uint8_t>& pool, const char* s, int32_t len, const char* unit,
-                     int32_t ulen, int32_t reps, bool& has_n)
-{
-    uint32_t off = (uint32_t)pool.size();
-    for (int32_t i = 0; i < len; ++i) { uint8_t c = encode_base(s[i]); has_n |= c >= 4; pool.push_back(c); }
-    for (int32_t k = 0; k < reps; ++k)
-        for (int32_t i = 0; i < ulen; ++i) { uint8_t c = encode_base(unit[i]); has_n |= c >= 4; pool.push_back(c); }
-    return off;
-}
-
 int common_init(nra_batch* b, int device, const nra_scoring_t* sc, int flags)
 {
     int ndev = 0;
@@ -961,6 +842,125 @@ int make_events(nra_batch* b, int n)
     return NRA_OK;
 }
 
+// ---- 1D: around the plan (nra_plan1d.h) -----------------------------------------------
+int check_batch1d_args(const nra_region_t* regions, int32_t n_regions, int32_t n_reads, const char* seqs,
+                       const int64_t* seq_off, const int32_t* read_region, const int32_t* kmin, const int32_t* kmax,
+                       const nra_scoring_t* sc)
+{
+    if (!regions || n_regions <= 0 || n_reads < 0) return fail(NRA_E_ARG, "bad region / read count");
+    if (n_reads > 0 && (!seqs || !seq_off || !kmin || !kmax)) return fail(NRA_E_ARG, "NULL input array");
+    if (n_regions > 1 && n_reads > 0 && !read_region) return fail(NRA_E_ARG, "read_region required when n_regions > 1");
+    if (!scoring_ok(sc)) return fail(NRA_E_ARG, "scoring parameters out of range");
+    for (int32_t g = 0; g < n_regions; ++g) {
+        const nra_region_t& rg = regions[g];
+        if (rg.left_len < 0 || rg.right_len < 0 || rg.unit_len <= 0 || !rg.unit ||
+            (rg.left_len > 0 && !rg.left) || (rg.right_len > 0 && !rg.right))
+            return fail(NRA_E_ARG, "bad region " + std::to_string(g));
+    }
+    return NRA_OK;
+}
+
+// the environment knobs of a 1D plan, as they stand at this call (the plan itself reads no environment)
+Plan1DKnobs plan1d_knobs()
+{
+    Plan1DKnobs k;
+    auto knob = [](const char* name, bool& has, int& value) {
+        if (const char* e = getenv(name)) { has = true; value = atoi(e); }
+    };
+    knob("NRA_RELAX_C", k.has_relax_c, k.relax_c);
+    knob("NRA_CHAIN_FROM", k.has_chain_from, k.chain_from);
+    knob("NRA_TEST_QSTEPS", k.has_qsteps, k.qsteps);
+    knob("NRA_TEST_SAT", k.has_sat, k.sat);
+    knob("NRA_TEST_SAT_STEPS", k.has_sat_steps, k.sat_steps);
+    return k;
+}
+
+// The device side of a 1D plan: the batch's buffers out of one arena chunk and their uploads, enqueued and waited for
+// once.  The order of the allocations is part of the contract: device addresses and the one-chunk sizing follow it.
+int upload_plan_1d(nra_batch* b, const Plan1D& plan, const PackedReads& pr, const int32_t* kmin, const int32_t* kmax)
+{
+    const int32_t n_reads = b->n_reads;
+    const int64_t total = plan.n_cands;
+    const bool brute = plan.brute, all_ext = (b->flags & NRA_F_ALL_EXTENTS) != 0;
+    const size_t nb = b->buckets.size();
+    // one chunk for everything: ~7 B per read base, ~40 B per candidate, the tasks, the chain strips
+    b->arena.expect(pr.q2bit.size() * 16 * 2 + (size_t)plan.snap_total * 4 + (size_t)total * 40 + plan.pool.size() + plan.sweep_tasks.size() * sizeof(NraSweepTask) +
+                    plan.pair_tasks.size() * sizeof(NraPairTask) + (size_t)n_reads * 64 + (4u << 20));
+    // (the chain strips get chunks of their own: they can be GBs)
+    UploadBatchScope uploads;            // every upload below is enqueued; one wait behind the last of them
+    HIP_TRY(b->pool.upload(plan.pool));
+    HIP_TRY(b->q2bit.upload(pr.q2bit));
+    HIP_TRY(b->qnmask.upload(pr.nmask));
+    HIP_TRY(b->regions.upload(plan.dregs));
+    HIP_TRY(b->reads.upload(pr.reads));
+    HIP_TRY(b->pair_tasks.upload(plan.pair_tasks));
+    HIP_TRY(b->sweep_tasks.upload(plan.sweep_tasks));
+    if (!brute) {
+        HIP_TRY(b->snap.alloc((size_t)plan.snap_total));
+        HIP_TRY(b->read_a1d.alloc((size_t)n_reads));
+        bool any_taint = false;
+        for (const Bucket& bk : b->buckets) any_taint = any_taint || bk.taint;
+        if (any_taint) b->redo.n = std::max<size_t>(plan.sweep_tasks.size(), 1);        // (a view into run_words, below)
+        if (!plan.qlist.empty()) {
+            HIP_TRY(b->q_list.upload(plan.qlist));
+            b->q_arrivals_off = (1 + b->buckets.size() + 3) / 4 * 4;
+            b->q_words_n = b->q_arrivals_off + plan.q_tasks;            // (a view into run_words, below)
+            HIP_TRY(b->q_state.alloc(plan.q_state));
+        }
+    }
+    HIP_TRY(b->cand_flag.alloc((size_t)total));
+    if (!plan.chain_blocks.empty()) {
+        HIP_TRY(b->chain_blocks.upload(plan.chain_blocks));
+        const size_t granules = std::max<size_t>(plan.mt_strip_total, 1) * 5 * (size_t)b->chain_cap;
+        HIP_TRY(b->mt_strips.alloc(granules));
+        // (on the batch's own stream: the bucket streams are ordered behind it by fork_ev; a null-stream memset is not
+        // ordered with these non-blocking streams at all)
+        HIP_TRY(hipMemsetAsync(b->mt_strips.p, 0, granules * 8, b->stream));       // no granule carries an epoch yet (epochs are never 0)
+        HIP_TRY(b->mt_words.alloc(2 + b->buckets.size()));
+        HIP_TRY(hipMemsetAsync(b->mt_words.p, 0, (2 + b->buckets.size()) * 4, b->stream));
+        HIP_TRY(hipStreamSynchronize(b->stream));
+    }
+    if (plan.strip_total || !plan.chain_blocks.empty()) {
+        if (plan.strip_total) HIP_TRY(b->chain_sweep.alloc(plan.strip_total));
+        // the chained buckets' extents launches run in turn and share these strips (int64 cells)
+        b->payload_strips = chain_strips(plan.chain_queue_cap, NRA_CHAIN_STRIPS, (size_t)6 * 8 * (size_t)b->chain_cap);
+        HIP_TRY(b->chain_payload.alloc((size_t)b->payload_strips * 6 * (size_t)b->chain_cap));
+    }
+    if (all_ext) HIP_TRY(b->queue_tasks.upload(plan.queue_tasks));
+    else HIP_TRY(b->queue_tasks.alloc(plan.queue_total));
+    HIP_TRY(b->queue_count.upload(plan.queue_count));
+    {
+        // the words of a run: [q_words | the row blocks' give-up word | tie_count | sat_count | redo], zero before any run too
+        // (so that nra_batch1d_resweeps and nra_batch1d_saturation read nothing of a run that has not happened)
+        const size_t n_redo = b->redo.n, n_words = b->q_words_n + 1 + 5 * std::max<size_t>(nb, 1) + 1 + n_redo;
+        HIP_TRY(b->run_words.alloc(n_words));
+        int32_t* w = b->run_words.p;
+        auto view = [&](DevBuf<int32_t>& buf, size_t n) { buf.p = w; buf.n = n; buf.owned = false; w += n; };
+        view(b->q_words, b->q_words_n);
+        b->mt_giveup = w++;
+        view(b->tie_count, std::max<size_t>(nb, 1));
+        if (reinterpret_cast<uintptr_t>(w) & 7) ++w;                     // (the 64-bit step counts of sat_count: 8-byte aligned)
+        view(b->sat_count, 4 * std::max<size_t>(nb, 1));
+        view(b->redo, n_redo);
+        HIP_TRY(hipMemsetAsync(b->run_words.p, 0, n_words * 4, b->stream));
+        HIP_TRY(hipStreamSynchronize(b->stream));
+    }
+    HIP_TRY(b->bucket_task_base.upload(plan.task_base));
+    {
+        std::vector<int32_t> v(kmin, kmin + n_reads); HIP_TRY(b->kmin.upload(v));
+        std::vector<int32_t> w(kmax, kmax + n_reads); HIP_TRY(b->kmax.upload(w));
+    }
+    HIP_TRY(b->read_bucket.upload(plan.read_bucket));
+    HIP_TRY(b->coff.upload(plan.coff));
+    HIP_TRY(b->cand_score.alloc((size_t)total));
+    HIP_TRY(b->cand_tstart.alloc((size_t)total));
+    HIP_TRY(b->cand_tend.alloc((size_t)total));
+    const int rc = alloc_results(b, (size_t)n_reads, false);
+    if (rc) return rc;
+    HIP_TRY(upload_batch_end());
+    return NRA_OK;
+}
+
 }  // namespace
 
 // =====================================================================================
@@ -1013,25 +1013,17 @@ int nra_batch1d_create(int device, const nra_region_t* regions, int32_t n_region
 {
     if (!out) return fail(NRA_E_ARG, "out is NULL");
     *out = nullptr;
-    if (!regions || n_regions <= 0 || n_reads < 0) return fail(NRA_E_ARG, "bad region / read count");
-    if (n_reads > 0 && (!seqs || !seq_off || !kmin || !kmax)) return fail(NRA_E_ARG, "NULL input array");
-    if (n_regions > 1 && n_reads > 0 && !read_region) return fail(NRA_E_ARG, "read_region required when n_regions > 1");
-    if (!scoring_ok(sc)) return fail(NRA_E_ARG, "scoring parameters out of range");
-    for (int32_t g = 0; g < n_regions; ++g) {
-        const nra_region_t& rg = regions[g];
-        if (rg.left_len < 0 || rg.right_len < 0 || rg.unit_len <= 0 || !rg.unit ||
-            (rg.left_len > 0 && !rg.left) || (rg.right_len > 0 && !rg.right))
-            return fail(NRA_E_ARG, "bad region " + std::to_string(g));
-    }
+    int rc = check_batch1d_args(regions, n_regions, n_reads, seqs, seq_off, read_region, kmin, kmax, sc);
+    if (rc) return rc;
 
     nra_batch* b = new nra_batch();
     std::unique_ptr<nra_batch> guard(b);
     ArenaScope arena_scope(&b->arena);
     b->kind = 1; b->n_reads = n_reads; b->n_regions = n_regions;
-    int rc = common_init(b, device, sc, flags);
+    rc = common_init(b, device, sc, flags);
     if (rc) return rc;
 
-    PhaseClock clk;
+    PhaseClock clk(g_debug_phases);
     clk.mark("device, stream");
     // the workers pack the reads while this thread builds templates, buckets and tasks from the layout
     PackedReads pr;
@@ -1040,570 +1032,30 @@ int nra_batch1d_create(int device, const nra_region_t* regions, int32_t n_region
     PackJob packing(n_reads, seqs, seq_off, pr);
     clk.mark("read layout, packing started");
 
-    // per-region largest k, candidate offsets
-    std::vector<int32_t> region_kmax((size_t)n_regions, 0);
-    std::vector<uint32_t> coff((size_t)n_reads + 1, 0);
-    std::vector<int32_t> read_bucket((size_t)n_reads, -1);
-    int64_t total = 0;
-    for (int32_t r = 0; r < n_reads; ++r) {
-        coff[r] = (uint32_t)total;
-        if (kmin[r] > kmax[r]) continue;
-        if (kmin[r] < 0) return fail(NRA_E_ARG, "kmin < 0");
-        const int g = pr.reads[r].region;
-        const int64_t tl = (int64_t)regions[g].left_len + (int64_t)regions[g].unit_len * kmax[r] + regions[g].right_len;
-        if (tl > NRA_MAX_TLEN_WIDE) return fail(NRA_E_RANGE, "template longer than " + std::to_string(NRA_MAX_TLEN_WIDE));
-        region_kmax[g] = std::max(region_kmax[g], kmax[r]);
-        total += (int64_t)kmax[r] - kmin[r] + 1;
-        if (total > 0x7ff00000ll) return fail(NRA_E_RANGE, "more than 2^31 candidates in one batch");
-    }
-    coff[n_reads] = (uint32_t)total;
-    b->n_cands = total;
-
-    // code pool + region table
-    std::vector<uint8_t> pool;
-    std::vector<NraDevRegion> dregs((size_t)n_regions);
-    bool has_n = false;                          // templates; the reads' share is known when the packing is over
-    for (int32_t g = 0; g < n_regions; ++g) {
-        const nra_region_t& rg = regions[g];
-        NraDevRegion d{};
-        d.p1_off = pool_append(pool, rg.left, rg.left_len, rg.unit, rg.unit_len, region_kmax[g], has_n);
-        d.p2_off = (uint32_t)pool.size();
-        d.p3_off = pool_append(pool, rg.right, rg.right_len, nullptr, 0, 0, has_n);
-        {   // rev(R) + rev(unit)^kmax for the reverse sweep
-            std::string rr(rg.right, rg.right + rg.right_len), ru(rg.unit, rg.unit + rg.unit_len);
-            std::reverse(rr.begin(), rr.end());
-            std::reverse(ru.begin(), ru.end());
-            d.pr_off = pool_append(pool, rr.data(), rg.right_len, ru.data(), rg.unit_len, region_kmax[g], has_n);
-        }
-        d.l1 = rg.left_len; d.m1 = rg.unit_len; d.l2 = 0; d.m2 = 0; d.l3 = rg.right_len;
-        dregs[g] = d;
-        if (pool.size() > 0xfff00000ull) return fail(NRA_E_RANGE, "template pool exceeds 4 GB");
-    }
-    pool.push_back(0);
-
-    // buckets by rows-per-lane; tasks
-    const bool all_ext = (flags & NRA_F_ALL_EXTENTS) != 0;
-    bool brute = all_ext || (flags & NRA_F_BRUTE_FORCE) != 0;
-    for (int32_t g = 0; g < n_regions; ++g)       // the junction needs a base on either side
-        if (regions[g].left_len < 1 || regions[g].right_len < 1) brute = true;
-    {   // the sweep kernels keep (substitution score + gap-open cost) in unsigned table bytes
-        // (doubled: the low bit of every state is the origin bit)
-        const int o1 = sc->gap_open1 + sc->gap_ext1;
-        if (o1 < sc->mismatch || o1 < sc->sc_ambi || 2 * (sc->match + o1) > 127) brute = true;
-        // and every state in [0x0400, 0x7bff] (nra_sweep.hip: bias 2048, "minus infinity" 1280)
-        const int o2 = sc->gap_open2 + sc->gap_ext2;
-        if (2 * sc->gap_ext1 > 256 || 2 * sc->gap_ext2 > 256 || 2 * (o2 + sc->mismatch + sc->sc_ambi) > 700) brute = true;
-        // The taint scheme quadruples the scores: the same bounds at 4x, and the relaxed cell opens its one
-        // gap state at o1 (= min(o1, o2): it shares the exact cell's substitution table).  Other schemes keep the doubled
-        // cells of every sweep.  NRA_RELAX_C (tests, measurements): the margin, in bases; 0 turns the scheme off.
-        b->relax_c = NRA_RELAX_C_DEFAULT;
-        if (const char* e = getenv("NRA_RELAX_C")) b->relax_c = std::max(0, atoi(e));
-        if (b->relax_c > 0) b->relax_c = std::max(b->relax_c, 64);
-        if ((flags & NRA_F_FULL_ANCHORS) || o1 > o2 || 4 * (sc->match + o1) > 127 || 4 * sc->gap_ext1 > 256 ||
-            4 * sc->gap_ext2 > 256 || 4 * (o2 + sc->mismatch + sc->sc_ambi) > 700)
-            b->relax_c = 0;
-    }
-    // Which reads leave the packed int16 sweeps for the chained int32 ones (one read per wave, any length):
-    // more rows than one register block, scores beyond the doubled int16 range, or a template whose
-    // extents do not fit the 16-bit payload of the int32 extents kernel.
-    const bool test_chain = (flags & NRA_F_TEST_CHAIN) != 0;
-    // reads of more rows than this leave the one-block kernels for the chained ones (NRA_CHAIN_FROM: experiments)
-    int chain_from = NRA_RING_MT_FROM;
-    if (const char* e = getenv("NRA_CHAIN_FROM")) chain_from = std::max(64, std::min(atoi(e), NRA_MAX_QLEN_1BLOCK));
-    const bool ring_units = [&] { for (int32_t g = 0; g < n_regions; ++g) if (regions[g].unit_len > NRA_SWEEP_RING_MAX_M) return false; return true; }();
-    if (!ring_units || brute || (flags & (NRA_F_DPP_SWEEP | NRA_F_SERIAL_CHAIN))) chain_from = NRA_MAX_QLEN_1BLOCK;
-    if (chain_from == NRA_RING_MT_FROM && !getenv("NRA_CHAIN_FROM")) {
-        // The reads of (NRA_RING_MT_FROM, 3072] rows can go either way: one register block of 28 - 48 rows per lane -- one
-        // wave per SIMD, padding in steps of 256 / 512 rows, 4.3 T cells/s x the fill of the launch's last round of the
-        // SIMDs -- or row blocks of 12 .. 15 rows per lane, three waves per SIMD: 3.7 - 4.0 T cells/s (4.1 - 4.4 with two
-        // blocks per read) once there are two rounds of them, 1.9 + 1.2 x rounds - 0.25 x (blocks per read - 2) below that
-        // (the blocks of a read lag one another).  The model is fitted to tools/gpu_block_rows.py: on 1000 - 10 000 reads
-        // of 1.6 - 3 kb it picks the faster form, or one within 3 %, in 54 of 54 cases
-        // (profiles/r03_row_blocks_or_one_block_54_cases.txt); such reads run up to 37 % faster as blocks, config 5
-        // 20.4 -> 17.3 ms.
-        int64_t n_class = 0, rows_single = 0, rows_blocks[NRA_RING_MT_R + 1] = {0}, rows_class[NRA_RING_MT_R + 1] = {0};
-        for (int32_t r = 0; r < n_reads; ++r) {
-            const int q = pr.reads[r].qlen;
-            if (kmin[r] > kmax[r] || q <= NRA_RING_MT_FROM || max_score(sc, q) > kScoreCapBit) continue;
-            for (int R = NRA_RING_MT_R_MIN; R <= NRA_RING_MT_R; ++R) {
-                const int64_t rows = ((int64_t)q + 64 * R - 1) / (64 * R) * (64 * R);
-                rows_blocks[R] += rows;
-                if (q <= NRA_MAX_QLEN_1BLOCK) rows_class[R] += rows;
-            }
-            if (q <= NRA_MAX_QLEN_1BLOCK) { ++n_class; rows_single += 64 * (int64_t)kRList[rows_for_qlen(q)]; }
-        }
-        if (n_class > 0) {
-            int R = NRA_RING_MT_R;
-            for (int r2 = NRA_RING_MT_R - 1; r2 >= NRA_RING_MT_R_MIN; --r2) if (rows_blocks[r2] < rows_blocks[R]) R = r2;
-            const double simds = (double)device_simds(b->device);
-            const double waves = (double)((n_class + 1) / 2), nblk = (double)rows_class[R] / (64.0 * R) / (double)n_class;
-            const double r1 = waves / simds, e1 = r1 / std::ceil(r1);
-            const double r2 = waves * nblk / (3.0 * simds);
-            const double t_single = (double)rows_single / (4.3 * e1);
-            const double cap = 3.7 + 0.1 * (R - NRA_RING_MT_R_MIN) + (nblk < 2.5 ? 0.4 : 0.0);
-            const double t_blocks = (double)rows_class[R] / std::min(cap, 1.9 + 1.2 * r2 - 0.25 * (nblk - 2.0));
-            if (t_single <= t_blocks) chain_from = NRA_MAX_QLEN_1BLOCK;
-        }
-    }
-    std::vector<uint8_t> chained((size_t)n_reads, 0);
-    for (int32_t r = 0; r < n_reads; ++r) {
-        if (kmin[r] > kmax[r]) continue;
-        const nra_region_t& rg = regions[pr.reads[r].region];
-        const int64_t ms = max_score(sc, pr.reads[r].qlen);
-        const int64_t tl = (int64_t)rg.left_len + (int64_t)rg.unit_len * kmax[r] + rg.right_len;
-        chained[r] = test_chain || pr.reads[r].qlen > chain_from || ms > kScoreCapBit || tl > NRA_MAX_TLEN;
-        if (brute && chained[r] && !test_chain) {
-            // without the sweeps (flank-less region, unusual scoring, brute force on request) only what the
-            // packed brute-force kernel holds can be scored
-            if (pr.reads[r].qlen > NRA_MAX_QLEN_1BLOCK || ms > kScoreCapPk16 || tl > NRA_MAX_TLEN)
-                return fail(NRA_E_RANGE, "read " + std::to_string(r) + " (" + std::to_string(pr.reads[r].qlen) +
-                                             " bases) needs the junction decomposition: no brute force / ALL_EXTENTS, "
-                                             "flanks >= 1, default-like scoring");
-            chained[r] = 0;
-        }
-    }
-    b->brute = brute;
-    clk.mark("  candidate offsets, templates, chained flags");
-    std::vector<NraSweepTask> sweep_tasks;
-    uint64_t snap_total = 0;
-    // the chained reads (every read with NRA_F_TEST_CHAIN): bucket kNumR = int32 cells, one read per wave;
-    // bucket kNumR + 1 = packed int16, two reads per wave -- doubled scores up to 27000 (reads of up to 6750
-    // bases with the default scoring) in the LDS-ring kernels, which hold units of up to NRA_SWEEP_RING_MAX_M
-    // buckets kNumR + 2 + i: half-wave sweeps (k_sweep_ring32), i = index of the half's rows per lane in kRList
-    std::vector<std::vector<int32_t>> by_bucket((size_t)2 * kNumR + 2);
-    const bool ring_ok = (flags & NRA_F_DPP_SWEEP) == 0 && !brute;
-    int chain_cols = 0;
-    for (int32_t r = 0; r < n_reads; ++r) {
-        if (kmin[r] > kmax[r] || pr.reads[r].qlen == 0) continue;
-        int bi = rows_for_qlen(pr.reads[r].qlen);
-        if (ring_ok && !chained[r] && pr.reads[r].qlen <= 32 * NRA_RING32_MAX_R &&
-            regions[pr.reads[r].region].unit_len <= NRA_SWEEP_RING_MAX_M && (flags & NRA_F_NO_HALF_WAVE) == 0)
-            bi = kNumR + 2 + rows_for_qlen(2 * pr.reads[r].qlen);        // 32 * R >= qlen
-        if (chained[r]) {
-            const nra_region_t& rg = regions[pr.reads[r].region];
-            const bool packed = max_score(sc, pr.reads[r].qlen) <= kScoreCapBit && rg.unit_len <= NRA_SWEEP_RING_MAX_M &&
-                                (flags & NRA_F_DPP_SWEEP) == 0;
-            bi = packed ? kNumR + 1 : kNumR;
-            chain_cols = std::max(chain_cols, rg.left_len + rg.unit_len * kmax[r] + rg.right_len);
-        }
-        read_bucket[r] = bi;
-        by_bucket[bi].push_back(r);
-    }
-    if ((!by_bucket[kNumR].empty() || !by_bucket[kNumR + 1].empty()) && brute)
-        return fail(NRA_E_RANGE, "NRA_F_TEST_CHAIN needs the junction decomposition (no brute force / ALL_EXTENTS, flanks >= 1)");
-    clk.mark("  reads to buckets");
-    {   // small buckets fold into the next instantiation of their own kind
-        std::vector<std::vector<int32_t>> full(by_bucket.begin(), by_bucket.begin() + kNumR);
-        std::vector<std::vector<int32_t>> halfb(by_bucket.begin() + kNumR + 2, by_bucket.end());
-        fold_small_buckets(full, 1024, 2);    // wider folding (up to 16384 reads / 4 rows) changes nothing in 1D
-        fold_small_buckets(halfb, 2048, 2);
-        for (int i = 0; i < kNumR; ++i) { by_bucket[i] = std::move(full[i]); by_bucket[kNumR + 2 + i] = std::move(halfb[i]); }
-    }
-    if (chain_from < NRA_MAX_QLEN_1BLOCK && !test_chain && !by_bucket[kNumR + 1].empty()) {
-        // ... and a handful of reads left in a one-block bucket above one row block (961 - 3072 bases, fewer than 256 of a
-        // kind: 128 waves) joins the row blocks, where there are any: a length distribution that straddles
-        // NRA_RING_MT_FROM would otherwise leave them a launch of their own (1000 reads of 1528 - 1582 bases, 24 of them
-        // below the line: 4.2 ms against 2.7).  Larger buckets stay: two blocks pad a 1000-base read by half.
-        for (int bi = 0; bi < kNumR; ++bi) {
-            if (kRList[bi] <= NRA_RING_MT_R || by_bucket[bi].empty() || by_bucket[bi].size() >= 256) continue;
-            for (int32_t r : by_bucket[bi]) {
-                const nra_region_t& rg = regions[pr.reads[r].region];
-                chain_cols = std::max(chain_cols, rg.left_len + rg.unit_len * kmax[r] + rg.right_len);
-                chained[r] = 1;
-                read_bucket[r] = kNumR + 1;
-                by_bucket[kNumR + 1].push_back(r);
-            }
-            by_bucket[bi].clear();
-        }
-    }
-    b->chain_cap = (chain_cols + 127) / 64 * 64 + 64;
-    clk.mark("  small buckets folded");
-    size_t strip_total = 0, chain_queue_cap = 0, mt_strip_total = 0;
-    std::vector<NraChainBlock> chain_blocks;
-    std::vector<NraPairTask> pair_tasks;
-    std::vector<NraTask> queue_tasks;       // ALL_EXTENTS only; otherwise just capacity
-    std::vector<int32_t> queue_count;
-    std::vector<uint32_t> task_base;
-    size_t queue_total = 0;
-    int64_t alg_cells = 0;
-    // longest reads first: int32 chain, packed chain, full-wave R = 48 ... 1, then the half-wave buckets 16 ... 1
-    std::vector<int> bucket_order{kNumR, kNumR + 1};
-    for (int i = kNumR - 1; i >= 0; --i) bucket_order.push_back(i);
-    for (int i = kNumR - 1; i >= 0; --i) bucket_order.push_back(kNumR + 2 + i);
-    for (const int bi : bucket_order) {
-        if (by_bucket[bi].empty()) continue;
-        Bucket bk;
-        bk.chain = bi == kNumR || bi == kNumR + 1;
-        bk.wide = bi == kNumR;
-        bk.half = bi >= kNumR + 2;
-        if (bk.chain) {
-            // LDS-ring chain unless a unit is too long for the ring (then the DPP chain, int32 only)
-            bk.ring = (flags & NRA_F_DPP_SWEEP) == 0;
-            for (int32_t r : by_bucket[bi])
-                if (regions[pr.reads[r].region].unit_len > NRA_SWEEP_RING_MAX_M) bk.ring = false;
-            bk.payload_R = test_chain ? NRA_CHAIN_R_TEST : NRA_CHAIN_R;
-            // the row blocks of a read as concurrent waves (k_sweep_ringmt), unless one read alone would need more
-            // strips than the scratch budget holds (then: one wave per read, block after block, two strips)
-            bk.mt = bk.ring && (flags & NRA_F_SERIAL_CHAIN) == 0;
-            if (bk.mt) {
-                const int rows = 64 * (test_chain ? NRA_CHAIN_R_TEST : NRA_RING_MT_R_MIN);      // (the shortest block there is)
-                int qmax = 0;
-                for (int32_t r : by_bucket[bi]) qmax = std::max(qmax, pr.reads[r].qlen);
-                const size_t fit = (size_t)(NRA_CHAIN_SCRATCH_BUDGET / 2) / ((size_t)5 * 8 * (size_t)b->chain_cap);
-                if ((size_t)((qmax + rows - 1) / rows) > fit + 1) bk.mt = false;
-            }
-            bk.R = test_chain ? NRA_CHAIN_R_TEST : (bk.mt ? NRA_RING_MT_R : bk.ring ? NRA_RING_CHAIN_R : NRA_CHAIN_R);
-            if (bk.mt && !test_chain && !bk.wide) {
-                // the block height that pads the bucket's reads least (ties: the taller block, fewer hand-offs; the int32
-                // blocks of the longest reads stay at 15: 7.7 kb cores 96 ms against 102 ms at 14 with 0.5 % fewer cells)
-                int64_t best = -1;
-                for (int R = NRA_RING_MT_R; R >= NRA_RING_MT_R_MIN; --R) {
-                    int64_t rows = 0;
-                    for (int32_t r : by_bucket[bi]) rows += ((int64_t)pr.reads[r].qlen + 64 * R - 1) / (64 * R) * (64 * R);
-                    if (best < 0 || rows < best) { best = rows; bk.R = R; }
-                }
-            }
-        } else {
-            bk.R = kRList[bk.half ? bi - kNumR - 2 : bi];
-        }
-        bk.pair_off = pair_tasks.size();
-        bk.queue_off = queue_total;
-        for (int32_t r : by_bucket[bi]) {
-            read_bucket[r] = (int32_t)b->buckets.size();
-            const NraDevRegion& d = dregs[pr.reads[r].region];
-            {   // algorithmic cells: q x sum over k of (|L| + m k + |R|)
-                const int64_t K = (int64_t)kmax[r] - kmin[r] + 1;
-                const int64_t sum_k = ((int64_t)kmin[r] + kmax[r]) * K / 2;
-                alg_cells += (int64_t)pr.reads[r].qlen * (K * ((int64_t)d.l1 + d.l3) + (int64_t)d.m1 * sum_k);
-            }
-            if (all_ext) {
-                for (int32_t k = kmin[r]; k <= kmax[r]; ++k) {
-                    queue_tasks.push_back(NraTask{r, k, 0, (int32_t)(coff[r] + (uint32_t)(k - kmin[r]))});
-                    bk.cells_queue += sweep_cells(bk.R, d.l1 + d.m1 * k + d.l3);
-                }
-            }
-            if (!all_ext && brute) {
-                for (int32_t k = kmin[r]; k <= kmax[r]; k += 2) {
-                    NraPairTask t{};
-                    t.read = r; t.k1a = k; t.k2a = 0; t.out_a = (int32_t)(coff[r] + (uint32_t)(k - kmin[r]));
-                    if (k + 1 <= kmax[r]) { t.k1b = k + 1; t.k2b = 0; t.out_b = t.out_a + 1; }
-                    else { t.k1b = k; t.k2b = 0; t.out_b = -1; }
-                    t.flags = 0;
-                    pair_tasks.push_back(t);
-                    const int tl = d.l1 + d.m1 * (t.out_b >= 0 ? k + 1 : k) + d.l3;
-                    bk.cells_pair += 2 * sweep_cells(bk.R, tl);
-                }
-            }
-            bk.queue_cap += (size_t)(kmax[r] - kmin[r] + 1);
-        }
-        if (!brute) {
-            // pair reads of one region by length: two reads share a wave (int16 halves)
-            std::vector<int32_t> order(by_bucket[bi]);
-            std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
-                if (pr.reads[x].region != pr.reads[y].region) return pr.reads[x].region < pr.reads[y].region;
-                return pr.reads[x].qlen > pr.reads[y].qlen;
-            });
-            bk.sweep_off = sweep_tasks.size();
-            // the LDS-ring sweeps hold unit lengths up to NRA_SWEEP_RING_MAX_M; a bucket with a longer unit
-            // keeps the DPP sweeps
-            if (!bk.chain) {
-                bk.ring = (flags & NRA_F_DPP_SWEEP) == 0;
-                for (int32_t r : order)
-                    if (dregs[pr.reads[r].region].m1 > NRA_SWEEP_RING_MAX_M) bk.ring = false;
-                // the taint scheme: quadrupled scores <= 27000 in the packed cells (nra_pk16.h)
-                bk.taint = bk.ring && b->relax_c > 0;
-                for (int32_t r : order)
-                    if (4 * max_score(sc, pr.reads[r].qlen) > 27000) bk.taint = false;
-            }
-            if (bk.half) {
-                // four reads of a region per wave: two pairs, one per half, the union of their windows
-                for (size_t i = 0; i < order.size();) {
-                    NraSweepTask t{};
-                    const int32_t g = pr.reads[order[i]].region;
-                    int32_t quad[4] = {-1, -1, -1, -1};
-                    int nq = 0;
-                    while (nq < 4 && i < order.size() && pr.reads[order[i]].region == g) quad[nq++] = order[i++];
-                    t.read_a = quad[0]; t.read_b = quad[1]; t.read_c = quad[2]; t.read_d = quad[3];
-                    t.kmin = kmin[quad[0]]; t.kmax = kmax[quad[0]];
-                    for (int j = 1; j < nq; ++j) { t.kmin = std::min(t.kmin, kmin[quad[j]]); t.kmax = std::max(t.kmax, kmax[quad[j]]); }
-                    const NraDevRegion& d = dregs[g];
-                    bk.cells_sweep += (int64_t)2 * 64 * bk.R * ((d.l1 + d.m1 * t.kmax + 31 * d.m1) + (d.l3 + 31));
-                    t.snap_off = snap_total;
-                    snap_total += (uint64_t)NRA_SNAP_LANE_STRIDE(bk.R) * 64;       // lane-major in the half-wave kernel
-                    sweep_tasks.push_back(t);
-                }
-            } else
-            for (size_t i = 0; i < order.size();) {
-                NraSweepTask t{};
-                t.read_a = order[i]; t.read_b = -1; t.read_c = -1; t.read_d = -1;
-                t.kmin = kmin[t.read_a]; t.kmax = kmax[t.read_a];
-                // (the int32 chained sweeps take one read per wave)
-                if (!bk.wide && i + 1 < order.size() && pr.reads[order[i + 1]].region == pr.reads[order[i]].region) {
-                    t.read_b = order[i + 1];
-                    t.kmin = std::min(t.kmin, kmin[t.read_b]);
-                    t.kmax = std::max(t.kmax, kmax[t.read_b]);
-                    i += 2;
-                } else {
-                    i += 1;
-                }
-                const NraDevRegion& d = dregs[pr.reads[t.read_a].region];
-                int qmax = pr.reads[t.read_a].qlen;
-                if (t.read_b >= 0) qmax = std::max(qmax, pr.reads[t.read_b].qlen);
-                const int nblk = bk.chain ? (qmax + 64 * bk.R - 1) / (64 * bk.R) : 1;
-                if (bk.ring)    // pipelines 64*m (forward) and 64 (reverse) columns deep, per row block
-                    bk.cells_sweep += (int64_t)nblk * (bk.wide ? 1 : 2) * 64 * bk.R *
-                                      ((d.l1 + d.m1 * t.kmax + 63 * d.m1) + (d.l3 + 63));
-                else
-                    bk.cells_sweep += (int64_t)nblk * (bk.wide ? 1 : 2) * (sweep128_cells(bk.R, d.l1 + d.m1 * t.kmax) +
-                                                                           sweep128_cells(bk.R, d.l3));
-                t.snap_off = snap_total;
-                snap_total += (uint64_t)nblk * 3 * bk.R * 64;
-                sweep_tasks.push_back(t);
-            }
-            bk.n_sweep = (int)(sweep_tasks.size() - bk.sweep_off);
-            if (bk.chain && bk.mt) {
-                // launch groups: as many tasks as the strip budget holds (one strip between consecutive blocks of a
-                // task), each group's (task, block) list block-major: all blocks 0, then all blocks 1, ...
-                const size_t fit = std::max<size_t>(1, (size_t)(NRA_CHAIN_SCRATCH_BUDGET / 2) / ((size_t)5 * 8 * (size_t)b->chain_cap));
-                const int rows = 64 * bk.R;
-                auto nblk_of = [&](const NraSweepTask& t) {
-                    int qmax = pr.reads[t.read_a].qlen;
-                    if (t.read_b >= 0) qmax = std::max(qmax, pr.reads[t.read_b].qlen);
-                    return std::max(1, (qmax + rows - 1) / rows);
-                };
-                size_t most_strips = 0;
-                for (int t0 = 0; t0 < bk.n_sweep;) {
-                    size_t used = 0;
-                    int t1 = t0, max_blk = 0;
-                    std::vector<size_t> base;
-                    while (t1 < bk.n_sweep) {
-                        const int nb2 = nblk_of(sweep_tasks[bk.sweep_off + (size_t)t1]);
-                        if (t1 > t0 && used + (size_t)(nb2 - 1) > fit) break;
-                        base.push_back(used);
-                        used += (size_t)(nb2 - 1);
-                        max_blk = std::max(max_blk, nb2);
-                        ++t1;
-                    }
-                    const size_t first_block = chain_blocks.size();
-                    for (int blk = 0; blk < max_blk; ++blk)
-                        for (int t = t0; t < t1; ++t) {
-                            const int nb2 = nblk_of(sweep_tasks[bk.sweep_off + (size_t)t]);
-                            if (blk >= nb2) continue;
-                            const int32_t sb = (int32_t)base[(size_t)(t - t0)];
-                            chain_blocks.push_back(NraChainBlock{t, blk, nb2, blk > 0 ? sb + blk - 1 : -1,
-                                                                 blk < nb2 - 1 ? sb + blk : -1});
-                        }
-                    bk.mt_groups.push_back({first_block, (int)(chain_blocks.size() - first_block)});
-                    most_strips = std::max(most_strips, used);
-                    t0 = t1;
-                }
-                bk.n_strips = (int)most_strips;
-                bk.strip_off = mt_strip_total;                     // (in strips of 5 * chain_cap granules)
-                mt_strip_total += most_strips;
-                chain_queue_cap = std::max(chain_queue_cap, bk.queue_cap);
-            } else if (bk.chain) {
-                // (two chained buckets at most -- packed and int32 -- share the budget)
-                bk.n_strips = chain_strips((size_t)bk.n_sweep, bk.ring ? NRA_RING_CHAIN_STRIPS : NRA_CHAIN_STRIPS,
-                                           (size_t)10 * 4 * (size_t)b->chain_cap, NRA_CHAIN_SCRATCH_BUDGET / 2);
-                bk.strip_off = strip_total;
-                strip_total += (size_t)bk.n_strips * 10 * (size_t)b->chain_cap;
-                chain_queue_cap = std::max(chain_queue_cap, bk.queue_cap);
-            }
-        }
-        bk.n_pair = (int)(pair_tasks.size() - bk.pair_off);
-        bk.n_queue = all_ext ? (int)bk.queue_cap : 0;
-        queue_total += bk.queue_cap;
-        queue_count.push_back(bk.n_queue);
-        task_base.push_back((uint32_t)bk.queue_off);
-        b->buckets.push_back(bk);
-    }
-    const size_t nb = b->buckets.size();
-    clk.mark("templates, buckets, tasks");
+    // (the plan reads the layout alone -- pr.reads -- not the words the workers are writing)
+    Plan1D plan;
+    rc = plan_1d(regions, n_regions, pr.reads, kmin, kmax, sc, flags, plan1d_knobs(), device_simds(device), clk, plan);
+    if (rc) return rc;
     packing.join();
-    b->has_n = (has_n || pr.has_n) ? 1 : 0;
+    b->has_n = (plan.has_n || pr.has_n) ? 1 : 0;
     clk.mark("2-bit packing (rest)");
 
-    // one chunk for everything: ~7 B per read base, ~40 B per candidate, the tasks, the chain strips
-    b->arena.expect(pr.q2bit.size() * 16 * 2 + (size_t)snap_total * 4 + (size_t)total * 40 + pool.size() + sweep_tasks.size() * sizeof(NraSweepTask) +
-                    pair_tasks.size() * sizeof(NraPairTask) + (size_t)n_reads * 64 + (4u << 20));
-    // (the chain strips get chunks of their own: they can be GBs)
-    UploadBatchScope uploads;            // every upload below is enqueued; one wait behind the last of them
-    HIP_TRY(b->pool.upload(pool));
-    HIP_TRY(b->q2bit.upload(pr.q2bit));
-    HIP_TRY(b->qnmask.upload(pr.nmask));
-    HIP_TRY(b->regions.upload(dregs));
-    HIP_TRY(b->reads.upload(pr.reads));
-    HIP_TRY(b->pair_tasks.upload(pair_tasks));
-    HIP_TRY(b->sweep_tasks.upload(sweep_tasks));
-    if (!brute) {
-        HIP_TRY(b->snap.alloc((size_t)snap_total));
-        HIP_TRY(b->read_a1d.alloc((size_t)n_reads));
-        bool any_taint = false;
-        for (const Bucket& bk : b->buckets) any_taint = any_taint || bk.taint;
-        if (any_taint) {
-            b->redo.n = std::max<size_t>(sweep_tasks.size(), 1);        // (a view into run_words, below)
-            b->task_reads.resize(sweep_tasks.size());
-            for (size_t t = 0; t < sweep_tasks.size(); ++t) {
-                const NraSweepTask& x = sweep_tasks[t];
-                b->task_reads[t] = (uint8_t)((x.read_a >= 0) + (x.read_b >= 0) + (x.read_c >= 0) + (x.read_d >= 0));
-            }
-        }
-        // Quanta (k_sweep_ringq): for the unchained LDS-ring buckets of a batch whose tasks are few against the wave slots --
-        // kernel-length tasks then end a launch with SIMDs holding 3 or 4 of them while others hold 2 or 3; with tens of
-        // tasks per slot (BASELINE config 4) two launches already run at 0.98 of the issue ceiling and the states at the
-        // cut (NRA_QSTATE_INTS(R) x 256 B a task) would only be traffic.
-        std::vector<uint32_t> qlist;
-        size_t q_tasks = 0, q_state = 0, n_q_tasks_all = 0;
-        for (const Bucket& bk : b->buckets) if (bk.ring && !bk.chain && !bk.mt) n_q_tasks_all += (size_t)bk.n_sweep;
-        // Parts of NRA_Q_STEPS = 384 steps.  Measured on one box, ms per step (config 2 | 5000 reads | 20 000 reads of it):
-        // no quanta 5.76 | 4.21 | 10.74; parts of 2048 (whole sweeps) 6.03; 1024 5.72; 768 5.32 | 3.39 | 9.93; 512 5.35 | 3.35 |
-        // 9.95; 448 5.25; 384 5.22 | 3.20 | 9.93; 320 5.33; 256 5.46 | 3.58 | 10.43; 192 5.55; 128 5.54.  With more than
-        // 8 tasks per SIMD the parts lose to two launches (40 000 reads 19.9 -> 20.2 ms, config 4 279 -> 285): the rule above.
-        // (NRA_TEST_QSTEPS overrides the part size for such measurements and for the tests.)
-        // Fewer tasks than SIMDs: a call's time is one task's chain of parts, every cut ~20 us of it (1000 reads: 1.99 -> 2.19 ms
-        // per step with parts of 384): a reverse sweep, a forward sweep to its first cut and the rest then, as in this round's
-        // first form.
-        int q_steps_wanted = n_q_tasks_all < (size_t)device_simds(device) ? NRA_Q_WHOLE : NRA_Q_STEPS;
-        if (const char* e = getenv("NRA_TEST_QSTEPS")) q_steps_wanted = std::max(64, atoi(e) / 64 * 64);
-        const bool want_quanta = (flags & (NRA_F_NO_QUANTA | NRA_F_DPP_SWEEP)) == 0 && n_q_tasks_all > 0 &&
-                                 n_q_tasks_all <= (size_t)8 * (size_t)device_simds(device);
-        for (Bucket& bk : b->buckets) {
-            if (!want_quanta || !bk.ring || bk.chain || bk.mt || bk.n_sweep <= 0) continue;
-            bk.quanta = true;
-            bk.q_off = qlist.size(); bk.q_task_off = q_tasks; bk.q_state_off = q_state;
-            // Parts of `q_steps` steps (a multiple of 64; longer for sweeps that would make more than NRA_Q_MAX_PARTS of them).
-            // Ticket order: every reverse sweep's part 0, task by task, then every part 1, ..., then the forward sweeps' parts
-            // the same way -- a part's producers (the part before it; for a forward part at or behind the first boundary step
-            // the task's whole reverse sweep) always hold smaller tickets.
-            const NraSweepTask* bt = sweep_tasks.data() + bk.sweep_off;
-            int max_steps = 0;
-            std::vector<int> steps_rev((size_t)bk.n_sweep), steps_fwd((size_t)bk.n_sweep), cut_fwd((size_t)bk.n_sweep);
-            for (int t = 0; t < bk.n_sweep; ++t) {
-                const NraDevRegion& d = dregs[pr.reads[bt[t].read_a].region];
-                steps_rev[(size_t)t] = NRA_Q_STEPS_REV(d.l3, bk.half);
-                steps_fwd[(size_t)t] = NRA_Q_STEPS_FWD(d.l1, d.m1, bt[t].kmax, bk.half);
-                cut_fwd[(size_t)t] = NRA_Q_CUT(d.l1 + d.m1 * bt[t].kmin - 1);
-                max_steps = std::max(max_steps, std::max(steps_rev[(size_t)t], steps_fwd[(size_t)t]));
-                bk.q_fwd_steps += steps_fwd[(size_t)t];
-            }
-            bk.q_steps = std::max(q_steps_wanted, ((max_steps + NRA_Q_MAX_PARTS - 2) / (NRA_Q_MAX_PARTS - 1) + 63) / 64 * 64);
-            for (int dir = 0; dir < 2; ++dir)
-                for (int part = 0; part < NRA_Q_MAX_PARTS; ++part) {
-                    bool any = false;
-                    for (int t = 0; t < bk.n_sweep; ++t) {
-                        // parts of this sweep: before the first cut (forward only), and from it on
-                        const int cut = dir ? cut_fwd[(size_t)t] : 0, steps = dir ? steps_fwd[(size_t)t] : steps_rev[(size_t)t];
-                        const int n_parts = (cut + bk.q_steps - 1) / bk.q_steps + std::max(1, (steps - cut + bk.q_steps - 1) / bk.q_steps);
-                        if (part < n_parts) {
-                            qlist.push_back(((uint32_t)dir << 31) | ((uint32_t)part << NRA_Q_PART_SHIFT) | (uint32_t)t);
-                            any = true;
-                        }
-                    }
-                    if (!any) break;
-                }
-            bk.n_quanta = (int)(qlist.size() - bk.q_off);
-            q_tasks += 2 * (size_t)bk.n_sweep;
-            int max_rev = 0;
-            for (int v : steps_rev) max_rev = std::max(max_rev, v);
-            q_state += (max_rev > bk.q_steps ? 2 : 1) * (size_t)bk.n_sweep * NRA_QSTATE_INTS(bk.R) * 64;
-        }
-        // (NRA_TEST_SAT=0 and NRA_TEST_SAT_STEPS in the environment, tests and measurements only: no saturation exit, and
-        // the steps between its checkpoints)
-        b->sat_steps = NRA_SAT_EXIT ? NRA_SAT_STEPS : -1;
-        if (const char* e = getenv("NRA_TEST_SAT_STEPS")) if (NRA_SAT_EXIT) b->sat_steps = std::max(0, atoi(e));
-        if (const char* e = getenv("NRA_TEST_SAT")) if (atoi(e) == 0) b->sat_steps = -1;
-        if (!qlist.empty()) {
-            HIP_TRY(b->q_list.upload(qlist));
-            b->q_arrivals_off = (1 + b->buckets.size() + 3) / 4 * 4;
-            b->q_words_n = b->q_arrivals_off + q_tasks;            // (a view into run_words, below)
-            HIP_TRY(b->q_state.alloc(q_state));
-        }
-    }
-    {
-        // Does a run have to clear cand_score and cand_flag first (run_1d)?  Not where the forward sweeps write both for
-        // every candidate.  Per kernel family, from its `flush` (nra_sweep.hip): a task's sweep puts out one value per
-        // repeat count of [task kmin, task kmax], the union of its reads' windows (the boundary of kcur leaves lane W - 1
-        // while kcur <= kmax; the last, partial group of W is flushed behind the loop), and `flush` stores score (-1 below
-        // min_score) and verdict for every read of the task whose window holds that count, under no other condition.
-        // A half-wave task's empty upper half (`half_on`) has no reads.  The re-sweep only rewrites.
-        // The table records that reading, family by family: a new family, or one whose `flush` changes, goes in with
-        // `false` (its batches keep the clears) until its `flush` has been read again.
-        enum Family { F_RING, F_RING32, F_RINGQ, F_RINGMT, F_RINGCHAIN, F_PK16, F_COUNT };
-        static const bool kFlushWritesAll[F_COUNT] = {
-            true,       // k_sweep_ring      (sweep_ring_body)
-            true,       // k_sweep_ring32    (sweep_ring_body, HALF)
-            true,       // k_sweep_ringq     (sweep_ring_body, QUANTA: the part that ends the forward sweep flushes the rest;
-                        //                    the saturation exit flushes and writes every count from kcur to the task's kmax)
-            true,       // k_sweep_ringmt    (the last row block's wave)
-            true,       // k_sweep_ringchain (the last row block)
-            true,       // k_sweep_pk16      (sweep_body; CHAIN: the last row block)
-        };
-        // not with brute force, NRA_F_ALL_EXTENTS or NRA_F_TIE_EXTENTS (no sweeps; the cleared flag 2 is what sends a
-        // candidate to the extents kernel there), and every read with candidates has to be in a bucket (an empty read is
-        // in none: its candidates keep the cleared -1)
-        bool all = !brute && !all_ext && (flags & NRA_F_TIE_EXTENTS) == 0;
-        for (int32_t r = 0; r < n_reads && all; ++r) all = kmin[r] > kmax[r] || pr.reads[r].qlen > 0;
-        for (const Bucket& bk : b->buckets) {
-            const Family f = bk.quanta ? F_RINGQ : bk.mt ? F_RINGMT : (bk.ring && bk.chain) ? F_RINGCHAIN
-                           : (bk.ring && bk.half) ? F_RING32 : bk.ring ? F_RING : F_PK16;
-            all = all && kFlushWritesAll[f];
-        }
-        b->sweeps_write_all = all;
-    }
-    HIP_TRY(b->cand_flag.alloc((size_t)total));
-    if (!chain_blocks.empty()) {
-        HIP_TRY(b->chain_blocks.upload(chain_blocks));
-        const size_t granules = std::max<size_t>(mt_strip_total, 1) * 5 * (size_t)b->chain_cap;
-        HIP_TRY(b->mt_strips.alloc(granules));
-        // (on the batch's own stream: the bucket streams are ordered behind it by fork_ev; a null-stream memset is not
-        // ordered with these non-blocking streams at all)
-        HIP_TRY(hipMemsetAsync(b->mt_strips.p, 0, granules * 8, b->stream));       // no granule carries an epoch yet (epochs are never 0)
-        HIP_TRY(b->mt_words.alloc(2 + b->buckets.size()));
-        HIP_TRY(hipMemsetAsync(b->mt_words.p, 0, (2 + b->buckets.size()) * 4, b->stream));
-        HIP_TRY(hipStreamSynchronize(b->stream));
-    }
-    if (strip_total || !chain_blocks.empty()) {
-        if (strip_total) HIP_TRY(b->chain_sweep.alloc(strip_total));
-        // the chained buckets' extents launches run in turn and share these strips (int64 cells)
-        b->payload_strips = chain_strips(chain_queue_cap, NRA_CHAIN_STRIPS, (size_t)6 * 8 * (size_t)b->chain_cap);
-        HIP_TRY(b->chain_payload.alloc((size_t)b->payload_strips * 6 * (size_t)b->chain_cap));
-    }
-    if (all_ext) HIP_TRY(b->queue_tasks.upload(queue_tasks));
-    else HIP_TRY(b->queue_tasks.alloc(queue_total));
-    HIP_TRY(b->queue_count.upload(queue_count));
-    {
-        // the words of a run: [q_words | the row blocks' give-up word | tie_count | sat_count | redo], zero before any run too
-        // (so that nra_batch1d_resweeps and nra_batch1d_saturation read nothing of a run that has not happened)
-        const size_t n_redo = b->redo.n, n_words = b->q_words_n + 1 + 5 * std::max<size_t>(nb, 1) + 1 + n_redo;
-        HIP_TRY(b->run_words.alloc(n_words));
-        int32_t* w = b->run_words.p;
-        auto view = [&](DevBuf<int32_t>& buf, size_t n) { buf.p = w; buf.n = n; buf.owned = false; w += n; };
-        view(b->q_words, b->q_words_n);
-        b->mt_giveup = w++;
-        view(b->tie_count, std::max<size_t>(nb, 1));
-        if (reinterpret_cast<uintptr_t>(w) & 7) ++w;                     // (the 64-bit step counts of sat_count: 8-byte aligned)
-        view(b->sat_count, 4 * std::max<size_t>(nb, 1));
-        view(b->redo, n_redo);
-        HIP_TRY(hipMemsetAsync(b->run_words.p, 0, n_words * 4, b->stream));
-        HIP_TRY(hipStreamSynchronize(b->stream));
-    }
-    HIP_TRY(b->bucket_task_base.upload(task_base));
-    {
-        std::vector<int32_t> v(kmin, kmin + n_reads); HIP_TRY(b->kmin.upload(v));
-        std::vector<int32_t> w(kmax, kmax + n_reads); HIP_TRY(b->kmax.upload(w));
-    }
-    HIP_TRY(b->read_bucket.upload(read_bucket));
-    HIP_TRY(b->coff.upload(coff));
-    HIP_TRY(b->cand_score.alloc((size_t)total));
-    HIP_TRY(b->cand_tstart.alloc((size_t)total));
-    HIP_TRY(b->cand_tend.alloc((size_t)total));
-    rc = alloc_results(b, (size_t)n_reads, false);
+    b->n_cands = plan.n_cands;
+    b->brute = plan.brute;
+    b->relax_c = plan.relax_c;
+    b->chain_cap = plan.chain_cap;
+    b->sat_steps = plan.sat_steps;
+    b->sweeps_write_all = plan.sweeps_write_all;
+    b->buckets = std::move(plan.buckets);
+    b->task_reads = std::move(plan.task_reads);
+    rc = upload_plan_1d(b, plan, pr, kmin, kmax);
     if (rc) return rc;
-    HIP_TRY(upload_batch_end());
     clk.mark("device buffers, H2D");
+
+    const size_t nb = b->buckets.size();
     rc = make_events(b, 2 + 6 * (int)nb + 2);
     if (rc) return rc;
-    if (!brute) {
+    if (!plan.brute) {
         b->bstreams.assign(nb, nullptr); b->bdone.assign(nb, nullptr);
         for (size_t i = 0; i < nb; ++i) {
             HIP_TRY(g_handles.stream(b->device, &b->bstreams[i]));
@@ -1613,15 +1065,37 @@ int nra_batch1d_create(int device, const nra_region_t* regions, int32_t n_region
     }
 
     clk.mark("events, streams");
-    b->stats.n_alignments = total;
-    b->stats.algorithmic_cells = alg_cells;
-    int64_t ex = 0;
-    for (const Bucket& bk : b->buckets) ex += bk.cells_pair + bk.cells_queue + bk.cells_sweep;
-    b->stats.executed_cells = ex;
-    b->stats.algorithmic_bytes = (int64_t)pr.q2bit.size() * 4 + (int64_t)pool.size() + total * 4 + (int64_t)n_reads * 17;
-    b->stats.intermediate_bytes = brute ? 0 : 2 * ((int64_t)snap_total + (int64_t)b->q_state.n) * 4;   // the junction snapshot and the wave states at the cut: written, then read
+    b->stats.n_alignments = plan.n_cands;
+    b->stats.algorithmic_cells = plan.alg_cells;
+    b->stats.executed_cells = plan.cells_pair + plan.cells_queue + plan.cells_sweep;
+    b->stats.algorithmic_bytes = (int64_t)pr.q2bit.size() * 4 + (int64_t)plan.pool.size() + plan.n_cands * 4 + (int64_t)n_reads * 17;
+    b->stats.intermediate_bytes = plan.brute ? 0 : 2 * ((int64_t)plan.snap_total + (int64_t)b->q_state.n) * 4;   // the junction snapshot and the wave states at the cut: written, then read
     *out = guard.release();
     return NRA_OK;
+}
+
+int64_t nra_plan1d_digest(const nra_region_t* regions, int32_t n_regions,
+                          int32_t n_reads, const char* seqs, const int64_t* seq_off,
+                          const int32_t* read_region, const int32_t* kmin, const int32_t* kmax,
+                          const nra_scoring_t* sc, int32_t flags, int32_t simds, char* buf, int64_t cap)
+{
+    int rc = check_batch1d_args(regions, n_regions, n_reads, seqs, seq_off, read_region, kmin, kmax, sc);
+    if (rc) return rc;
+    if (simds <= 0 || cap < 0 || (cap > 0 && !buf)) return fail(NRA_E_ARG, "bad simds / buffer");
+    PackedReads pr;
+    rc = pack_layout(n_reads, seq_off, read_region, n_regions, pr, NRA_MAX_QLEN);
+    if (rc) return rc;
+    PhaseClock clk(false);
+    Plan1D plan;
+    rc = plan_1d(regions, n_regions, pr.reads, kmin, kmax, sc, flags, plan1d_knobs(), simds, clk, plan);
+    if (rc) return rc;
+    const std::string text = plan_1d_digest(plan);
+    if (cap > 0) {
+        const size_t n = std::min(text.size(), (size_t)cap - 1);
+        memcpy(buf, text.data(), n);
+        buf[n] = 0;
+    }
+    return (int64_t)text.size() + 1;
 }
 
 // what a run of a 1D batch clears first (run_1d; nra_batch1d_clears reports it)
@@ -2305,7 +1779,7 @@ int set_cells_common(nra_batch* b, const int8_t* read_strand, int64_t n_cells, c
     const int32_t n_reads = b->n_reads;
     const int32_t flags = b->flags;
     std::vector<NraDevRead> reads(b->host_reads);              // + the shadows of chained reads, below
-    PhaseClock clk;
+    PhaseClock clk(g_debug_phases);
 
     std::vector<uint32_t> first((size_t)n_reads, 0), cnt((size_t)n_reads, 0);
     int32_t k1max = 0, k2max = 0;
