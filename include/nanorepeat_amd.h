@@ -663,6 +663,47 @@ int nra_censored_posteriors(int device, int64_t n_values, const double* values, 
                             const double* prob_tau, const int32_t* model_n, const int32_t* model_open, const double* w,
                             const double* nu, int64_t n_resp, double* resp);
 
+/* ---- bootstrap of the censored allele fit: the model search of every replicate of every problem in one call
+ *
+ * A bootstrap problem is a problem as above in sorted layout: its m = n_exact exact values ascending, then its
+ * q = N - m bounds ascending.  Replicate b of it is the row idx[b][0..N) of indices into the problem's values,
+ * ascending, so that its first m_b = #(idx[b][j] < m) positions are exact values in order and the others bounds in
+ * order; position j holds value idx[b][j] of the problem (the row 0, 1, ..., N - 1 is the problem itself).
+ * Model search of a replicate with m_b >= 1, every fit as specified for nra_censored_fit on the replicate's values:
+ *   d_b = the number of distinct values among the exact positions; q_b = N - m_b.
+ *   for n = 1 .. min(max_alleles, d_b), open = 0 and, when q_b > 0, open = 1:
+ *     three starts, each n means taken from the replicate by position, with pos(k, n, L) = min(L - 1, floor((k + 0.5) /
+ *     n * L)) evaluated in float64, the division and the product each rounded once:
+ *       start 0: exact position pos(k, n, m_b) for k < n;
+ *       start 1: value pos(k, n, N) of the merge of the two sorted runs for k < n;
+ *       start 2: exact position pos(k, n - 1, m_b) for k < n - 1, then the larger of the runs' last values.
+ *     the best start is the largest ll, a tie to the lowest start.
+ *     BIC = -2 ll + (2 n + open - 1) lnN, the product taken first, nothing contracted; lnN is the caller's ln N.
+ *   the model is the lowest BIC; within 1e-9 of it the fewest parameters 2 n + open win, then open = 0.
+ * A replicate with m_b = 0 is not fitted: NRA_CENS_BOOT_NO_EXACT, n = 0, open = (q_b > 0).
+ * A replicate is a function of its problem's values, its row, tau, lnN, max_alleles, max_iter and tol alone: not of
+ * the other replicates or problems of the call, their order, the flags or the run.  DESIGN.md section 27. */
+#define NRA_CENS_BOOT_FITTED    0
+#define NRA_CENS_BOOT_NO_EXACT  1
+#define NRA_CENS_BOOT_MAX_B  1000   /* largest n_rep */
+
+/* Problems as for nra_censored_fit, each in sorted layout, with prob_ln_n[p] = ln N.  idx: n_rep * N indices per
+ * problem, problems in order, replicate-major; rep_m[p * n_rep + b] = m_b.  Replicate b of problem p is r = p * n_rep + b
+ * and writes status[r], model_n[r], model_open[r], best_start[r], n_iter[r], ll[r], bic[r], nu[8 r + k] for k < n and
+ * w[9 r + k] for k < n + open (the open weight at k = n); entries not written are 0.  flags: NRA_CENS_F_STREAM; the
+ * results do not depend on it.
+ * n_rep < 1, an index outside 0 .. N - 1, a row that is not ascending, rep_m that disagrees with its row, a value, tau
+ * or lnN that is not finite, tau <= 0, n_exact outside 1..N, values that are not ascending within a part, max_iter < 1,
+ * tol negative or not finite, or an unknown flag is NRA_E_ARG; n_rep > 1000, max_alleles outside 1..8, N > 1 048 576,
+ * max_iter > 500 or more than 2^31 - 1 replicates in all is NRA_E_RANGE.  Arguments are checked before the device is
+ * touched. */
+int nra_censored_bootstrap(int device, int64_t n_values, const double* values, int32_t n_problems,
+                           const int64_t* prob_off, const int32_t* prob_n, const int32_t* prob_n_exact,
+                           const double* prob_tau, const double* prob_ln_n, int32_t n_rep, const int32_t* idx,
+                           const int32_t* rep_m, int32_t max_alleles, int32_t max_iter, double tol, int32_t flags,
+                           int32_t* status, int32_t* model_n, int32_t* model_open, int32_t* best_start,
+                           int32_t* n_iter, double* ll, double* bic, double* nu, double* w);
+
 /* ---- allele consensus: one sequence per group of tracts (no counterpart in the reference) ----------------------------
  *
  * Integer arithmetic throughout: the outputs are a function of the group alone, bit for bit.

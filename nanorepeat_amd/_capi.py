@@ -40,7 +40,7 @@ EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count
            "nra_screen_set_motifs", "nra_screen_reads_partial",
            "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts", "nra_mixture_fit", "nra_mixture_bootstrap",
            "nra_tract_consensus", "nra_allele_split", "nra_flank_phase", "nra_tract_segments", "nra_tract_periods",
-           "nra_censored_fit", "nra_censored_posteriors")
+           "nra_censored_fit", "nra_censored_posteriors", "nra_censored_bootstrap")
 
 
 E_RANGE = -3      # NRA_E_RANGE
@@ -212,6 +212,10 @@ def load():
     lib.nra_censored_posteriors.restype = C.c_int
     lib.nra_censored_posteriors.argtypes = [C.c_int, C.c_int64, pf64, C.c_int32, pi64, pi32, pi32, pf64, pi32, pi32,
                                             pf64, pf64, C.c_int64, pf64]
+    lib.nra_censored_bootstrap.restype = C.c_int
+    lib.nra_censored_bootstrap.argtypes = [C.c_int, C.c_int64, pf64, C.c_int32, pi64, pi32, pi32, pf64, pf64, C.c_int32,
+                                           pi32, pi32, C.c_int32, C.c_int32, C.c_double, C.c_int32, pi32, pi32, pi32,
+                                           pi32, pi32, pf64, pf64, pf64, pf64]
     lib.nra_allele_split.restype = C.c_int
     lib.nra_allele_split.argtypes = [C.c_int, C.c_int32, pi64, C.c_int32, C.c_char_p, pi64, C.c_char_p, pi64] + \
                                     [C.c_int32] * 7 + [pi32, pi32, pi32, C.c_int64, pi32, pi64, C.c_int64, p8, pi64, pi64]
@@ -912,6 +916,40 @@ def censored_posteriors(values, prob_off, prob_n, prob_n_exact, prob_tau, model_
                                        _ptr(mn, C.c_int32), _ptr(mo, C.c_int32), _ptr(ww, C.c_double),
                                        _ptr(mu, C.c_double), len(resp), _ptr(resp, C.c_double)))
     return [resp[r_off[p]:r_off[p + 1]].reshape(int(pn[p]), int(nc[p])) for p in range(len(po))]
+
+
+CENS_BOOT_FITTED, CENS_BOOT_NO_EXACT = 0, 1      # NRA_CENS_BOOT_FITTED, NRA_CENS_BOOT_NO_EXACT
+
+
+def censored_bootstrap(values, prob_off, prob_n, prob_n_exact, prob_tau, prob_ln_n, n_rep, idx, rep_m, max_alleles,
+                       max_iter=500, tol=1e-9, flags=0, device=0):
+    """nra_censored_bootstrap: the model search of n_rep replicates of every problem.  Problems as for censored_fit, each
+    in sorted layout (exact values ascending, then bounds ascending), prob_ln_n[p] = math.log(prob_n[p]); idx: the
+    problems' ascending index rows (n_rep * prob_n[p] each) concatenated in problem order, rep_m [problems, n_rep] the
+    exact positions of every row -> dict(status, model_n, model_open, best_start, n_iter, ll, bic [problems, n_rep];
+    nu [problems, n_rep, 8]; w [problems, n_rep, 9], the open weight at index model_n)."""
+    lib = load()
+    y, po, pn, pe, pt = _censored_problems(values, prob_off, prob_n, prob_n_exact, prob_tau)
+    pl = np.ascontiguousarray(prob_ln_n, np.float64)
+    ix = np.ascontiguousarray(idx, np.int32).ravel()
+    rm = np.ascontiguousarray(rep_m, np.int32).ravel()
+    n_rep, n = int(n_rep), len(po)
+    if len(pl) != n:
+        raise ValueError("one lnN per problem")
+    if len(ix) != max(n_rep, 0) * int(np.maximum(pn, 0).astype(np.int64).sum()) or len(rm) != max(n_rep, 0) * n:
+        raise ValueError("n_rep * N indices and n_rep exact counts per problem")
+    r = (n, max(n_rep, 0))
+    out = dict(status=np.zeros(r, np.int32), model_n=np.zeros(r, np.int32), model_open=np.zeros(r, np.int32),
+               best_start=np.zeros(r, np.int32), n_iter=np.zeros(r, np.int32), ll=np.zeros(r), bic=np.zeros(r),
+               nu=np.zeros(r + (CENS_MAX_COMPONENTS,)), w=np.zeros(r + (CENS_MAX_COMPONENTS + 1,)))
+    _check(lib.nra_censored_bootstrap(
+        device, len(y), _ptr(y, C.c_double), n, _ptr(po, C.c_int64), _ptr(pn, C.c_int32), _ptr(pe, C.c_int32),
+        _ptr(pt, C.c_double), _ptr(pl, C.c_double), n_rep, _ptr(ix, C.c_int32), _ptr(rm, C.c_int32), int(max_alleles),
+        int(max_iter), float(tol), flags, _ptr(out["status"], C.c_int32), _ptr(out["model_n"], C.c_int32),
+        _ptr(out["model_open"], C.c_int32), _ptr(out["best_start"], C.c_int32), _ptr(out["n_iter"], C.c_int32),
+        _ptr(out["ll"], C.c_double), _ptr(out["bic"], C.c_double), _ptr(out["nu"], C.c_double),
+        _ptr(out["w"], C.c_double)))
+    return out
 
 
 BOOT_DECIDED, BOOT_NEEDS_MORE = 0, 1      # NRA_BOOT_DECIDED, NRA_BOOT_NEEDS_MORE

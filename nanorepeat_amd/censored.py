@@ -19,6 +19,13 @@ without a spanning read is not fitted: 0 closed alleles, and an open one when it
 `censored_regions` fills `region.censored_fit`; `write_censored_fit`, `write_censored_reads` and
 `write_censored_summary` write `<region>.censored_fit.tsv`, `<region>.censored_reads.tsv` and
 `<out_prefix>.NanoRepeat_censored.tsv`; `report_censored_calls` prints one NOTICE.
+
+`censored_bootstrap=B` resamples every region's reads B times, spanning reads and bounds jointly,
+and runs the whole model search of every replicate in one `nra_censored_bootstrap` call: `bootstrap_problems` builds
+the sorted layouts and the index rows and computes, in numpy over a region's replicates, how often the called model
+comes back (`Model_Support`), how often an open allele does (`Open_Support`) and the percentile interval of every
+called allele's size and weight; `write_censored_bootstrap` and `write_censored_bootstrap_summary` write
+`<region>.censored_bootstrap.tsv` and `<out_prefix>.NanoRepeat_censored_bootstrap.tsv`.  Nothing is thresholded.
 """
 import math
 import sys
@@ -297,3 +304,174 @@ def report_censored_calls(regions, stream=None):
         print(f"NOTICE: censored fit: {n_open} region(s) have an open allele (an allele no read spans); in {n_diff} "
               "region(s) the number of closed alleles differs from the standard call", file=stream)
     return n_open, n_diff
+
+
+# ---------------------------------------------------------------------------- bootstrap
+BOOT_SALT = 0x63656E73                # "cens": keeps these draws apart from every other stream of (seed, region)
+BOOT_FITTED, BOOT_NO_EXACT = 0, 1     # NRA_CENS_BOOT_FITTED, NRA_CENS_BOOT_NO_EXACT
+
+
+def sorted_layout(problem):
+    """The values of a problem as the bootstrap reads them: the exact ones ascending, then the bounds ascending."""
+    return sorted(problem.y[:problem.m]) + sorted(problem.y[problem.m:])
+
+
+def resample_rows(seed, region_index, m, n_points, n_rep):
+    """(idx [n_rep, N] int32, rep_m [n_rep] int32): N draws from all N observations per replicate, every row sorted, so
+    that a replicate's first rep_m positions are exact values in order and the others bounds in order."""
+    rng = np.random.default_rng([int(seed), int(region_index), BOOT_SALT])
+    idx = np.sort(rng.integers(0, n_points, size=(n_rep, n_points)), axis=1).astype(np.int32)
+    return idx, (idx < m).sum(axis=1).astype(np.int32)
+
+
+def percentile_interval(values, confidence):
+    """Section 24's nearest-rank interval (bootstrap.percentile_interval) of r values; None for r = 0."""
+    from .bootstrap import percentile_interval as interval
+    return interval(values, confidence)
+
+
+class CensoredBootstrap:
+    """The bootstrap of one region against its call `fit` (a CensoredFit with m >= 1).  Per replicate: `num_spanning`,
+    `n`, `open`, and `nu`, `w` [B, n] of its closed alleles by size (ties by index, as fit_problems ranks them; padded
+    with nan) and `w_open` (nan without one, and for a replicate that was not fitted).  Against the call: `model_support`, `open_support`, `distribution`, and
+    `rows`: per called allele (kind, size CI low, size CI high, weight low, weight high, replicates used)."""
+
+    def __init__(self, seed, num_spanning, n, open_, nu, w, fit, confidence):
+        self.seed = seed
+        self.num_spanning, self.n, self.open = (np.asarray(v, np.int64) for v in (num_spanning, n, open_))
+        B = self.n_replicates = len(self.n)
+        nu, w = np.asarray(nu, np.float64).reshape(B, -1), np.asarray(w, np.float64).reshape(B, -1)
+        C = nu.shape[1]
+        closed = np.arange(C)[None, :] < self.n[:, None]
+        order = np.argsort(np.where(closed, nu, np.inf), axis=1, kind="stable")
+        self.nu = np.where(closed, np.take_along_axis(nu, order, axis=1), np.nan)
+        self.w = np.where(closed, np.take_along_axis(w[:, :C], order, axis=1), np.nan)
+        at_n = np.take_along_axis(w, np.minimum(self.n, w.shape[1] - 1)[:, None], axis=1)[:, 0]
+        self.w_open = np.where((self.open == 1) & (self.n > 0), at_n, np.nan)
+        same_n = self.n == fit.n
+        same = same_n & (self.open == fit.open)
+        self.model_support = float(same.sum()) / B
+        self.open_support = float((self.open == 1).sum()) / B
+        models, tally = np.unique(np.stack([self.open, self.n], axis=1), axis=0, return_counts=True)
+        self.distribution = ",".join(f"{int(n_)}+{int(o)}:{int(c)}" for (o, n_), c in zip(models, tally))
+        self.rows = []
+        for k in range(fit.n):
+            size = percentile_interval(np.exp(self.nu[same_n, k]) - 10.0, confidence)
+            weight = percentile_interval(self.w[same_n, k], confidence)
+            self.rows.append(("closed",) + (size or (None, None)) + (weight or (None, None)) + (int(same_n.sum()),))
+        if fit.open:
+            weight = percentile_interval(self.w_open[same], confidence)
+            self.rows.append(("open", None, None) + (weight or (None, None)) + (int(same.sum()),))
+
+
+def bootstrap_problems(problems, fits, n_rep, seed, confidence=0.95, max_alleles=MAX_ALLELES, engine=None, device=0,
+                       indices=None):
+    """One CensoredBootstrap per problem (None where it has no exact value): the sorted layouts, index rows, rep_m and
+    lnN of all problems with m >= 1, one engine.censored_bootstrap call, the statistics in numpy over the replicates of
+    a region.  `fits`: fit_problems' result; `indices`: every problem's region index (default: its place in the list),
+    which with `seed` names its random stream; `engine`: an object with censored_bootstrap (default _capi)."""
+    if engine is None:
+        from . import _capi
+        engine = _capi
+    if not 1 <= max_alleles <= 8:
+        raise ValueError(f"censored_max_alleles must be in 1..8, not {max_alleles!r}")
+    if n_rep < 1 or int(n_rep) != n_rep:
+        raise ValueError(f"censored_bootstrap must be a number of replicates >= 1 here, not {n_rep!r}")
+    n_rep = int(n_rep)
+    indices = list(range(len(problems))) if indices is None else list(indices)
+    out = [None] * len(problems)
+    live = [i for i, pr in enumerate(problems) if pr.m > 0]
+    if not live:
+        return out
+    values, off, rows, rep_m = [], [], [], []
+    for i in live:
+        pr = problems[i]
+        off.append(len(values)); values += sorted_layout(pr)
+        idx, m_b = resample_rows(seed, indices[i], pr.m, pr.m + pr.q, n_rep)
+        rows.append(idx.ravel()); rep_m.append(m_b)
+    n_pts = [problems[i].m + problems[i].q for i in live]
+    rep = engine.censored_bootstrap(np.array(values), np.array(off, np.int64), np.array(n_pts, np.int32),
+                                    np.array([problems[i].m for i in live], np.int32),
+                                    np.array([problems[i].tau for i in live]), np.array([math.log(n) for n in n_pts]),
+                                    n_rep, np.concatenate(rows), np.stack(rep_m), max_alleles, max_iter=MAX_ITER, tol=TOL,
+                                    device=device)
+    for p, i in enumerate(live):
+        out[i] = CensoredBootstrap(seed, rep_m[p], rep["model_n"][p], rep["model_open"][p], rep["nu"][p], rep["w"][p],
+                                   fits[i], confidence)
+    return out
+
+
+def bootstrap_regions(repeat_regions, n_rep, seed, confidence=0.95, max_alleles=MAX_ALLELES, engine=None, device=0):
+    """Sets `region.censored_bootstrap` (a CensoredBootstrap, or None without a fit or a spanning read) for every region
+    that censored_regions has been through."""
+    with_fit = [r for r in repeat_regions if getattr(r, "censored_fit", None) is not None]
+    boots = bootstrap_problems([r.censored_fit.problem for r in with_fit], [r.censored_fit for r in with_fit], n_rep,
+                               seed, confidence, max_alleles, engine, device, [r.index for r in with_fit])
+    for region in repeat_regions:
+        region.censored_bootstrap = None
+    for region, boot in zip(with_fit, boots):
+        region.censored_bootstrap = boot
+    return repeat_regions
+
+
+def censored_bootstrap_text(region):
+    boot = region.censored_bootstrap
+    lines = [f"##RepeatRegion={region.to_unique_id()}\n", f"##Seed={boot.seed}\n",
+             "#Replicate\tNum_Spanning\tNum_Closed\tOpen\tSizes\tWeights\n"]
+    for b in range(boot.n_replicates):
+        n, o = int(boot.n[b]), int(boot.open[b])
+        sizes = ",".join(f"{math.exp(v) - 10.0:.1f}" for v in boot.nu[b, :n]) or "-"
+        weights = ",".join([f"{v:.4f}" for v in boot.w[b, :n]] + ([f"{boot.w_open[b]:.4f}"] if n and o else [])) or "-"
+        lines.append(f"{b}\t{int(boot.num_spanning[b])}\t{n}\t{o}\t{sizes}\t{weights}\n")
+    return "".join(lines)
+
+
+def write_censored_bootstrap(region):
+    """`<region out_prefix>.censored_bootstrap.tsv`: the model of every replicate (not with no_details)."""
+    if region.no_details or not region.out_prefix or getattr(region, "censored_bootstrap", None) is None:
+        return None
+    path = f"{region.out_prefix}.censored_bootstrap.tsv"
+    with open(path, "w") as f:
+        f.write(censored_bootstrap_text(region))
+    return path
+
+
+BOOT_HEADER = ("#Chrom\tStart\tEnd\tMotif\tAllele\tKind\tSize\tWeight\tCI_Low\tCI_High\tWeight_Low\tWeight_High\t"
+               "Replicates_Used\tNum_Replicates\tModel_Support\tOpen_Support\tModel_Distribution\n")
+BOOT_FIELDS = 17
+
+
+def censored_bootstrap_rows(region):
+    head = f"{region.chrom}\t{max(0, region.start_pos)}\t{region.end_pos}\t{region.repeat_unit_seq}"
+    boot = getattr(region, "censored_bootstrap", None)
+    if boot is None:
+        return head + "\t-" * (BOOT_FIELDS - 4) + "\n"
+    cf = region.censored_fit
+    out = []
+    for a, (kind, lo, hi, w_lo, w_hi, used) in enumerate(boot.rows):
+        size = cf.sizes()[a] if kind == "closed" else None
+        out.append(f"{head}\t{a + 1}\t{kind}\t{_f(size, '.1f')}\t{cf.w[a]:.4f}\t{_f(lo, '.1f')}\t{_f(hi, '.1f')}\t"
+                   f"{_f(w_lo, '.4f')}\t{_f(w_hi, '.4f')}\t{used}\t{boot.n_replicates}\t{boot.model_support:.4f}\t"
+                   f"{boot.open_support:.4f}\t{boot.distribution}\n")
+    return "".join(out)
+
+
+def write_censored_bootstrap_summary(regions, out_prefix):
+    """`<out_prefix>.NanoRepeat_censored_bootstrap.tsv`: one row per (region, called allele), in BED order; a region
+    without a fit gets one row of `-`."""
+    path = f"{out_prefix}.NanoRepeat_censored_bootstrap.tsv"
+    with open(path, "w") as f:
+        f.write(BOOT_HEADER)
+        f.write("".join(censored_bootstrap_rows(region) for region in regions))
+    return path
+
+
+def report_censored_bootstrap(regions, stream=None):
+    """One NOTICE counting the regions whose called model has less than half of the replicates.  Returns the count."""
+    stream = stream or sys.stderr
+    boots = [b for b in (getattr(r, "censored_bootstrap", None) for r in regions) if b is not None]
+    weak = sum(b.model_support < 0.5 for b in boots)
+    if weak:
+        print(f"NOTICE: censored bootstrap: in {weak} of {len(boots)} region(s) fewer than half of the replicates give the "
+              "called model", file=stream)
+    return weak

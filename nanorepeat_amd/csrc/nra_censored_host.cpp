@@ -1,10 +1,14 @@
 // nra_censored_host.cpp -- C ABI of the censored allele fit (nra_censored_fit, nra_censored_posteriors): argument checks,
 // one upload, one launch of k_censored_fit (nra_censored.hip) per register class or one of k_censored_resp, one download.
 // A fit is one wavefront and shares nothing with another, so a call is never chunked.
+// nra_censored_bootstrap: the same checks and those of the index rows; per launch group (whole problems whose records
+// and index rows fit a byte budget) one packed upload, one launch of k_censored_boot per register class, one of
+// k_censored_pick, one download.  The per-(replicate, n, open) records never leave the device.
 #include "nra_host_util.h"
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <new>
 #include <string>
 #include <vector>
@@ -205,6 +209,157 @@ int nra_censored_posteriors(int device, int64_t n_values, const double* values, 
         NRA_HIP_TRY(hipMemcpy(resp, d_r.p, (size_t)need * sizeof(double), hipMemcpyDeviceToHost));
     } catch (const std::bad_alloc&) {
         return fail(NRA_E_NOMEM, "censored posteriors: host allocation failed");
+    }
+    return NRA_OK;
+}
+
+// The model search of n_rep replicates of every problem.  A replicate is a function of its own
+// row alone, so the split into launch groups is invisible in the results.
+int nra_censored_bootstrap(int device, int64_t n_values, const double* values, int32_t n_problems,
+                           const int64_t* prob_off, const int32_t* prob_n, const int32_t* prob_n_exact,
+                           const double* prob_tau, const double* prob_ln_n, int32_t n_rep, const int32_t* idx,
+                           const int32_t* rep_m, int32_t max_alleles, int32_t max_iter, double tol, int32_t flags,
+                           int32_t* status, int32_t* model_n, int32_t* model_open, int32_t* best_start,
+                           int32_t* n_iter, double* ll, double* bic, double* nu, double* w)
+{
+    if (flags & ~NRA_CENS_F_STREAM) return fail(NRA_E_ARG, "unknown flag");
+    if (n_rep < 1) return fail(NRA_E_ARG, "fewer than one replicate");
+    if (n_rep > NRA_CENS_BOOT_MAX_B) return fail(NRA_E_RANGE, "more than 1000 replicates");
+    if (max_alleles < 1 || max_alleles > NRA_CENS_MAX_COMPONENTS) return fail(NRA_E_RANGE, "max_alleles must be in 1..8");
+    if (max_iter < 1) return fail(NRA_E_ARG, "max_iter must be >= 1");
+    if (max_iter > NRA_CENS_MAX_ITER) return fail(NRA_E_RANGE, "max_iter is more than 500");
+    if (!std::isfinite(tol) || tol < 0.0) return fail(NRA_E_ARG, "tol must be finite and >= 0");
+    if (int rc = check_problems(n_values, values, n_problems, prob_off, prob_n, prob_n_exact, prob_tau)) return rc;
+    if ((int64_t)n_problems * n_rep > INT32_MAX) return fail(NRA_E_RANGE, "more than 2^31 - 1 replicates in all");
+    if (n_problems > 0 && (!prob_ln_n || !idx || !rep_m || !status || !model_n || !model_open || !best_start || !n_iter ||
+                           !ll || !bic || !nu || !w))
+        return fail(NRA_E_ARG, "NULL array");
+    std::vector<int64_t> idx_off;
+    try {
+        idx_off.resize((size_t)n_problems + 1, 0);
+    } catch (const std::bad_alloc&) {
+        return fail(NRA_E_NOMEM, "censored bootstrap: host allocation failed");
+    }
+    for (int32_t p = 0; p < n_problems; ++p) {
+        const std::string who = "problem " + std::to_string(p);
+        const int32_t N = prob_n[p], m = prob_n_exact[p];
+        if (!std::isfinite(prob_ln_n[p])) return fail(NRA_E_ARG, who + ": lnN is not finite");
+        const double* y = values + prob_off[p];
+        for (int32_t i = 1; i < N; ++i)
+            if (i != m && y[i] < y[i - 1]) return fail(NRA_E_ARG, who + ": its values are not ascending within a part");
+        const int32_t* ix = idx + idx_off[(size_t)p];
+        for (int32_t b = 0; b < n_rep; ++b) {
+            const int32_t* row = ix + (int64_t)b * N;
+            int32_t exact = 0;
+            for (int32_t j = 0; j < N; ++j) {
+                if (row[j] < 0 || row[j] >= N) return fail(NRA_E_ARG, who + ": a resampling index is outside its values");
+                if (j > 0 && row[j] < row[j - 1]) return fail(NRA_E_ARG, who + ": a resampling row is not ascending");
+                exact += row[j] < m;
+            }
+            if (rep_m[(int64_t)p * n_rep + b] != exact)
+                return fail(NRA_E_ARG, who + ": rep_m disagrees with the resampling row");
+        }
+        idx_off[(size_t)p + 1] = idx_off[(size_t)p] + (int64_t)n_rep * N;
+    }
+    if (int rc = use_device(device, n_problems > 0)) return rc;
+    if (n_problems == 0) return NRA_OK;
+    try {
+        const size_t np = (size_t)n_problems, slots = 2 * (size_t)max_alleles;
+        // launch groups of whole problems: records and index rows each within the budget, at least one problem
+        const int64_t budget = test_bytes("NRA_TEST_CENS_BOOT_BYTES", (int64_t)1 << 30);
+        const int64_t rec_bytes_of_problem = (int64_t)n_rep * (int64_t)slots * (int64_t)sizeof(NraCensBootRec);
+        DevBuf<char> d_up, d_down;
+        DevBuf<NraCensBootRec> d_recs;
+        std::vector<char> up, down;
+        std::vector<NraCensBootProblem> pr;
+        std::vector<int32_t> jobs;
+        for (size_t p0 = 0; p0 < np;) {
+            size_t p1 = p0;
+            int64_t rec_bytes = 0, idx_bytes = 0, n_val = 0;
+            while (p1 < np) {
+                const int64_t ib = (idx_off[p1 + 1] - idx_off[p1]) * 4;
+                if (p1 > p0 && (rec_bytes + rec_bytes_of_problem > budget || idx_bytes + ib > budget)) break;
+                rec_bytes += rec_bytes_of_problem;
+                idx_bytes += ib;
+                n_val += prob_n[p1];
+                ++p1;
+            }
+            const size_t gp = p1 - p0, gr = gp * (size_t)n_rep, r0 = p0 * (size_t)n_rep;
+            const size_t n_idx = (size_t)(idx_off[p1] - idx_off[p0]);
+            // the problems of the group, their values packed in order; the replicates of one kernel: class -> jobs
+            pr.resize(gp);
+            int64_t o_val = 0;
+            for (size_t p = p0; p < p1; ++p) {
+                pr[p - p0] = NraCensBootProblem{o_val, idx_off[p] - idx_off[p0], prob_tau[p], prob_ln_n[p], prob_n[p],
+                                                prob_n_exact[p]};
+                o_val += prob_n[p];
+            }
+            const int classes[2] = {NRA_CENS_KREG, 0};
+            struct Launch { int kreg; size_t begin, count; };
+            std::vector<Launch> launches;
+            jobs.clear();
+            jobs.reserve(gr);
+            for (int kreg : classes) {
+                const size_t begin = jobs.size();
+                for (size_t p = 0; p < gp; ++p) {
+                    const bool reg = !(flags & NRA_CENS_F_STREAM) && pr[p].n_points <= 64 * NRA_CENS_KREG;
+                    if ((reg ? NRA_CENS_KREG : 0) == kreg)
+                        for (int32_t b = 0; b < n_rep; ++b) jobs.push_back((int32_t)(p * (size_t)n_rep + b));
+                }
+                if (jobs.size() > begin) launches.push_back({kreg, begin, jobs.size() - begin});
+            }
+            // one buffer up: values, problems, idx, rep_m, jobs (8-byte parts first)
+            const size_t b_y = (size_t)n_val * 8, b_pr = gp * sizeof(NraCensBootProblem), b_idx = n_idx * 4, b_m = gr * 4;
+            const size_t o_y = 0, o_pr = o_y + b_y, o_idx = o_pr + b_pr, o_m = o_idx + b_idx, o_jobs = o_m + b_m,
+                         up_bytes = o_jobs + gr * 4;
+            up.assign(up_bytes, 0);
+            for (size_t p = p0; p < p1; ++p)
+                std::memcpy(up.data() + o_y + (size_t)pr[p - p0].off * 8, values + prob_off[p], (size_t)prob_n[p] * 8);
+            std::memcpy(up.data() + o_pr, pr.data(), b_pr);
+            std::memcpy(up.data() + o_idx, idx + idx_off[p0], b_idx);
+            std::memcpy(up.data() + o_m, rep_m + r0, b_m);
+            std::memcpy(up.data() + o_jobs, jobs.data(), gr * 4);
+            // one buffer down: ll, bic, nu, w, then status, n, open, best start, n_iter
+            const size_t q_ll = 0, q_bic = q_ll + gr * 8, q_nu = q_bic + gr * 8,
+                         q_w = q_nu + gr * 8 * NRA_CENS_MAX_COMPONENTS,
+                         q_st = q_w + gr * 8 * (NRA_CENS_MAX_COMPONENTS + 1), q_n = q_st + gr * 4, q_o = q_n + gr * 4,
+                         q_bs = q_o + gr * 4, q_it = q_bs + gr * 4, down_bytes = q_it + gr * 4;
+            NRA_HIP_TRY(d_up.ensure(up_bytes));
+            NRA_HIP_TRY(d_down.ensure(down_bytes));
+            NRA_HIP_TRY(d_recs.ensure(gr * slots));
+            NRA_HIP_TRY((hipError_t)nra_copy_h2d(d_up.p, up.data(), up_bytes));
+            const NraCensBootProblem* g_pr = reinterpret_cast<const NraCensBootProblem*>(d_up.p + o_pr);
+            const int32_t* g_m = reinterpret_cast<const int32_t*>(d_up.p + o_m);
+            for (const Launch& l : launches) {
+                const int e = nra_launch_censored_boot(
+                    nullptr, l.kreg, (int)l.count, reinterpret_cast<const int32_t*>(d_up.p + o_jobs) + l.begin, n_rep,
+                    max_alleles, g_pr, reinterpret_cast<const double*>(d_up.p + o_y),
+                    reinterpret_cast<const int32_t*>(d_up.p + o_idx), g_m, max_iter, tol, d_recs.p);
+                if (e != 0) return fail(NRA_E_DEVICE, std::string("k_censored_boot: ") + hipGetErrorString((hipError_t)e));
+            }
+            const int e = nra_launch_censored_pick(
+                nullptr, (int)gr, n_rep, max_alleles, g_pr, g_m, d_recs.p, reinterpret_cast<int32_t*>(d_down.p + q_st),
+                reinterpret_cast<int32_t*>(d_down.p + q_n), reinterpret_cast<int32_t*>(d_down.p + q_o),
+                reinterpret_cast<int32_t*>(d_down.p + q_bs), reinterpret_cast<int32_t*>(d_down.p + q_it),
+                reinterpret_cast<double*>(d_down.p + q_ll), reinterpret_cast<double*>(d_down.p + q_bic),
+                reinterpret_cast<double*>(d_down.p + q_nu), reinterpret_cast<double*>(d_down.p + q_w));
+            if (e != 0) return fail(NRA_E_DEVICE, std::string("k_censored_pick: ") + hipGetErrorString((hipError_t)e));
+            NRA_HIP_TRY(hipStreamSynchronize(nullptr));
+            down.resize(down_bytes);
+            NRA_HIP_TRY((hipError_t)nra_copy_d2h(down.data(), d_down.p, down_bytes));
+            std::memcpy(ll + r0, down.data() + q_ll, gr * 8);
+            std::memcpy(bic + r0, down.data() + q_bic, gr * 8);
+            std::memcpy(nu + r0 * NRA_CENS_MAX_COMPONENTS, down.data() + q_nu, gr * 8 * NRA_CENS_MAX_COMPONENTS);
+            std::memcpy(w + r0 * (NRA_CENS_MAX_COMPONENTS + 1), down.data() + q_w, gr * 8 * (NRA_CENS_MAX_COMPONENTS + 1));
+            std::memcpy(status + r0, down.data() + q_st, gr * 4);
+            std::memcpy(model_n + r0, down.data() + q_n, gr * 4);
+            std::memcpy(model_open + r0, down.data() + q_o, gr * 4);
+            std::memcpy(best_start + r0, down.data() + q_bs, gr * 4);
+            std::memcpy(n_iter + r0, down.data() + q_it, gr * 4);
+            p0 = p1;
+        }
+    } catch (const std::bad_alloc&) {
+        return fail(NRA_E_NOMEM, "censored bootstrap: host allocation failed");
     }
     return NRA_OK;
 }

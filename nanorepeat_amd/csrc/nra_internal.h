@@ -357,6 +357,24 @@ struct NraCensFit {
     int32_t n_points, n_exact, n, open;
 };
 
+// Bootstrap of the censored fit (k_censored_boot, k_censored_pick).  One problem of a launch
+// group: its n_points sorted values (the first n_exact exact) from double `off` of the value buffer, its replicates'
+// index rows (n_points per replicate) from entry `idx_off`, tau and ln(n_points) as the host computed it
+struct NraCensBootProblem {
+    int64_t off, idx_off;
+    double tau, ln_n;
+    int32_t n_points, n_exact;
+};
+
+// what one wave leaves for (replicate, n, open): fitted = 0 when the replicate does not fit that model; else the best
+// of the three starts.  Entries beyond n (nu) and n + open (w) are not written
+struct NraCensBootRec {
+    double ll;
+    double w[9];             // NRA_CENS_MAX_COMPONENTS + 1: the open weight at n
+    double nu[8];            // NRA_CENS_MAX_COMPONENTS
+    int32_t fitted, start, n_iter, pad;
+};
+
 // Allele consensus (nra_consensus.hip, nra_consensus_host.cpp): banded unit-cost alignment of every tract of a group to
 // the group's backbone, one wave per tract, votes into the group's tables, then a new backbone per group (DESIGN.md
 // section 18).  Band class c: a lane owns c consecutive diagonals, the band holds 64 c.
@@ -512,6 +530,18 @@ int nra_launch_censored_fit(hipStream_t st, int kreg, int n, const int32_t* ids,
                             double* nu, int32_t* iter);
 int nra_launch_censored_resp(hipStream_t st, int n, const NraCensFit* models, const double* values, const double* w,
                              const double* nu, double* resp);
+// bootstrap of the censored fit (nra_censored.hip).  Boot: workgroup g (one wave) runs model (n, open) = slot
+// g % (2 max_alleles) of replicate jobs[g / (2 max_alleles)] (replicate r = problem r / n_rep, row r % n_rep, rep_m[r]
+// exact positions) and writes recs[r * 2 max_alleles + slot]; kreg is NRA_CENS_KREG (every problem of the launch has n_points <= 64 * kreg
+// and its replicates' values are staged in LDS) or 0 = streaming.  Pick: one lane per
+// replicate 0 .. n_replicates - 1 reads its records and writes its outputs (nu: 8 per replicate, w: 9)
+int nra_launch_censored_boot(hipStream_t st, int kreg, int n_jobs, const int32_t* jobs, int n_rep, int max_alleles,
+                             const NraCensBootProblem* probs, const double* values, const int32_t* idx,
+                             const int32_t* rep_m, int max_iter, double tol, NraCensBootRec* recs);
+int nra_launch_censored_pick(hipStream_t st, int n_replicates, int n_rep, int max_alleles,
+                             const NraCensBootProblem* probs, const int32_t* rep_m, const NraCensBootRec* recs,
+                             int32_t* status, int32_t* model_n, int32_t* model_open, int32_t* best_start,
+                             int32_t* n_iter, double* ll, double* bic, double* nu, double* w);
 
 // copies between pageable host memory and the device through the calling thread's pinned stage (nra_host.cpp);
 // they return a hipError_t

@@ -197,7 +197,7 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
                       switch_cost=None, read_alignments=False, discover_periods=False, in_repeat_reads=False,
                       bootstrap=0, bootstrap_confidence=0.95, flank_phase=False, flank_len=3000, flank_skip=20,
                       flank_min_sites=2, censored_fit=False, censored_error_rate=None, censored_max_alleles=6,
-                      **engines):
+                      censored_bootstrap=0, **engines):
     """The BAM command from files to files (nanoRepeat_bam.py:614-751): for every region of the BED
     file, reads from the alignment file -> `<out_prefix>.details/<chr>/<region>.*` ->
     `<out_prefix>.NanoRepeat_output.tsv`.  The reference forks up to 16 workers, one region each;
@@ -229,6 +229,11 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
     (censored.py): the spanning reads' sizes and the bounds of the one-anchor and in-repeat reads in one mixture
     likelihood, with an open allele where no read spans one; censored_error_rate is its sd in the log domain (None: the
     data type's error rate) and censored_max_alleles the largest number of closed alleles it tries.
+    censored_bootstrap=B > 0 (with censored_fit=True, else ValueError; independent of `mixture`) adds the bootstrap of
+    that fit: B resamples of every region's spanning reads and bounds, their model searches in
+    one GPU call, `<region>.censored_bootstrap.tsv` and `<out_prefix>.NanoRepeat_censored_bootstrap.tsv` with the share
+    of replicates that give the called model and an open allele and a bootstrap_confidence interval for every called
+    allele's size and weight (censored_engine may carry `censored_bootstrap` as a stand-in for the call).
     `engines` may carry aligner / scorer / structure_engine / motif_engine / extension_engine / mixture_engine /
     consensus_engine / split_engine / segment_engine / path_aligner / period_engine / bootstrap_engine / flank_engine /
     censored_engine stand-ins.  Returns the regions."""
@@ -237,6 +242,7 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
     _check_bootstrap(bootstrap, mixture)
     censored = _censored_options(censored_fit, censored_error_rate, censored_max_alleles, partial_reads,
                                  in_repeat_reads)
+    _check_censored_bootstrap(censored_bootstrap, censored_fit)
     regions = nr_io.read_repeat_region_file(repeat_region_bed, no_details)
     ref_fasta_dict = nr_io.fasta_file2dict(ref_fasta)
     live, reads_of = [], []
@@ -257,7 +263,7 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
                         partial_reads, mixture, allele_consensus, allele_split,
                         _run_options(motif_runs, segment_motifs, switch_cost), read_alignments, discover_periods,
                         in_repeat_reads=in_repeat_reads, bootstrap=(bootstrap, bootstrap_confidence), flank=flank,
-                        censored=censored)
+                        censored=censored, censored_bootstrap=censored_bootstrap)
     return regions
 
 
@@ -307,12 +313,19 @@ def _censored_options(censored_fit, error_rate, max_alleles, partial_reads, in_r
                 use_in_repeat=bool(in_repeat_reads))
 
 
+def _check_censored_bootstrap(censored_bootstrap, censored_fit):
+    if isinstance(censored_bootstrap, bool) or censored_bootstrap < 0 or int(censored_bootstrap) != censored_bootstrap:
+        raise ValueError(f"censored_bootstrap must be a number of replicates >= 0, not {censored_bootstrap!r}")
+    if censored_bootstrap and not censored_fit:
+        raise ValueError("censored_bootstrap > 0 needs censored_fit=True: it resamples the reads of that fit")
+
+
 def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
                         read_structure=False, motif_options=None, partial_reads=False, mixture="sklearn",
                         allele_consensus=False, allele_split=False, run_options=None, read_alignments=False,
                         discover_periods=False, in_repeat_reads=False, candidates=None, bootstrap=(0, 0.95), flank=None,
-                        censored=None):
+                        censored=None, censored_bootstrap=0):
     """The commands' common tail: steps 1-4 for the regions with reads, then one TSV row per BED region; with
     read_structure, the structure of every read with a size and the two structure files; with motif_options (a dict
     of motifs.motif_regions keywords), the tandem motifs of every read with a core and the two motif files; with
@@ -332,7 +345,9 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
     With `flank` (a dict of flank.flank_regions keywords), the flank haplotypes of every region with reads (one-anchor
     reads too when partial_reads is on), the two flank files and a NOTICE per region with an unspanned haplotype.
     With `censored` (a dict of censored.censored_regions keywords), after the one-anchor and in-repeat reads: the
-    censored allele fit of every region with reads or candidates, its three files and one NOTICE."""
+    censored allele fit of every region with reads or candidates, its three files and one NOTICE; with
+    censored_bootstrap (replicates) > 0 then the bootstrap of that fit (confidence: bootstrap[1]; the streams are named
+    by `seed`, a fresh one when it is None), its two files and one NOTICE."""
     if in_repeat_reads:
         for region in live:
             region.keep_no_anchor_reads = True
@@ -392,6 +407,16 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
                 nr_censored.write_censored_reads(region)
             nr_censored.write_censored_summary(regions, out_prefix)
             nr_censored.report_censored_calls(of)
+            if censored_bootstrap:
+                from . import mixture as nr_mixture
+                stand_in = engines.get("censored_engine")
+                nr_censored.bootstrap_regions(
+                    of, int(censored_bootstrap), nr_mixture.fresh_seed() if seed is None else seed, bootstrap[1],
+                    censored["max_alleles"], stand_in if hasattr(stand_in, "censored_bootstrap") else None, device)
+                for region in of:
+                    nr_censored.write_censored_bootstrap(region)
+                nr_censored.write_censored_bootstrap_summary(regions, out_prefix)
+                nr_censored.report_censored_bootstrap(of)
     if allele_consensus:
         from . import consensus
         consensus.consensus_regions(live, device=device, engine=engines.get("consensus_engine"),
@@ -457,7 +482,7 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         discover_periods=False, partial_reads=False, in_repeat_reads=False, motif_share_pct=5,
                         bootstrap=0, bootstrap_confidence=0.95, flank_phase=False, flank_len=3000, flank_skip=20,
                         flank_min_sites=2, censored_fit=False, censored_error_rate=None, censored_max_alleles=6,
-                        **engines):
+                        censored_bootstrap=0, **engines):
     """The FASTQ / FASTA command (nanoRepeat.py:109, `-t fastq|fasta`) from files to files, without a genome mapper:
     the reads each region sees are chosen by the anchor k-mer screen (screen.reads_by_region) instead of a
     genome-wide mapping and a BAM window, then the BAM command's steps run unchanged.  Every region's reference
@@ -474,8 +499,8 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
     23) offers the reads with one anchor only and the reads made of a region's motif (at least motif_share_pct % of
     their k-mer windows) as candidates, written to `<region>.partial_candidates.fastq`; they go through the anchor step
     apart from the region's reads and never reach the sizes or the phasing.  bootstrap=B > 0 (with mixture="gpu")
-    adds the bootstrap files, flank_phase=True the flank haplotype files and censored_fit=True the censored allele fit,
-    as for quantify_from_bam.
+    adds the bootstrap files, flank_phase=True the flank haplotype files, censored_fit=True the censored allele fit
+    and censored_bootstrap=B > 0 its bootstrap files, as for quantify_from_bam.
     `engines` may carry aligner / scorer / screener / structure_engine / motif_engine / extension_engine /
     mixture_engine / consensus_engine / split_engine / segment_engine / path_aligner / period_engine /
     bootstrap_engine / flank_engine / censored_engine stand-ins.  Returns the regions."""
@@ -484,6 +509,7 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
     _check_bootstrap(bootstrap, mixture)
     censored = _censored_options(censored_fit, censored_error_rate, censored_max_alleles, partial_reads,
                                  in_repeat_reads)
+    _check_censored_bootstrap(censored_bootstrap, censored_fit)
     regions = nr_io.read_repeat_region_file(repeat_region_bed, no_details)
     ref_fasta_dict = nr_io.fasta_file2dict(ref_fasta)
     screened = []
@@ -523,7 +549,8 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         run_options=_run_options(motif_runs, segment_motifs, switch_cost),
                         read_alignments=read_alignments, discover_periods=discover_periods,
                         partial_reads=partial_reads, in_repeat_reads=in_repeat_reads, candidates=candidates,
-                        bootstrap=(bootstrap, bootstrap_confidence), flank=flank, censored=censored)
+                        bootstrap=(bootstrap, bootstrap_confidence), flank=flank, censored=censored,
+                        censored_bootstrap=censored_bootstrap)
     return regions
 
 
