@@ -896,6 +896,54 @@ int nra_tract_segments(int device, int32_t n_sets, const int32_t* set_motif_off,
                        const int32_t* tract_set, int32_t switch_cost, int32_t* edits, int32_t* start_phase,
                        int32_t* start_motif, uint8_t* path, uint8_t* motif_of);
 
+/* ---- CpG methylation per read: the MM/ML calls of a read, counted over its tract and flanks (no counterpart in the
+ * reference)
+ *
+ * All of it is integer arithmetic; the result of a read does not depend on the other reads of the call or their order.
+ *
+ * The sequenced strand.  A read has the stored bytes S[0..n) and the flag bits 0 (stored reversed: the record holds the
+ * reverse complement of what was sequenced) and 1 (implicit: a C the list skips is unmodified).  The sequenced strand
+ * is O: O[i] = S[i] without bit 0, O[i] = comp(S[n-1-i]) with it.  Case is ignored; every byte other than A, C, G, T
+ * is "other" and is its own complement.
+ *
+ * Ranks.  n_c = the number of C in O.  The read's list is m deltas d_0 .. d_{m-1} (>= 0) and m call bytes; the listed
+ * ranks are L_j = j + d_0 + ... + d_j, 0-based among the C of O (summed in 64 bits: they do not wrap).  If m > 0 and
+ * L_{m-1} >= n_c, the read's status is NRA_METH_BAD_TAG and all its counters are 0; a read with m > n has that status
+ * without being decoded.  Otherwise the status is NRA_METH_OK.
+ *
+ * Sites and calls.  A site is a stored index s, 0 <= s < n - 1, with S[s] = C and S[s+1] = G: the same set whichever
+ * strand was sequenced.  Its C on the sequenced strand is O[s] without bit 0 and O[n-2-s] with it; r is that C's rank.
+ * The site's call is probs[j] if r = L_j; byte 0 if r is not listed and bit 1 is set; none otherwise.
+ *
+ * Segments.  nb = ceil(flank / bin); a read has 2 nb + 1 segments, in this order: before[0..nb), tract, after[0..nb).
+ * A site is in the tract when tract_lo <= s and s + 2 <= tract_hi; in before[(tract_lo - s - 2) / bin] when
+ * s + 2 <= tract_lo and tract_lo - s - 2 < flank; in after[(s - tract_hi) / bin] when s >= tract_hi and
+ * s - tract_hi < flank.  A site with one base on either side of a tract edge, or farther out than `flank`, is in no
+ * segment.  Bin 0 is the one next to the repeat.  "Before" and "after" are in stored coordinates: which of them is the
+ * reference's left side is the caller's business.
+ *
+ * Counters per segment, five int32 in this order: sites, called (sites with a call), meth (call >= hi_byte), unmeth
+ * (call <= lo_byte), sum (of the call bytes).  DESIGN.md section 28. */
+#define NRA_METH_OK        0
+#define NRA_METH_BAD_TAG   1
+#define NRA_METH_MAX_N     4000000   /* bases of a read: whole reads go in, not cores (the target limit of nra_align_pairs) */
+#define NRA_METH_MAX_FLANK 100000
+#define NRA_METH_MAX_BINS  64
+#define NRA_METH_COUNTERS  5
+
+/* read r = bytes [seq_off[r], seq_off[r+1]) of `seqs` (any case); its list = entries [mod_off[r], mod_off[r+1]) of
+ * `deltas` and `probs`; flags[r] bits 0 and 1 as above (other bits: NRA_E_ARG); its tract = stored [tract_lo[r],
+ * tract_hi[r]), 0 <= lo <= hi <= n.  Writes counts[(r * (2 nb + 1) + segment) * 5 + counter], n_c[r] and status[r].
+ * A read of more than 4 000 000 bases, flank > 100 000 or more than 64 bins is NRA_E_RANGE; a negative delta, offsets
+ * that decrease, a tract outside 0 <= lo <= hi <= n, a NULL array with n_reads > 0, flank or bin below 1, bin > flank,
+ * or bytes outside 0 <= lo_byte < hi_byte <= 255 are NRA_E_ARG.  Arguments are checked before the device is touched;
+ * n_reads = 0 writes nothing. */
+int nra_read_methylation(int device, int32_t n_reads, const char* seqs, const int64_t* seq_off,
+                         const int32_t* deltas, const uint8_t* probs, const int64_t* mod_off,
+                         const uint8_t* flags, const int32_t* tract_lo, const int32_t* tract_hi,
+                         int32_t flank, int32_t bin, int32_t lo_byte, int32_t hi_byte,
+                         int32_t* counts, int32_t* n_c, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,7 +40,7 @@ EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count
            "nra_screen_set_motifs", "nra_screen_reads_partial",
            "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts", "nra_mixture_fit", "nra_mixture_bootstrap",
            "nra_tract_consensus", "nra_allele_split", "nra_flank_phase", "nra_tract_segments", "nra_tract_periods",
-           "nra_censored_fit", "nra_censored_posteriors", "nra_censored_bootstrap")
+           "nra_censored_fit", "nra_censored_posteriors", "nra_censored_bootstrap", "nra_read_methylation")
 
 
 E_RANGE = -3      # NRA_E_RANGE
@@ -229,6 +229,9 @@ def load():
     lib.nra_tract_segments.restype = C.c_int
     lib.nra_tract_segments.argtypes = [C.c_int, C.c_int32, pi32, C.c_char_p, pi64, C.c_int32, C.c_char_p, pi64, pi32,
                                        C.c_int32, pi32, pi32, pi32, p8, p8]
+    lib.nra_read_methylation.restype = C.c_int
+    lib.nra_read_methylation.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, pi32, p8, pi64, p8, pi32, pi32,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, pi32, pi32, pi32]
     lib.nra_tract_periods.restype = C.c_int
     lib.nra_tract_periods.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, C.c_int32, pi32, pi32]
     _LIB = lib
@@ -797,6 +800,37 @@ def tract_periods(tracts, max_period=64, device=0):
     out = dict(match=np.zeros((n, max(max_period, 0)), np.int32), valid=np.zeros((n, max(max_period, 0)), np.int32))
     _check(lib.nra_tract_periods(device, n, data, _ptr(off, C.c_int64), max_period, _ptr(out["match"], C.c_int32),
                                  _ptr(out["valid"], C.c_int32)))
+    return out
+
+
+def read_methylation(reads, mods, flags, tract_lo, tract_hi, flank=2000, bin=200, lo_byte=63, hi_byte=192, device=0):
+    """nra_read_methylation: the CpG calls of every read counted over its tract and flank bins.  reads: the stored
+    sequences; mods[i] = (deltas, probs) of read i's list; flags[i]: bit 0 stored reversed, bit 1 implicit; the tract
+    of read i is stored [tract_lo[i], tract_hi[i]).  -> dict(counts int32 [n, 2 nb + 1, 5] with nb = ceil(flank / bin)
+    and the segments before[0..nb), tract, after[0..nb), n_c [n], status [n])."""
+    lib = load()
+    data, off = pack_reads(list(reads))
+    n = len(off) - 1
+    if not (len(mods) == len(flags) == len(tract_lo) == len(tract_hi) == n):
+        raise ValueError("one list, flag byte and tract per read")
+    mod_off = np.zeros(n + 1, np.int64)
+    mod_off[1:] = np.cumsum([len(d) for d, _ in mods])
+    if any(len(d) != len(p) for d, p in mods):
+        raise ValueError("one call byte per delta")
+    deltas = np.ascontiguousarray(np.concatenate([np.asarray(d, np.int32) for d, _ in mods] or
+                                                 [np.zeros(0, np.int32)]), np.int32)
+    probs = np.ascontiguousarray(np.concatenate([np.asarray(p, np.uint8) for _, p in mods] or
+                                                [np.zeros(0, np.uint8)]), np.uint8)
+    flags = np.ascontiguousarray(flags, np.uint8)
+    lo, hi = np.ascontiguousarray(tract_lo, np.int32), np.ascontiguousarray(tract_hi, np.int32)
+    nb = (flank + bin - 1) // bin if flank >= 1 and bin >= 1 else 0
+    out = dict(counts=np.zeros((n, 2 * min(nb, 64) + 1, 5), np.int32), n_c=np.zeros(n, np.int32),
+               status=np.zeros(n, np.int32))
+    _check(lib.nra_read_methylation(device, n, data, _ptr(off, C.c_int64), _ptr(deltas, C.c_int32),
+                                    _ptr(probs, C.c_uint8), _ptr(mod_off, C.c_int64), _ptr(flags, C.c_uint8),
+                                    _ptr(lo, C.c_int32), _ptr(hi, C.c_int32), flank, bin, lo_byte, hi_byte,
+                                    _ptr(out["counts"], C.c_int32), _ptr(out["n_c"], C.c_int32),
+                                    _ptr(out["status"], C.c_int32)))
     return out
 
 

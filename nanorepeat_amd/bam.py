@@ -19,11 +19,48 @@ class BamRecord:
     """The fields `extract_fastq_from_bam` reads, named as pysam names them."""
 
     __slots__ = ("query_name", "query_sequence", "query_qualities", "reference_id", "reference_start",
-                 "reference_end", "flag")
+                 "reference_end", "flag", "tags", "hard_clipped")
 
-    def __init__(self, query_name, query_sequence, query_qualities, reference_id, reference_start, reference_end, flag):
+    def __init__(self, query_name, query_sequence, query_qualities, reference_id, reference_start, reference_end, flag,
+                 tags=None, hard_clipped=False):
         self.query_name, self.query_sequence, self.query_qualities = query_name, query_sequence, query_qualities
         self.reference_id, self.reference_start, self.reference_end, self.flag = reference_id, reference_start, reference_end, flag
+        self.tags, self.hard_clipped = tags, hard_clipped          # tags: None unless the file parses them (parse_tags)
+
+
+_TAG_SIZES = {"A": 1, "c": 1, "C": 1, "s": 2, "S": 2, "i": 4, "I": 4, "f": 4}
+_TAG_INTS = {"c": "<b", "C": "<B", "s": "<h", "S": "<H", "i": "<i", "I": "<I"}
+_CIGAR_HARD_CLIP = 5
+
+
+def parse_mod_tags(block, p):
+    """The base modification tags among a record's optional fields (block[p:]) -> {"MM": text, "ML": bytes, "MN": int},
+    each only when present (`Mm` / `Ml`, the earlier spelling, count as MM / ML).  Every field type is stepped over by
+    its size: A c C s S i I f, Z and H (to the NUL), B (a subtype of c C s S i I f and a count)."""
+    tags, end = {}, len(block)
+    while p + 3 <= end:
+        key, typ = block[p:p + 2].decode("latin-1"), chr(block[p + 2])
+        p += 3
+        if typ in _TAG_SIZES:
+            if key == "MN" and typ in _TAG_INTS:
+                tags["MN"] = struct.unpack_from(_TAG_INTS[typ], block, p)[0]
+            p += _TAG_SIZES[typ]
+        elif typ in "ZH":
+            q = block.index(b"\x00", p)
+            if typ == "Z" and key in ("MM", "Mm"):
+                tags["MM"] = block[p:q].decode("latin-1")
+            p = q + 1
+        elif typ == "B":
+            sub, count = chr(block[p]), struct.unpack_from("<i", block, p + 1)[0]
+            if sub not in _TAG_SIZES or sub == "A":
+                raise ValueError(f"BAM record with an array tag of unknown subtype {sub!r}")
+            p += 5
+            if sub == "C" and key in ("ML", "Ml"):
+                tags["ML"] = bytes(block[p:p + count])
+            p += count * _TAG_SIZES[sub]
+        else:
+            raise ValueError(f"BAM record with a tag of unknown type {typ!r}")
+    return tags
 
 
 class BgzfReader:
@@ -103,6 +140,7 @@ class BamFile:
             self.lengths.append(struct.unpack("<i", self._bgzf.read(4))[0])
         self._linear = self._read_bai()
         self._first_record_known = False
+        self.parse_tags = False          # True: records carry their MM / ML / MN tags and whether they are hard-clipped
 
     def close(self):
         self._bgzf.close()
@@ -138,16 +176,19 @@ class BamFile:
             ref_id, pos, l_read_name, _mapq, _bin, n_cigar, flag, l_seq = struct.unpack_from("<iiBBHHHi", block, 0)
             p = 32
             name = block[p:p + l_read_name - 1].decode(); p += l_read_name
-            ref_len = 0
+            ref_len, hard_clipped = 0, False
             for v in struct.unpack_from(f"<{n_cigar}I", block, p):
                 if _CIGAR_REF[v & 15 if (v & 15) < 9 else 1]:
                     ref_len += v >> 4
+                hard_clipped = hard_clipped or (v & 15) == _CIGAR_HARD_CLIP
             p += 4 * n_cigar
             packed = block[p:p + (l_seq + 1) // 2]; p += (l_seq + 1) // 2
             seq = "".join(_SEQ_CODES[b >> 4] + _SEQ_CODES[b & 15] for b in packed)[:l_seq]
             qual = block[p:p + l_seq]
             quals = None if (l_seq == 0 or qual[0] == 0xff) else list(qual)
-            yield BamRecord(name, seq if l_seq else None, quals, ref_id, pos, pos + max(ref_len, 1), flag)
+            tags = parse_mod_tags(block, p + l_seq) if self.parse_tags else None
+            yield BamRecord(name, seq if l_seq else None, quals, ref_id, pos, pos + max(ref_len, 1), flag, tags,
+                            hard_clipped)
 
     def fetch(self, contig, start, stop):
         """Records overlapping [start, stop) of `contig`, in file order (the file must be sorted)."""
@@ -186,15 +227,41 @@ def open_alignment_file(in_bam_file, ref_fasta=None):
     return BamFile(in_bam_file)
 
 
-def extract_fastq_from_bam(in_bam_file, repeat_region, flank_dist, out_fastq_file, ref_fasta=None):
+def record_mod_tags(read):
+    """(mm_text, ml_bytes, stored_reversed, usable) of a record, ours (parse_tags) or pysam's (has_tag / get_tag,
+    is_reverse, cigartuples); text and bytes are None where the tag is absent.  `usable` is False when the record is
+    hard-clipped or carries MN different from the length of its sequence: MM then counts bases the record lacks."""
+    if isinstance(read, BamRecord):
+        tags = read.tags or {}
+        mm, ml, mn = tags.get("MM"), tags.get("ML"), tags.get("MN")
+        reverse, hard = bool(read.flag & 0x10), read.hard_clipped
+    else:
+        def tag(*keys):
+            for k in keys:
+                if read.has_tag(k):
+                    return read.get_tag(k)
+            return None
+        mm, ml, mn = tag("MM", "Mm"), tag("ML", "Ml"), tag("MN")
+        if ml is not None:
+            ml = bytes(bytearray(ml))
+        reverse = bool(read.is_reverse)
+        hard = any(op == _CIGAR_HARD_CLIP for op, _ in (read.cigartuples or ()))
+    usable = not hard and (mn is None or int(mn) == len(read.query_sequence))
+    return mm, ml, reverse, usable
+
+
+def extract_fastq_from_bam(in_bam_file, repeat_region, flank_dist, out_fastq_file, ref_fasta=None, mod_tags=None):
     """nanoRepeat_bam.py:576-600: every read overlapping the region +- flank_dist, once (first
     record of a name wins), sequence as stored; missing qualities become '.' (Phred 13).
-    Returns the number of reads written."""
+    Returns the number of reads written.  `mod_tags`: a dict that receives {read_name: record_mod_tags(record)} of
+    the records written (None: tags are not looked at)."""
     quality_shift = 33
     assert flank_dist >= 0
     start_pos = max(0, repeat_region.start_pos - flank_dist)
     end_pos = repeat_region.end_pos + flank_dist
     bam = open_alignment_file(in_bam_file, ref_fasta)
+    if mod_tags is not None and isinstance(bam, BamFile):
+        bam.parse_tags = True
     written = set()
     try:
         with open(out_fastq_file, "w") as fastq:
@@ -207,6 +274,8 @@ def extract_fastq_from_bam(in_bam_file, repeat_region, flank_dist, out_fastq_fil
                     quals = chr(quality_shift + 13) * len(read.query_sequence)
                 fastq.write(f"@{read.query_name}\n{read.query_sequence}\n+\n{quals}\n")
                 written.add(read.query_name)
+                if mod_tags is not None:
+                    mod_tags[read.query_name] = record_mod_tags(read)
     finally:
         bam.close()
     return len(written)

@@ -584,6 +584,28 @@ int nra_launch_tract_motifs(hipStream_t st, int n_grid, int n_tracts, const NraM
 int nra_launch_tract_periods(hipStream_t st, int n_grid, int n_tracts, const NraPeriodTract* tracts,
                              const uint8_t* codes, int32_t* match, int32_t* valid);
 
+// CpG methylation (nra_methyl.hip, nra_methyl_host.cpp): one workgroup of 256 threads per read.
+#define NRA_METH_THREADS 256
+#define NRA_METH_F_REVERSED 1                 // bit 0 of a read's flags: stored reversed
+#define NRA_METH_F_IMPLICIT 2                 // bit 1: a C the list skips is unmodified
+#define NRA_METH_F_TOO_MANY 4                 // set by the host: m > n, BAD_TAG without being decoded
+// one read of a launch: its bytes start at byte `seq` of the chunk's sequence buffer, its list at entry `mod` of the
+// chunk's deltas (overwritten by the ranks L) and call bytes; its result is row `out` of the chunk's results
+struct NraMethRead {
+    uint64_t seq;
+    uint64_t mod;
+    int32_t n;
+    int32_t m;
+    int32_t lo;
+    int32_t hi;
+    int32_t flags;
+    int32_t pad;
+};
+// n_grid workgroups stride over the reads.  counts[r][2 nb + 1][5], n_c[r], status[r]; ranks: the deltas, in place
+int nra_launch_read_methylation(hipStream_t st, int n_grid, int n_reads, const NraMethRead* reads, const uint8_t* seqs,
+                                int32_t* ranks, const uint8_t* probs, int flank, int bin, int nb, int lo_byte,
+                                int hi_byte, int32_t* counts, int32_t* n_c, int32_t* status);
+
 // launchers (nra_kernels.hip).  All asynchronous on `st`; return hipError_t as int.
 int nra_launch_score_pk16(int R, int has_n, hipStream_t st, int n_tasks,
                           const NraPairTask* tasks, const NraDevRead* reads,

@@ -59,6 +59,33 @@ def read_fastq(fastq_file):
     return reads
 
 
+def read_fastq_mod_tags(fastq_file):
+    """{read_name: (mm_text, ml_bytes, stored_reversed, usable)} from the header comments of a FASTQ file: the tab- or
+    space-separated `MM:Z:...`, `ML:B:C,...` and `MN:i:...` that `samtools fastq -T MM,ML` writes (`Mm` / `Ml` too).
+    A FASTQ record is the read as sequenced, so stored_reversed is False; `usable` is False where MN differs from the
+    length of the sequence.  Reads without such comments are left out; the first record of a name wins."""
+    tags = dict()
+    with gzopen(fastq_file) as fp:
+        while True:
+            l1, l2, l3, l4 = fp.readline(), fp.readline(), fp.readline(), fp.readline()
+            if not l1 or not l2 or not l3 or not l4:
+                break
+            words = l1.strip()[1:].split()
+            if not words or words[0] in tags:
+                continue
+            mm = ml = mn = None
+            for w in words[1:]:
+                if w[:5] in ("MM:Z:", "Mm:Z:"):
+                    mm = w[5:]
+                elif w[:7] in ("ML:B:C,", "Ml:B:C,") or w in ("ML:B:C", "Ml:B:C"):
+                    ml = bytes(int(x) for x in w[7:].split(",") if x)
+                elif w[:5] == "MN:i:":
+                    mn = int(w[5:])
+            if mm is not None or ml is not None:
+                tags[words[0]] = (mm, ml, False, mn is None or mn == len(l2.strip()))
+    return tags
+
+
 def iter_reads(path, chunk_bases=1 << 28):
     """Reads of a FASTQ or FASTA file (gzip-aware) as chunks of (names, seqs, quals) lists of about `chunk_bases`
     bases each (a chunk ends at the first record that reaches it).  The format is the first record's: `@` FASTQ

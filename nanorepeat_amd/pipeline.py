@@ -197,7 +197,8 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
                       switch_cost=None, read_alignments=False, discover_periods=False, in_repeat_reads=False,
                       bootstrap=0, bootstrap_confidence=0.95, flank_phase=False, flank_len=3000, flank_skip=20,
                       flank_min_sites=2, censored_fit=False, censored_error_rate=None, censored_max_alleles=6,
-                      censored_bootstrap=0, **engines):
+                      censored_bootstrap=0, methylation=False, meth_flank=2000, meth_bin=200, meth_hi=192, meth_lo=63,
+                      meth_mod_code="m", **engines):
     """The BAM command from files to files (nanoRepeat_bam.py:614-751): for every region of the BED
     file, reads from the alignment file -> `<out_prefix>.details/<chr>/<region>.*` ->
     `<out_prefix>.NanoRepeat_output.tsv`.  The reference forks up to 16 workers, one region each;
@@ -234,21 +235,28 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
     one GPU call, `<region>.censored_bootstrap.tsv` and `<out_prefix>.NanoRepeat_censored_bootstrap.tsv` with the share
     of replicates that give the called model and an open allele and a bootstrap_confidence interval for every called
     allele's size and weight (censored_engine may carry `censored_bootstrap` as a stand-in for the call).
+    methylation=True adds the CpG methylation files (methylation.py): the 5mC calls of the records' MM / ML tags
+    (modification code meth_mod_code) counted per read and per allele over the repeat tract and over the meth_flank read
+    bases on either side of it in bins of meth_bin; a call byte >= meth_hi counts as methylated, one <= meth_lo as
+    unmethylated.
     `engines` may carry aligner / scorer / structure_engine / motif_engine / extension_engine / mixture_engine /
     consensus_engine / split_engine / segment_engine / path_aligner / period_engine / bootstrap_engine / flank_engine /
-    censored_engine stand-ins.  Returns the regions."""
+    censored_engine / methylation_engine stand-ins.  Returns the regions."""
     from . import bam as nr_bam, mixture as nr_mixture
     nr_mixture.check_engine_name(mixture)
     _check_bootstrap(bootstrap, mixture)
+    meth = _methylation_options(methylation, meth_flank, meth_bin, meth_hi, meth_lo, meth_mod_code)
     censored = _censored_options(censored_fit, censored_error_rate, censored_max_alleles, partial_reads,
                                  in_repeat_reads)
     _check_censored_bootstrap(censored_bootstrap, censored_fit)
     regions = nr_io.read_repeat_region_file(repeat_region_bed, no_details)
     ref_fasta_dict = nr_io.fasta_file2dict(ref_fasta)
-    live, reads_of = [], []
+    live, reads_of, tags_of = [], [], []
     for i, region in enumerate(regions):
         _set_region_paths(region, i, out_prefix)
-        n = nr_bam.extract_fastq_from_bam(in_bam_file, region, anchor_len, region.region_fq_file, ref_fasta)
+        tags = {} if meth is not None else None
+        n = nr_bam.extract_fastq_from_bam(in_bam_file, region, anchor_len, region.region_fq_file, ref_fasta,
+                                          **({} if tags is None else dict(mod_tags=tags)))
         if n == 0:
             continue
         nr_io.extract_ref_sequence(ref_fasta_dict, region, anchor_len)
@@ -256,6 +264,9 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
             continue
         live.append(region)
         reads_of.append(nr_io.read_fastq(region.region_fq_file))
+        tags_of.append(tags)
+    if meth is not None:
+        meth["tags_of"] = tags_of
     flank = _flank_options(flank_phase, flank_len, flank_skip, flank_min_sites, regions, ref_fasta_dict)
     _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
@@ -263,7 +274,7 @@ def quantify_from_bam(in_bam_file, ref_fasta, repeat_region_bed, out_prefix, dat
                         partial_reads, mixture, allele_consensus, allele_split,
                         _run_options(motif_runs, segment_motifs, switch_cost), read_alignments, discover_periods,
                         in_repeat_reads=in_repeat_reads, bootstrap=(bootstrap, bootstrap_confidence), flank=flank,
-                        censored=censored, censored_bootstrap=censored_bootstrap)
+                        censored=censored, censored_bootstrap=censored_bootstrap, methylation=meth)
     return regions
 
 
@@ -298,6 +309,15 @@ def _flank_options(flank_phase, flank_len, flank_skip, flank_min_sites, regions,
     return dict(flank_len=flank_len, skip=flank_skip, min_sites=flank_min_sites)
 
 
+def _methylation_options(methylation, flank, bin_len, hi, lo, mod_code):
+    """None, or the keywords of methylation.methylation_regions (the commands add `tags_of`)."""
+    if not methylation:
+        return None
+    from . import methylation as nr_methylation
+    nr_methylation.check_options(flank, bin_len, hi, lo, mod_code)
+    return dict(flank=flank, bin_len=bin_len, hi=hi, lo=lo, mod_code=mod_code)
+
+
 def _censored_options(censored_fit, error_rate, max_alleles, partial_reads, in_repeat_reads):
     """None, or the keywords of censored.censored_regions."""
     if not censored_fit:
@@ -325,7 +345,7 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
                         read_structure=False, motif_options=None, partial_reads=False, mixture="sklearn",
                         allele_consensus=False, allele_split=False, run_options=None, read_alignments=False,
                         discover_periods=False, in_repeat_reads=False, candidates=None, bootstrap=(0, 0.95), flank=None,
-                        censored=None, censored_bootstrap=0):
+                        censored=None, censored_bootstrap=0, methylation=None):
     """The commands' common tail: steps 1-4 for the regions with reads, then one TSV row per BED region; with
     read_structure, the structure of every read with a size and the two structure files; with motif_options (a dict
     of motifs.motif_regions keywords), the tandem motifs of every read with a core and the two motif files; with
@@ -347,7 +367,9 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
     With `censored` (a dict of censored.censored_regions keywords), after the one-anchor and in-repeat reads: the
     censored allele fit of every region with reads or candidates, its three files and one NOTICE; with
     censored_bootstrap (replicates) > 0 then the bootstrap of that fit (confidence: bootstrap[1]; the streams are named
-    by `seed`, a fresh one when it is None), its two files and one NOTICE."""
+    by `seed`, a fresh one when it is None), its two files and one NOTICE.  With `methylation` (a dict of
+    methylation.methylation_regions keywords and `tags_of`, the tags of every region with reads), the CpG counters of
+    every read with a size, the three methylation files and one NOTICE counting the reads without usable calls."""
     if in_repeat_reads:
         for region in live:
             region.keep_no_anchor_reads = True
@@ -467,6 +489,15 @@ def _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mod
             nr_flank.write_flank_phase(region)
         nr_flank.write_flank_summary(regions, out_prefix)
         nr_flank.report_unspanned_haplotypes(flank_of)
+    if methylation is not None:
+        from . import methylation as nr_methylation
+        options = dict(methylation)
+        nr_methylation.methylation_regions(live, reads_of, options.pop("tags_of"), device=device,
+                                           engine=engines.get("methylation_engine"), **options)
+        for region in live:
+            nr_methylation.write_read_methylation(region)
+            nr_methylation.write_allele_methylation(region)
+        nr_methylation.write_methylation_summary(regions, out_prefix)
     if no_details:
         import shutil
         shutil.rmtree(f"{out_prefix}.details", ignore_errors=True)
@@ -482,7 +513,8 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         discover_periods=False, partial_reads=False, in_repeat_reads=False, motif_share_pct=5,
                         bootstrap=0, bootstrap_confidence=0.95, flank_phase=False, flank_len=3000, flank_skip=20,
                         flank_min_sites=2, censored_fit=False, censored_error_rate=None, censored_max_alleles=6,
-                        censored_bootstrap=0, **engines):
+                        censored_bootstrap=0, methylation=False, meth_flank=2000, meth_bin=200, meth_hi=192,
+                        meth_lo=63, meth_mod_code="m", **engines):
     """The FASTQ / FASTA command (nanoRepeat.py:109, `-t fastq|fasta`) from files to files, without a genome mapper:
     the reads each region sees are chosen by the anchor k-mer screen (screen.reads_by_region) instead of a
     genome-wide mapping and a BAM window, then the BAM command's steps run unchanged.  Every region's reference
@@ -500,13 +532,16 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
     their k-mer windows) as candidates, written to `<region>.partial_candidates.fastq`; they go through the anchor step
     apart from the region's reads and never reach the sizes or the phasing.  bootstrap=B > 0 (with mixture="gpu")
     adds the bootstrap files, flank_phase=True the flank haplotype files, censored_fit=True the censored allele fit
-    and censored_bootstrap=B > 0 its bootstrap files, as for quantify_from_bam.
+    and censored_bootstrap=B > 0 its bootstrap files, as for quantify_from_bam.  methylation=True adds the CpG
+    methylation files as for quantify_from_bam, from the MM / ML tags in the header comments of a FASTQ file
+    (io.read_fastq_mod_tags); FASTA input has none.
     `engines` may carry aligner / scorer / screener / structure_engine / motif_engine / extension_engine /
     mixture_engine / consensus_engine / split_engine / segment_engine / path_aligner / period_engine /
-    bootstrap_engine / flank_engine / censored_engine stand-ins.  Returns the regions."""
+    bootstrap_engine / flank_engine / censored_engine / methylation_engine stand-ins.  Returns the regions."""
     from . import screen as nr_screen, mixture as nr_mixture
     nr_mixture.check_engine_name(mixture)
     _check_bootstrap(bootstrap, mixture)
+    meth = _methylation_options(methylation, meth_flank, meth_bin, meth_hi, meth_lo, meth_mod_code)
     censored = _censored_options(censored_fit, censored_error_rate, censored_max_alleles, partial_reads,
                                  in_repeat_reads)
     _check_censored_bootstrap(censored_bootstrap, censored_fit)
@@ -542,6 +577,9 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
             live.append(region)
             reads_of.append({name: seq for name, (seq, _) in reads.items()})
     flank = _flank_options(flank_phase, flank_len, flank_skip, flank_min_sites, regions, ref_fasta_dict)
+    if meth is not None:
+        tags = _fastq_mod_tags(in_reads)
+        meth["tags_of"] = [{name: tags[name] for name in reads if name in tags} for reads in reads_of]
     _quantify_and_write(regions, live, reads_of, out_prefix, data_type, fast_mode, ploidy, max_mutual_overlap,
                         max_num_components, remove_noisy_reads, no_details, num_cpu, device, scoring, seed, engines,
                         read_structure, _motif_options(discover_motifs, min_motif_count, min_motif_share),
@@ -550,8 +588,17 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         read_alignments=read_alignments, discover_periods=discover_periods,
                         partial_reads=partial_reads, in_repeat_reads=in_repeat_reads, candidates=candidates,
                         bootstrap=(bootstrap, bootstrap_confidence), flank=flank, censored=censored,
-                        censored_bootstrap=censored_bootstrap)
+                        censored_bootstrap=censored_bootstrap, methylation=meth)
     return regions
+
+
+def _fastq_mod_tags(in_reads):
+    """io.read_fastq_mod_tags of a FASTQ file; {} for FASTA input, which has no place for tags."""
+    with nr_io.gzopen(in_reads) as fp:
+        first = fp.readline()
+        while first and not first.strip():
+            first = fp.readline()
+    return nr_io.read_fastq_mod_tags(in_reads) if first[:1] == "@" else {}
 
 
 def _place_candidates(regions, live, reads_of, data_type, num_cpu, device, scoring, aligner, in_repeat_reads, offered,
