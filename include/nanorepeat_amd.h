@@ -944,6 +944,47 @@ int nra_read_methylation(int device, int32_t n_reads, const char* seqs, const in
                          int32_t flank, int32_t bin, int32_t lo_byte, int32_t hi_byte,
                          int32_t* counts, int32_t* n_c, int32_t* status);
 
+/* ---- Repeat scan: the tandem runs of every read, with no region, anchor or motif given (no counterpart in the
+ * reference)
+ *
+ * All of it is integer arithmetic; the result of a read does not depend on the other reads of the call or their order.
+ *
+ * Windows.  As for the screen: read r has len - k + 1 window positions (none when len < k); a window is valid when its
+ * k bytes are all A, C, G, T in either case.
+ *
+ * Window class.  A valid window w has period q when w[i] == w[i + q] for every i < k - q, compared without regard to
+ * case.  Its smallest period p in 1..6, if any, makes it a periodic window with the word w[0:p], upper-cased (a
+ * smallest period is primitive).  Its canonical word is the smallest (A < C < G < T) among the p rotations of the word
+ * and the p rotations of the word's reverse complement; its class id is (4^p - 4) / 3 + the canonical word read as a
+ * base-4 number, first base most significant (0 .. 5459).  The window is forward when the canonical word is a rotation
+ * of the word itself, else reverse; a class that is its own reverse complement (AT, ACGT) has forward windows only.
+ *
+ * Islands.  For read r and class C, the positions of C's windows in ascending order, cut wherever two neighbours differ
+ * by more than max_gap; each piece is an island with start = its first position, end = its last position + k, windows =
+ * its number of positions and fwd_windows = the forward ones among them.  The islands with end - start >= min_span are
+ * the runs, ordered by (read, start, end, class).  Islands of different classes may overlap.  DESIGN.md section 29. */
+#define NRA_SCAN_MAX_N   4000000   /* bases of a read */
+#define NRA_SCAN_MAX_GAP 100000
+
+typedef struct nra_scan_stats {
+    int64_t n_windows;    /* valid windows */
+    int64_t n_periodic;   /* periodic windows among them */
+    int64_t n_segments;   /* what the kernel wrote: runs of consecutive windows of one class and orientation in a tile */
+    int64_t n_chunks;     /* uploads */
+    double kernel_ms;     /* k_scan_repeats, summed over the chunks (HIP events) */
+} nra_scan_stats_t;
+
+/* read r = bytes [seq_off[r], seq_off[r+1]) of `seqs`.  On entry *n_runs is the capacity of the six run arrays, on
+ * return the number of runs; with too small a capacity nothing is written, *n_runs is the number needed and the call
+ * returns NRA_E_RANGE.  `stats` may be NULL.  k outside 8..15, max_gap outside 1..100 000, min_span < k, a negative
+ * count or capacity, offsets that decrease or a NULL array that is needed are NRA_E_ARG; a read of more than 4 000 000
+ * bases is NRA_E_RANGE.  Arguments are checked before the device is touched.  Empty reads, reads shorter than k and
+ * n_reads = 0 are fine. */
+int nra_scan_repeats(int device, int32_t n_reads, const char* seqs, const int64_t* seq_off, int32_t k,
+                     int32_t max_gap, int32_t min_span, int64_t* n_runs, int32_t* run_read, int32_t* run_start,
+                     int32_t* run_end, int32_t* run_class, int32_t* run_windows, int32_t* run_fwd_windows,
+                     nra_scan_stats_t* stats);
+
 #ifdef __cplusplus
 }
 #endif

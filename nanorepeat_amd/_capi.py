@@ -40,7 +40,8 @@ EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count
            "nra_screen_set_motifs", "nra_screen_reads_partial",
            "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts", "nra_mixture_fit", "nra_mixture_bootstrap",
            "nra_tract_consensus", "nra_allele_split", "nra_flank_phase", "nra_tract_segments", "nra_tract_periods",
-           "nra_censored_fit", "nra_censored_posteriors", "nra_censored_bootstrap", "nra_read_methylation")
+           "nra_censored_fit", "nra_censored_posteriors", "nra_censored_bootstrap", "nra_read_methylation",
+           "nra_scan_repeats")
 
 
 E_RANGE = -3      # NRA_E_RANGE
@@ -91,6 +92,14 @@ class ScreenStats(C.Structure):
                                          "n_empty_regions", "index_bytes", "bases_screened", "n_calls")] + \
                [(n, C.c_double) for n in ("build_ms", "kernel_ms", "sum_kernel_ms")] + \
                [("n_classes", C.c_int64), ("motif_kernel_ms", C.c_double), ("sum_motif_kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class ScanStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_windows", "n_periodic", "n_segments", "n_chunks")] + \
+               [("kernel_ms", C.c_double)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -232,6 +241,9 @@ def load():
     lib.nra_read_methylation.restype = C.c_int
     lib.nra_read_methylation.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, pi32, p8, pi64, p8, pi32, pi32,
                                          C.c_int32, C.c_int32, C.c_int32, C.c_int32, pi32, pi32, pi32]
+    lib.nra_scan_repeats.restype = C.c_int
+    lib.nra_scan_repeats.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, C.c_int32, C.c_int32, C.c_int32, pi64,
+                                     pi32, pi32, pi32, pi32, pi32, pi32, C.POINTER(ScanStats)]
     lib.nra_tract_periods.restype = C.c_int
     lib.nra_tract_periods.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, C.c_int32, pi32, pi32]
     _LIB = lib
@@ -832,6 +844,33 @@ def read_methylation(reads, mods, flags, tract_lo, tract_hi, flank=2000, bin=200
                                     _ptr(out["counts"], C.c_int32), _ptr(out["n_c"], C.c_int32),
                                     _ptr(out["status"], C.c_int32)))
     return out
+
+
+SCAN_KEYS = ("read", "start", "end", "cls", "windows", "fwd_windows")
+
+
+def scan_repeats(seqs, k=11, max_gap=100, min_span=200, device=0, capacity=None):
+    """nra_scan_repeats: the tandem runs of every read, no region or motif given -> dict(read, start, end, cls, windows,
+    fwd_windows: int32 per run, ordered by (read, start, end, cls); stats: dict).  When the runs exceed `capacity`, the
+    call is repeated once with the capacity the library asked for."""
+    lib = load()
+    data, off = pack_reads(list(seqs))
+    n = len(off) - 1
+    if capacity is None:
+        capacity = 4 * n + 1024
+    while True:
+        out = {key: np.zeros(capacity, np.int32) for key in SCAN_KEYS}
+        n_runs = C.c_int64(capacity)
+        st = ScanStats()
+        rc = lib.nra_scan_repeats(device, n, data, _ptr(off, C.c_int64), k, max_gap, min_span, C.byref(n_runs),
+                                  *(_ptr(out[key], C.c_int32) for key in SCAN_KEYS), C.byref(st))
+        if rc == E_RANGE and n_runs.value > capacity:
+            capacity = int(n_runs.value)
+            continue
+        _check(rc)
+        out = {key: v[:n_runs.value] for key, v in out.items()}
+        out["stats"] = st.as_dict()
+        return out
 
 
 def extend_tracts(motifs, tracts, read_motif, match=2, mismatch=4, gap=6, device=0):

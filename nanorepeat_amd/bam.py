@@ -190,6 +190,11 @@ class BamFile:
             yield BamRecord(name, seq if l_seq else None, quals, ref_id, pos, pos + max(ref_len, 1), flag, tags,
                             hard_clipped)
 
+    def records(self):
+        """Every record from the reader's position on, in file order, mapped or not: the whole file when it was just
+        opened."""
+        return self._records()
+
     def fetch(self, contig, start, stop):
         """Records overlapping [start, stop) of `contig`, in file order (the file must be sorted)."""
         if contig not in self.references:

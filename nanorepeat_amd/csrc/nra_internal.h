@@ -223,6 +223,22 @@ struct NraScreenEntry {
 #define NRA_MOTIF_TAB_ENTRIES (NRA_MOTIF_TAB_OFF(NRA_MOTIF_MAX_ROOT) + (1u << (2 * NRA_MOTIF_MAX_ROOT)))   // 5460
 #define NRA_MOTIF_MAX_LEN 64
 
+// Repeat scan (nra_scan.hip, nra_scan_host.cpp): the tiles of the screen with the position of a
+// tile's first window in its read; the table has the layout above, filled for every primitive p-mer with
+// (class id + 1) << 1 | reverse.
+struct NraScanTile {
+    int64_t base;
+    int32_t read;
+    int32_t n_win;
+    int32_t pos;
+    int32_t pad;
+};
+
+// `len` consecutive windows of one table entry, the first at window position `start` of `read`, all inside one tile
+struct NraScanSegment {
+    int32_t read, start, len, entry;
+};
+
 // Repeat structure (nra_structure.hip, nra_structure_host.cpp): the wraparound edit-distance alignment of a read's tract
 // against its motif repeated without end, one lane per read.  A launch takes reads of one phase
 // capacity P (motif length p <= P), sorted by tract length, descending, 64 to a wave.
@@ -557,6 +573,12 @@ int nra_launch_screen_hits(hipStream_t st, int64_t n_tiles, const NraScreenTile*
 int nra_launch_screen_motifs(hipStream_t st, int64_t n_tiles, const NraScreenTile* tiles, const uint8_t* seqs, int k,
                              const uint16_t* class_tab, NraScreenEntry* entries, unsigned long long cap,
                              unsigned long long* count);
+// repeat scan (nra_scan.hip): one workgroup per tile.  Segments go to segments[0, cap); *count ends as the number of
+// segments the tiles have, which may exceed cap (the host then grows the list and runs again); tile_valid[i] = the
+// valid windows of tile i (a store per tile: one counter for all tiles would be one more contended atomic per tile)
+int nra_launch_scan_repeats(hipStream_t st, int64_t n_tiles, const NraScanTile* tiles, const uint8_t* seqs, int k,
+                            const uint16_t* class_tab, NraScanSegment* segments, unsigned long long cap,
+                            unsigned long long* count, uint32_t* tile_valid);
 
 // repeat structure (nra_structure.hip): one lane per read, forward DP then traceback.  P in {1..6, 8, 16, 32, 64};
 // res[2 i] = edits, res[2 i + 1] = start phase of read i

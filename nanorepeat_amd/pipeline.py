@@ -514,7 +514,7 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         bootstrap=0, bootstrap_confidence=0.95, flank_phase=False, flank_len=3000, flank_skip=20,
                         flank_min_sites=2, censored_fit=False, censored_error_rate=None, censored_max_alleles=6,
                         censored_bootstrap=0, methylation=False, meth_flank=2000, meth_bin=200, meth_hi=192,
-                        meth_lo=63, meth_mod_code="m", **engines):
+                        meth_lo=63, meth_mod_code="m", discover_repeats=False, **engines):
     """The FASTQ / FASTA command (nanoRepeat.py:109, `-t fastq|fasta`) from files to files, without a genome mapper:
     the reads each region sees are chosen by the anchor k-mer screen (screen.reads_by_region) instead of a
     genome-wide mapping and a BAM window, then the BAM command's steps run unchanged.  Every region's reference
@@ -534,10 +534,13 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
     adds the bootstrap files, flank_phase=True the flank haplotype files, censored_fit=True the censored allele fit
     and censored_bootstrap=B > 0 its bootstrap files, as for quantify_from_bam.  methylation=True adds the CpG
     methylation files as for quantify_from_bam, from the MM / ML tags in the header comments of a FASTQ file
-    (io.read_fastq_mod_tags); FASTA input has none.
+    (io.read_fastq_mod_tags); FASTA input has none.  discover_repeats=True adds the discovered-repeat files
+    (discover.py) after everything else, from a second pass over the file that needs no region:
+    the tandem runs of every read, and per motif class how many reads carry one and how many BED regions have it.
     `engines` may carry aligner / scorer / screener / structure_engine / motif_engine / extension_engine /
     mixture_engine / consensus_engine / split_engine / segment_engine / path_aligner / period_engine /
-    bootstrap_engine / flank_engine / censored_engine / methylation_engine stand-ins.  Returns the regions."""
+    bootstrap_engine / flank_engine / censored_engine / methylation_engine / scan_engine stand-ins.  Returns the
+    regions."""
     from . import screen as nr_screen, mixture as nr_mixture
     nr_mixture.check_engine_name(mixture)
     _check_bootstrap(bootstrap, mixture)
@@ -589,7 +592,23 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         partial_reads=partial_reads, in_repeat_reads=in_repeat_reads, candidates=candidates,
                         bootstrap=(bootstrap, bootstrap_confidence), flank=flank, censored=censored,
                         censored_bootstrap=censored_bootstrap, methylation=meth)
+    if discover_repeats:
+        from . import discover as nr_discover
+        nr_discover.discover_file(in_reads, out_prefix, repeat_region_bed, no_details=no_details, device=device,
+                                  chunk_bases=chunk_bases, engine=engines.get("scan_engine"))
     return regions
+
+
+def discover_repeats(reads_path, out_prefix, repeat_region_bed=None, k=11, max_gap=100, min_span=200, no_details=False,
+                     device=0, engine=None):
+    """The discovery command from files to files (no counterpart in the reference): every read of a FASTQ / FASTA / BAM
+    file through the repeat scan (discover.py), with no region, anchor or motif given ->
+    `<out_prefix>.discovered_runs.tsv` (one row per tandem run of at least min_span bases; not with no_details) and
+    `<out_prefix>.NanoRepeat_discovered.tsv` (one row per motif class with a run; with a BED file, how many of its
+    regions have that class).  `engine` stands in for _capi.scan_repeats (tests).  Returns the class rows."""
+    from . import discover as nr_discover
+    return nr_discover.discover_file(reads_path, out_prefix, repeat_region_bed, k, max_gap, min_span, no_details, device,
+                                     engine=engine)
 
 
 def _fastq_mod_tags(in_reads):

@@ -229,7 +229,7 @@ DECOY_KINDS = ("slice", "random", "single", "nrun", "lower", "short")
 
 
 def panel(n_regions=12, n_chroms=3, anchor_len=1000, reads_per_region=10, model="ont", edge_overlaps=(), n_decoys=0,
-          shared=0, shared_len=300, lower_every=7, seed=SEED):
+          shared=0, shared_len=300, lower_every=7, seed=SEED, units=None):
     """A seeded multi-region panel for the FASTQ / FASTA command (screen + anchors + rounds).
 
     Regions sit on `n_chroms` chromosomes with at least 4 kb between the windows region +- anchor_len.  Per region:
@@ -239,7 +239,8 @@ def panel(n_regions=12, n_chroms=3, anchor_len=1000, reads_per_region=10, model=
     lowercase.  `n_decoys` decoys cycle through DECOY_KINDS: a genome slice outside every window, random sequence,
     one anchor only, random sequence with N runs, a lowercase genome slice, a read shorter than 11 bases.
     `shared` > 0: the same `shared_len`-base element replaces the middle of the left anchor of that many regions
-    (k-mers shared by more anchors than max_occ are masked by the screen).
+    (k-mers shared by more anchors than max_occ are masked by the screen).  `units`: region g's motif is
+    units[g % len(units)] instead of a random one of 3..6 bases.
 
     Returns dict(ref={chrom: seq}, bed=[line], regions=[(chrom, start, end, unit)], reads=[(name, seq)] in a
     shuffled file order, truth={name: (region, k)}, overlap={name: (left bases, right bases) of the anchors}).
@@ -252,7 +253,7 @@ def panel(n_regions=12, n_chroms=3, anchor_len=1000, reads_per_region=10, model=
     regions, deserts = [], []              # deserts: (chrom, start, end) outside every window
     for g in range(n_regions):
         chrom = f"chr{g % n_chroms + 1}"
-        unit = rand_unit(rng, int(rng.integers(3, 7)))
+        unit = units[g % len(units)] if units else rand_unit(rng, int(rng.integers(3, 7)))
         kref = int(rng.integers(8, 21))
         left = rand_seq(rng, anchor_len + extra)
         if g < shared:
