@@ -985,6 +985,42 @@ int nra_scan_repeats(int device, int32_t n_reads, const char* seqs, const int64_
                      int32_t* run_end, int32_t* run_class, int32_t* run_windows, int32_t* run_fwd_windows,
                      nra_scan_stats_t* stats);
 
+/* ---- Sketch pairs: which sequences of a group share k-mers (no counterpart in the reference)
+ *
+ * All of it is integer arithmetic; the result depends on neither the order of the sequences nor the other groups.
+ *
+ * Windows, valid windows and canon are the anchor screen's: a k-window (k odd, 11..15) is valid when all its bytes are
+ * ACGTacgt, canon(w) = min(code(w), code(revcomp(w))), 2 bits per base, first base most significant.  A valid window is
+ * periodic when w[i] == w[i+q] for all i < k - q and some q in 1..6, case ignored.  The sketch of a sequence is the set
+ * of the distinct canon(w) over its valid windows that are not periodic; a sequence shorter than k or without such a
+ * window has an empty sketch.  For a < b with group[a] == group[b] >= 0, shared(a, b) = |sketch(a) & sketch(b)|; the
+ * result is every such pair with shared >= min_shared, ordered by (a, b).  A negative group id pairs with nobody; group
+ * ids need not be contiguous or sorted.  DESIGN.md section 30. */
+#define NRA_SKETCH_MAX_N     2048    /* bases of a sequence */
+#define NRA_SKETCH_MAX_GROUP 65536   /* sequences of one group */
+
+typedef struct nra_sketch_stats {
+    int64_t n_windows;    /* valid windows */
+    int64_t n_kmers;      /* the sum of the sketch sizes */
+    int64_t n_compared;   /* pairs (a, b) compared: n (n - 1) / 2 summed over the groups */
+    int64_t n_tiles;      /* workgroups of k_sketch_pairs: a sequence against up to 64 later ones of its group */
+    double kernel_ms;     /* sketch_ms + pairs_ms (HIP events) */
+    double sketch_ms;     /* k_sketch */
+    double pairs_ms;      /* k_sketch_pairs, both runs when the pair list had to grow */
+    double upload_ms;     /* host: offsets, allocations and the copies to the device (wall clock) */
+    double sort_ms;       /* host: the sort of the pairs (wall clock) */
+} nra_sketch_stats_t;
+
+/* sequence s = bytes [seq_off[s], seq_off[s+1]) of `seqs`.  On entry *n_pairs is the capacity of the three pair arrays,
+ * on return the number of pairs; with too small a capacity nothing is written, *n_pairs is the number needed and the
+ * call returns NRA_E_RANGE.  sketch_size (n_seqs values, may be NULL) receives every sequence's sketch size, stats may
+ * be NULL.  k even or outside 11..15, min_shared < 1, a negative count or capacity, offsets that decrease or a NULL
+ * array that is needed are NRA_E_ARG; a sequence of more than 2048 bases or a group of more than 65 536 sequences is
+ * NRA_E_RANGE.  Arguments are checked before the device is touched.  n_seqs = 0 is fine. */
+int nra_sketch_pairs(int device, int32_t n_seqs, const char* seqs, const int64_t* seq_off, const int32_t* group,
+                     int32_t k, int32_t min_shared, int64_t* n_pairs, int32_t* pair_a, int32_t* pair_b,
+                     int32_t* pair_shared, int32_t* sketch_size, nra_sketch_stats_t* stats);
+
 #ifdef __cplusplus
 }
 #endif

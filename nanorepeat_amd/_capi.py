@@ -41,7 +41,7 @@ EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count
            "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts", "nra_mixture_fit", "nra_mixture_bootstrap",
            "nra_tract_consensus", "nra_allele_split", "nra_flank_phase", "nra_tract_segments", "nra_tract_periods",
            "nra_censored_fit", "nra_censored_posteriors", "nra_censored_bootstrap", "nra_read_methylation",
-           "nra_scan_repeats")
+           "nra_scan_repeats", "nra_sketch_pairs")
 
 
 E_RANGE = -3      # NRA_E_RANGE
@@ -100,6 +100,14 @@ class ScreenStats(C.Structure):
 class ScanStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_windows", "n_periodic", "n_segments", "n_chunks")] + \
                [("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class SketchStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_windows", "n_kmers", "n_compared", "n_tiles")] + \
+               [(n, C.c_double) for n in ("kernel_ms", "sketch_ms", "pairs_ms", "upload_ms", "sort_ms")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -244,6 +252,9 @@ def load():
     lib.nra_scan_repeats.restype = C.c_int
     lib.nra_scan_repeats.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, C.c_int32, C.c_int32, C.c_int32, pi64,
                                      pi32, pi32, pi32, pi32, pi32, pi32, C.POINTER(ScanStats)]
+    lib.nra_sketch_pairs.restype = C.c_int
+    lib.nra_sketch_pairs.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, pi32, C.c_int32, C.c_int32, pi64, pi32, pi32,
+                                     pi32, pi32, C.POINTER(SketchStats)]
     lib.nra_tract_periods.restype = C.c_int
     lib.nra_tract_periods.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, C.c_int32, pi32, pi32]
     _LIB = lib
@@ -869,6 +880,42 @@ def scan_repeats(seqs, k=11, max_gap=100, min_span=200, device=0, capacity=None)
             continue
         _check(rc)
         out = {key: v[:n_runs.value] for key, v in out.items()}
+        out["stats"] = st.as_dict()
+        return out
+
+
+SKETCH_KEYS = ("a", "b", "shared")
+SKETCH_MAX_LEN = 2048      # NRA_SKETCH_MAX_N
+SKETCH_MAX_GROUP = 65536   # NRA_SKETCH_MAX_GROUP
+
+
+def sketch_pairs(seqs, groups, k=13, min_shared=1, device=0, capacity=None):
+    """nra_sketch_pairs: the pairs of sequences of one group (groups[i], negative: none) that share at least min_shared
+    canonical non-periodic k-mers -> dict(a, b, shared: int32 per pair, a < b, ordered by (a, b); sketch_size: int32
+    per sequence; stats: dict).  When the pairs exceed `capacity`, the call is repeated once with the capacity the
+    library asked for."""
+    lib = load()
+    data, off = pack_reads(list(seqs))
+    n = len(off) - 1
+    grp = np.ascontiguousarray(groups, np.int32)
+    if grp.shape != (n,):
+        raise ValueError("one group id per sequence")
+    if capacity is None:
+        capacity = 16 * n + 1024
+    while True:
+        out = {key: np.zeros(capacity, np.int32) for key in SKETCH_KEYS}
+        size = np.zeros(n, np.int32)
+        n_pairs = C.c_int64(capacity)
+        st = SketchStats()
+        rc = lib.nra_sketch_pairs(device, n, data, _ptr(off, C.c_int64), _ptr(grp, C.c_int32), k, min_shared,
+                                  C.byref(n_pairs), *(_ptr(out[key], C.c_int32) for key in SKETCH_KEYS),
+                                  _ptr(size, C.c_int32), C.byref(st))
+        if rc == E_RANGE and n_pairs.value > capacity:
+            capacity = int(n_pairs.value)
+            continue
+        _check(rc)
+        out = {key: v[:n_pairs.value] for key, v in out.items()}
+        out["sketch_size"] = size
         out["stats"] = st.as_dict()
         return out
 

@@ -239,6 +239,22 @@ struct NraScanSegment {
     int32_t read, start, len, entry;
 };
 
+// K-mer sketches and their pairs (nra_sketch.hip, nra_sketch_host.cpp).  A sequence has at most
+// NRA_SKETCH_MAX_LEN bases, so its sketch fits the NRA_SKETCH_MAX_LEN sort slots of one workgroup and, in the pair
+// kernel, fills the NRA_SKETCH_SET_SLOTS slots of the LDS set at most half.  A tile of the pair kernel is one sequence i
+// against up to NRA_SKETCH_BLOCK later sequences of its group.
+#define NRA_SKETCH_MAX_LEN 2048
+#define NRA_SKETCH_THREADS 256
+#define NRA_SKETCH_SET_SLOTS 4096
+#define NRA_SKETCH_BLOCK 64
+#define NRA_SKETCH_LAUNCH_TILES (1 << 23)        // tiles per launch: a grid of 2^32 threads or more runs only in part
+#define NRA_SKETCH_EMPTY 0xffffffffu            // no k-mer: k <= 15, so a code has at most 30 bits
+
+// one returned pair, original sequence indices, a < b
+struct NraSketchPair {
+    int32_t a, b, shared, pad;
+};
+
 // Repeat structure (nra_structure.hip, nra_structure_host.cpp): the wraparound edit-distance alignment of a read's tract
 // against its motif repeated without end, one lane per read.  A launch takes reads of one phase
 // capacity P (motif length p <= P), sorted by tract length, descending, 64 to a wave.
@@ -579,6 +595,21 @@ int nra_launch_screen_motifs(hipStream_t st, int64_t n_tiles, const NraScreenTil
 int nra_launch_scan_repeats(hipStream_t st, int64_t n_tiles, const NraScanTile* tiles, const uint8_t* seqs, int k,
                             const uint16_t* class_tab, NraScanSegment* segments, unsigned long long cap,
                             unsigned long long* count, uint32_t* tile_valid);
+
+// sketches (nra_sketch.hip): one workgroup per sequence.  Sequence s = bytes [seq_base[s], seq_base[s] + seq_len[s]) of
+// `seqs` (padded by 64 bytes); its sketch goes, ascending, to sketch[sk_off[s] ...], its size to sk_len[s] and its
+// number of valid windows to n_valid[s]
+int nra_launch_sketch(hipStream_t st, int32_t n_seqs, const uint8_t* seqs, const int64_t* seq_base, const int32_t* seq_len,
+                      int k, const int64_t* sk_off, uint32_t* sketch, int32_t* sk_len, int32_t* n_valid);
+// sketch pairs (nra_sketch.hip): workgroups [tile0, tile0 + n_tiles) of the implicit tile list, n_tiles at most
+// NRA_SKETCH_LAUNCH_TILES.  Position s of the
+// sorted order (sequences by group, then index) owns the tiles [tile_first[s], tile_first[s + 1]): block t of it is the
+// positions s + 1 + 64 t ... below grp_end[s].  order[s] is the sequence at position s.  Pairs with at least min_shared
+// shared k-mers go to pairs[0, cap); *count ends as their number, which may exceed cap
+int nra_launch_sketch_pairs(hipStream_t st, int64_t tile0, int64_t n_tiles, int32_t n_sorted, const int64_t* tile_first,
+                            const int32_t* order, const int32_t* grp_end, const int64_t* sk_off, const uint32_t* sketch,
+                            const int32_t* sk_len, int min_shared, NraSketchPair* pairs, unsigned long long cap,
+                            unsigned long long* count);
 
 // repeat structure (nra_structure.hip): one lane per read, forward DP then traceback.  P in {1..6, 8, 16, 32, 64};
 // res[2 i] = edits, res[2 i + 1] = start phase of read i

@@ -81,13 +81,15 @@ def _bam_chunks(path, chunk_bases):
         bam.close()
 
 
-def scan_reads(path, k=11, max_gap=100, min_span=200, chunk_bases=1 << 28, device=0, engine=None):
+def scan_reads(path, k=11, max_gap=100, min_span=200, chunk_bases=1 << 28, device=0, engine=None, flank_len=0):
     """Streams `path` (FASTQ or FASTA, gzip-aware; a path ending in .bam: the primary records with a sequence) through
     the scan, one call per chunk of about chunk_bases bases.  Returns the runs in file order, then by start: dicts with
     name, read_len, ref, ref_start ('-' for FASTQ / FASTA; the record's contig and start, or '*', for BAM), start, end,
     span, class_id, cls (the class's word), unit (read[start:start + p], upper-cased), strand, copies (span // p),
     windows, density (windows / (span - k + 1)) and kind (run_kind with edge = max_gap).  `engine`: a stand-in for
-    _capi.scan_repeats(seqs, k, max_gap, min_span, device)."""
+    _capi.scan_repeats(seqs, k, max_gap, min_span, device).  flank_len > 0 (loci.py): the rows also carry left_flank =
+    read[start - flank_len:start] and right_flank = read[end:end + flank_len], cut at the read's ends, and read_index,
+    the read's ordinal among the records the scan saw."""
     if engine is None:
         from . import _capi
         engine = _capi.scan_repeats
@@ -95,7 +97,7 @@ def scan_reads(path, k=11, max_gap=100, min_span=200, chunk_bases=1 << 28, devic
         chunks = _bam_chunks(path, chunk_bases)
     else:
         chunks = ((names, seqs, None) for names, seqs, _ in nr_io.iter_reads(path, chunk_bases))
-    rows = []
+    rows, n_before = [], 0
     for names, seqs, refs in chunks:
         got = engine(seqs, k, max_gap, min_span, device)
         cols = [got[key] for key in ("read", "start", "end", "cls", "windows", "fwd_windows")]
@@ -107,6 +109,10 @@ def scan_reads(path, k=11, max_gap=100, min_span=200, chunk_bases=1 << 28, devic
                              span=span, class_id=cid, cls=word, unit=seq[start:start + p].upper(),
                              strand="+" if 2 * fwd >= windows else "-", copies=span // p, windows=windows,
                              density=windows / (span - k + 1), kind=run_kind(start, end, len(seq), max_gap)))
+            if flank_len > 0:
+                rows[-1].update(left_flank=seq[max(0, start - flank_len):start], right_flank=seq[end:end + flank_len],
+                                read_index=n_before + r)
+        n_before += len(seqs)
     return rows
 
 
@@ -158,12 +164,34 @@ def write_classes(classes, path):
             f.write("\t".join(str(c[col]) for col in CLASS_COLUMNS) + "\n")
 
 
+def fetch_reads(path, indices, chunk_bases=1 << 28):
+    """{read_index: (name, sequence)} of the records scan_reads numbered `indices`: one more pass over the file."""
+    wanted, out, n_before = set(indices), {}, 0
+    if not wanted:
+        return out
+    if str(path).lower().endswith(".bam"):
+        chunks = _bam_chunks(path, chunk_bases)
+    else:
+        chunks = nr_io.iter_reads(path, chunk_bases)
+    for names, seqs, _ in chunks:
+        for i in wanted.intersection(range(n_before, n_before + len(seqs))):
+            out[i] = (names[i - n_before], seqs[i - n_before])
+        n_before += len(seqs)
+    return out
+
+
 def discover_file(reads_path, out_prefix, repeat_region_bed=None, k=11, max_gap=100, min_span=200, no_details=False,
-                  device=0, chunk_bases=1 << 28, engine=None, stream=None):
+                  device=0, chunk_bases=1 << 28, engine=None, stream=None, group_loci=False, flank_len=500, sketch_k=13,
+                  min_shared=None, min_locus_reads=3, sketch_engine=None):
     """scan_reads of the file -> `<out_prefix>.discovered_runs.tsv` (not with no_details) and
     `<out_prefix>.NanoRepeat_discovered.tsv`, and one NOTICE counting the classes with runs and no BED region.  Returns
-    the summary rows (class_rows)."""
-    rows = scan_reads(reads_path, k, max_gap, min_span, chunk_bases, device, engine)
+    the summary rows (class_rows).  group_loci=True (loci.py) also groups the runs into loci by
+    their flanks and writes the four locus files; the two files above are what they are without it."""
+    if group_loci:
+        from . import loci as nr_loci
+        min_shared = nr_loci.check_options(flank_len, sketch_k, min_shared, min_locus_reads)
+    rows = scan_reads(reads_path, k, max_gap, min_span, chunk_bases, device, engine,
+                      flank_len=flank_len if group_loci else 0)
     catalogue = catalogue_classes(repeat_region_bed) if repeat_region_bed else None
     classes = class_rows(rows, catalogue)
     if not no_details:
@@ -173,4 +201,7 @@ def discover_file(reads_path, out_prefix, repeat_region_bed=None, k=11, max_gap=
     if new:
         print(f"NOTICE: {new} repeat class(es) have runs of at least {min_span} bases in the reads and no region in "
               f"the BED file", file=stream or sys.stderr)
+    if group_loci:
+        nr_loci.loci_files(reads_path, out_prefix, rows, catalogue, sketch_k, min_shared, min_locus_reads, no_details,
+                           device, chunk_bases, sketch_engine, stream)
     return classes

@@ -514,7 +514,8 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         bootstrap=0, bootstrap_confidence=0.95, flank_phase=False, flank_len=3000, flank_skip=20,
                         flank_min_sites=2, censored_fit=False, censored_error_rate=None, censored_max_alleles=6,
                         censored_bootstrap=0, methylation=False, meth_flank=2000, meth_bin=200, meth_hi=192,
-                        meth_lo=63, meth_mod_code="m", discover_repeats=False, **engines):
+                        meth_lo=63, meth_mod_code="m", discover_repeats=False, group_loci=False, locus_flank_len=500,
+                        sketch_k=13, min_shared=None, min_locus_reads=3, **engines):
     """The FASTQ / FASTA command (nanoRepeat.py:109, `-t fastq|fasta`) from files to files, without a genome mapper:
     the reads each region sees are chosen by the anchor k-mer screen (screen.reads_by_region) instead of a
     genome-wide mapping and a BAM window, then the BAM command's steps run unchanged.  Every region's reference
@@ -537,11 +538,20 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
     (io.read_fastq_mod_tags); FASTA input has none.  discover_repeats=True adds the discovered-repeat files
     (discover.py) after everything else, from a second pass over the file that needs no region:
     the tandem runs of every read, and per motif class how many reads carry one and how many BED regions have it.
+    group_loci=True beside it adds the four locus files (loci.py): the runs grouped into loci by
+    their flanks (locus_flank_len bases a side -- discover_repeats()' flank_len, which is the flank haplotypes' keyword
+    here --, sketch_k, min_shared: None is the measured default) and a pseudo-reference with a BED file for the core
+    loci with at least min_locus_reads spanned runs; without discover_repeats=True it is a ValueError.
     `engines` may carry aligner / scorer / screener / structure_engine / motif_engine / extension_engine /
     mixture_engine / consensus_engine / split_engine / segment_engine / path_aligner / period_engine /
-    bootstrap_engine / flank_engine / censored_engine / methylation_engine / scan_engine stand-ins.  Returns the
-    regions."""
+    bootstrap_engine / flank_engine / censored_engine / methylation_engine / scan_engine / sketch_engine stand-ins.
+    Returns the regions."""
     from . import screen as nr_screen, mixture as nr_mixture
+    if group_loci:
+        from . import loci as nr_loci
+        if not discover_repeats:
+            raise ValueError("group_loci=True needs discover_repeats=True")
+        nr_loci.check_options(locus_flank_len, sketch_k, min_shared, min_locus_reads)
     nr_mixture.check_engine_name(mixture)
     _check_bootstrap(bootstrap, mixture)
     meth = _methylation_options(methylation, meth_flank, meth_bin, meth_hi, meth_lo, meth_mod_code)
@@ -595,20 +605,30 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
     if discover_repeats:
         from . import discover as nr_discover
         nr_discover.discover_file(in_reads, out_prefix, repeat_region_bed, no_details=no_details, device=device,
-                                  chunk_bases=chunk_bases, engine=engines.get("scan_engine"))
+                                  chunk_bases=chunk_bases, engine=engines.get("scan_engine"), group_loci=group_loci,
+                                  flank_len=locus_flank_len, sketch_k=sketch_k, min_shared=min_shared,
+                                  min_locus_reads=min_locus_reads, sketch_engine=engines.get("sketch_engine"))
     return regions
 
 
 def discover_repeats(reads_path, out_prefix, repeat_region_bed=None, k=11, max_gap=100, min_span=200, no_details=False,
-                     device=0, engine=None):
+                     device=0, engine=None, group_loci=False, flank_len=500, sketch_k=13, min_shared=None,
+                     min_locus_reads=3, sketch_engine=None):
     """The discovery command from files to files (no counterpart in the reference): every read of a FASTQ / FASTA / BAM
     file through the repeat scan (discover.py), with no region, anchor or motif given ->
     `<out_prefix>.discovered_runs.tsv` (one row per tandem run of at least min_span bases; not with no_details) and
     `<out_prefix>.NanoRepeat_discovered.tsv` (one row per motif class with a run; with a BED file, how many of its
-    regions have that class).  `engine` stands in for _capi.scan_repeats (tests).  Returns the class rows."""
+    regions have that class).  `engine` stands in for _capi.scan_repeats (tests).  group_loci=True (loci.py; DESIGN.md
+    section 30) groups the runs into loci by the flank_len bases on either side of them (canonical sketch_k-mers, two
+    sides match at min_shared shared ones: None is the measured default) and adds `<out_prefix>.discovered_loci.tsv`,
+    `.discovered_locus_runs.tsv` (not with no_details) and `.discovered_loci.fa` / `.bed`, a pseudo-reference of the
+    core loci with at least min_locus_reads spanned runs that quantify_from_reads takes as its reference and BED file;
+    `sketch_engine` stands in for _capi.sketch_pairs.  A bad value is a ValueError.  Returns the class rows."""
     from . import discover as nr_discover
     return nr_discover.discover_file(reads_path, out_prefix, repeat_region_bed, k, max_gap, min_span, no_details, device,
-                                     engine=engine)
+                                     engine=engine, group_loci=group_loci, flank_len=flank_len, sketch_k=sketch_k,
+                                     min_shared=min_shared, min_locus_reads=min_locus_reads,
+                                     sketch_engine=sketch_engine)
 
 
 def _fastq_mod_tags(in_reads):
