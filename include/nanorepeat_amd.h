@@ -372,6 +372,31 @@ int64_t nra_plan1d_digest(const nra_region_t* regions, int32_t n_regions,
                           int32_t n_reads, const char* seqs, const int64_t* seq_off,
                           const int32_t* read_region, const int32_t* kmin, const int32_t* kmax,
                           const nra_scoring_t* sc, int32_t flags, int32_t simds, char* buf, int64_t cap);
+/* 2D: the plans a joint batch of these reads would make for a sequence of steps, as text, on the host (no device needed;
+ * additive, ABI 4; for tests and measurements).  The steps are played in order on what a batch carries from one cell list
+ * to the next; after each the batch counts as run and waited for.  A step carries its own inputs: its strands (or NULL),
+ * its cells / grid / bounds and buffers, the keep budget in bytes and a stand-in for the device's free bytes; what the
+ * keep arena holds is what the last keeping step asked for.  Per step: the plan's scalars, one line per bucket and per
+ * group of sweeps, for every array of the plan and of the carried state its length and a 64-bit FNV-1a hash over its
+ * values -- or the step's error code and text.  Buffer and return value as nra_plan1d_digest. */
+#define NRA_PLAN2D_CELLS 0        /* nra_batch2d_set_cells */
+#define NRA_PLAN2D_GRID 1         /* nra_batch2d_set_grid */
+#define NRA_PLAN2D_SWEEP_FLANKS 2 /* nra_batch2d_sweep_flanks */
+#define NRA_PLAN2D_REFINE 3       /* nra_batch2d_refine (behind the step before it, as if that one was not waited for) */
+#define NRA_PLAN2D_INVALIDATE 4   /* nra_batch2d_invalidate */
+typedef struct {
+    int32_t kind;
+    const int8_t* read_strand;
+    int64_t n_cells;                                        /* cell list */
+    const int32_t *cell_read, *cell_k1, *cell_k2;
+    int32_t start1, step1, count1, start2, step2, count2;   /* grid */
+    const double *lo1, *hi1, *lo2, *hi2;                    /* grid, refinement */
+    int32_t buf1, buf2;                                     /* refinement */
+    int64_t keep_budget, device_free;                       /* bytes */
+} nra_plan2d_step_t;
+int64_t nra_plan2d_digest(const nra_joint_region_t* region, int32_t n_reads, const char* seqs, const int64_t* seq_off,
+                          const nra_scoring_t* sc, int32_t flags, const nra_plan2d_step_t* steps, int32_t n_steps,
+                          char* buf, int64_t cap);
 int  nra_batch2d_fetch(nra_batch_t* b, int8_t* read_strand,
                        int32_t* cell_score, int32_t* cell_wscore,
                        int32_t* best_wscore, int64_t* sum_k1, int64_t* sum_k2,

@@ -35,7 +35,7 @@ F_FULL_ANCHORS = 8192  # testing / comparison, 1D: the exact cell over every anc
 EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count",
            "nra_default_scoring", "nra_release_cached_memory", "nra_round3_1d", "nra_joint_2d", "nra_align_pairs", "nra_align_pairs_cigar", "nra_align_paths", "nra_batch1d_create",
            "nra_batch2d_create", "nra_batch2d_create_reads", "nra_batch2d_set_cells", "nra_joint_grid_cells", "nra_batch2d_set_grid", "nra_batch2d_invalidate", "nra_batch2d_sweep_flanks", "nra_batch2d_refine", "nra_batch_run", "nra_batch_sync", "nra_batch_stats",
-           "nra_batch1d_fetch", "nra_batch1d_resweeps", "nra_batch1d_saturation", "nra_batch1d_clears", "nra_plan1d_digest", "nra_batch2d_fetch", "nra_batch_destroy",
+           "nra_batch1d_fetch", "nra_batch1d_resweeps", "nra_batch1d_saturation", "nra_batch1d_clears", "nra_plan1d_digest", "nra_plan2d_digest", "nra_batch2d_fetch", "nra_batch_destroy",
            "nra_screen_create", "nra_screen_reads", "nra_screen_stats", "nra_screen_destroy",
            "nra_screen_set_motifs", "nra_screen_reads_partial",
            "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts", "nra_mixture_fit", "nra_mixture_bootstrap",
@@ -70,6 +70,16 @@ class JointRegion(C.Structure):
                 ("unit2", C.c_char_p), ("right", C.c_char_p),
                 ("left_len", C.c_int32), ("unit1_len", C.c_int32), ("mid_len", C.c_int32),
                 ("unit2_len", C.c_int32), ("right_len", C.c_int32)]
+
+
+class Plan2DStep(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("read_strand", C.POINTER(C.c_int8)), ("n_cells", C.c_int64),
+                ("cell_read", C.POINTER(C.c_int32)), ("cell_k1", C.POINTER(C.c_int32)), ("cell_k2", C.POINTER(C.c_int32)),
+                ("start1", C.c_int32), ("step1", C.c_int32), ("count1", C.c_int32),
+                ("start2", C.c_int32), ("step2", C.c_int32), ("count2", C.c_int32),
+                ("lo1", C.POINTER(C.c_double)), ("hi1", C.POINTER(C.c_double)),
+                ("lo2", C.POINTER(C.c_double)), ("hi2", C.POINTER(C.c_double)),
+                ("buf1", C.c_int32), ("buf2", C.c_int32), ("keep_budget", C.c_int64), ("device_free", C.c_int64)]
 
 
 class Stats(C.Structure):
@@ -189,6 +199,9 @@ def load():
     lib.nra_batch1d_clears.argtypes = [vp, pi32, pi32]
     lib.nra_plan1d_digest.restype = C.c_int64
     lib.nra_plan1d_digest.argtypes = lib.nra_batch1d_create.argtypes[1:-1] + [C.c_int32, C.c_char_p, C.c_int64]
+    lib.nra_plan2d_digest.restype = C.c_int64
+    lib.nra_plan2d_digest.argtypes = [C.POINTER(JointRegion), C.c_int32, C.c_char_p, pi64, C.POINTER(Scoring), C.c_int32,
+                                      C.POINTER(Plan2DStep), C.c_int32, C.c_char_p, C.c_int64]
     lib.nra_batch1d_fetch.argtypes = [vp, pi32, pi64, pi32, p8, pi32, pi32, pi32]
     lib.nra_batch2d_fetch.restype = C.c_int
     lib.nra_batch2d_fetch.argtypes = [vp, pi8, pi32, pi32, pi32, pi64, pi64, pi32, p8]
@@ -376,6 +389,52 @@ def plan1d_digest(regions, reads, kmin, kmax, read_region=None, sc=None, flags=0
         _check(int(need))
     buf = C.create_string_buffer(int(need))
     _check(min(0, int(lib.nra_plan1d_digest(*args, buf, need))))
+    return buf.value.decode()
+
+
+PLAN2D_KINDS = {"cells": 0, "grid": 1, "sweep_flanks": 2, "refine": 3, "invalidate": 4}
+JOINT_KEEP_BUDGET = 96 << 30     # NRA_JOINT_KEEP_BUDGET
+
+
+def plan2d_digest(region, reads, steps, sc=None, flags=0):
+    """nra_plan2d_digest: the plans a joint batch of `reads` would make for `steps`, played in order, as text (no device
+    needed).  A step is a dict: kind (a key of PLAN2D_KINDS), strand (or None), cells = (cell_read, k1, k2), grid = Grid,
+    bounds = (lo1, hi1, lo2, hi2) and buf = (buf1, buf2) of a refinement, budget / free in bytes."""
+    lib = load()
+    sc = sc or default_scoring()
+    seqs, off = pack_reads(reads)
+    jr, keep = _joint_region(region)
+    arr = (Plan2DStep * max(len(steps), 1))()
+    for i, s in enumerate(steps):
+        t = arr[i]
+        t.kind = PLAN2D_KINDS[s["kind"]]
+        t.keep_budget = s.get("budget", JOINT_KEEP_BUDGET)
+        t.device_free = s.get("free", 256 << 30)
+        if s.get("strand") is not None:
+            st = np.ascontiguousarray(s["strand"], np.int8)
+            keep.append(st)
+            t.read_strand = _ptr(st, C.c_int8)
+        if "cells" in s:
+            cr, k1, k2 = (np.ascontiguousarray(a, np.int32) for a in s["cells"])
+            keep += [cr, k1, k2]
+            t.n_cells = len(cr)
+            t.cell_read, t.cell_k1, t.cell_k2 = (_ptr(a, C.c_int32) for a in (cr, k1, k2))
+        if "grid" in s:
+            g = s["grid"]
+            keep.append(g)
+            (t.start1, t.step1, t.count1), (t.start2, t.step2, t.count2) = g.axes
+            t.lo1, t.hi1, t.lo2, t.hi2 = (_ptr(a, C.c_double) for a in g.bounds)
+        if "bounds" in s:
+            b = [np.ascontiguousarray(a, np.float64) for a in s["bounds"]]
+            keep += b
+            t.lo1, t.hi1, t.lo2, t.hi2 = (_ptr(a, C.c_double) for a in b)
+            t.buf1, t.buf2 = s["buf"]
+    args = (C.byref(jr), len(reads), seqs, _ptr(off, C.c_int64), C.byref(sc), flags, arr, len(steps))
+    need = lib.nra_plan2d_digest(*args, None, 0)
+    if need < 0:
+        _check(int(need))
+    buf = C.create_string_buffer(int(need))
+    _check(min(0, int(lib.nra_plan2d_digest(*args, buf, need))))
     return buf.value.decode()
 
 

@@ -35,7 +35,7 @@ KERNELS = (("nra_kernels.hip", (1, 2, 3, 4)),
            ("nra_methyl.hip", (40,)),
            ("nra_scan.hip", (41,)),
            ("nra_sketch.hip", (42,)))
-HOSTS = ("nra_host.cpp", "nra_plan1d.cpp", "nra_screen_host.cpp", "nra_structure_host.cpp", "nra_motif_host.cpp", "nra_extend_host.cpp",
+HOSTS = ("nra_host.cpp", "nra_plan1d.cpp", "nra_plan2d.cpp", "nra_screen_host.cpp", "nra_structure_host.cpp", "nra_motif_host.cpp", "nra_extend_host.cpp",
          "nra_mixture_host.cpp", "nra_consensus_host.cpp", "nra_split_host.cpp", "nra_segment_host.cpp",
          "nra_period_host.cpp", "nra_bootstrap_host.cpp", "nra_flank_host.cpp", "nra_censored_host.cpp", "nra_methyl_host.cpp",
          "nra_scan_host.cpp", "nra_sketch_host.cpp")

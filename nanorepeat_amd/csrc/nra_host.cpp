@@ -8,6 +8,7 @@
 #include "nanorepeat_amd.h"
 #include "nra_internal.h"
 #include "nra_plan1d.h"
+#include "nra_plan2d.h"
 
 #include <algorithm>
 #include <atomic>
@@ -352,15 +353,6 @@ hipError_t copy_d2h(void* dst, const void* src, size_t bytes)
     return hipSuccess;
 }
 
-// 2D decomposition: reads of one bucket whose wave states fit the state buffer together; the
-// prefix sweeps of a group run, then its tail sweeps, then the next group reuses the buffer.
-struct JointGroup {
-    int R = 0;
-    int bucket = 0;
-    int n_pre = 0, n_tail = 0;
-    size_t pre_off = 0, tail_off = 0;
-};
-
 NraScoreParams to_params(const nra_scoring_t& sc)
 {
     NraScoreParams p;
@@ -406,9 +398,6 @@ uint32_t next_epoch()
     return e;
 }
 
-// k_joint_sweep (reverse and tail sweeps): the step loop stops when the lane of the read's last row has taken the last column
-int64_t joint_cells(int R, int ncols, int qlen) { return (int64_t)64 * R * ((int64_t)ncols + std::min(63, std::max(qlen - 1, 0) / R)); }
-
 }  // namespace
 
 extern "C" int nra_copy_h2d(void* dst, const void* src, size_t bytes) { return (int)copy_h2d(dst, src, bytes); }
@@ -420,23 +409,15 @@ struct nra_batch {
     Arena keep_arena;          // 2D: column states kept from one routed grid for the next
     // 2D: what nra_batch2d_set_cells needs from the reads part
     std::vector<NraDevRead> host_reads;
-    std::vector<uint8_t> chained_reads;
-    std::string jr_left, jr_unit1, jr_mid, jr_unit2, jr_right;
+    Region2D jr;
     nra_scoring_t scoring{};
     size_t n_q2bit_words = 0;
     bool reads_have_n = false;
-    // 2D: the reverse sweep of a read (the R side of the junction, A) depends on the read, R and the strand
-    // only: a later cell list of the same batch reuses it (rev_strand: strand it was made for, 0 = not made)
-    std::vector<int8_t> rev_strand;
-    std::vector<std::pair<int32_t, int8_t>> rev_pending;    // made by the next run
-    // 2D: rows-per-lane bucket and partner of every read, fixed when the reads are packed: the packed sweeps
-    // (k_joint_pk16) take two reads per wave, and the state they leave at the end of L depends on the read and
-    // its strand only, so it is kept like the reverse sweeps (lst_strand / lst_pending)
-    std::vector<int32_t> jbucket, jpair_of;
-    std::vector<NraJointPairTask> jpairs;
-    bool jpack_l = false, jpack_r = false;
-    std::vector<int8_t> lst_strand;
-    std::vector<std::pair<int32_t, int8_t>> lst_pending;
+    // 2D: what is fixed when the reads are packed, what the batch carries from one cell list to the next, and what the
+    // next run makes valid (nra_plan2d.h)
+    Reads2D r2;
+    Carried2D carried;
+    Pending2D pending;
     DevBuf<int32_t> jlstate, jrstate;            // packed wave states at the end of L / of rev(R) outside the window
     DevBuf<NraJointPairTask> jlpk_tasks, jrpk_tasks;
     int kind = 0;              // 1 = 1D, 2 = 2D
@@ -471,7 +452,7 @@ struct nra_batch {
     // B(k1) / A(k2), one combine task per read
     DevBuf<int32_t> jfs, jrs, jfb, jra;
     DevBuf<NraJointCombineTask> jcomb_tasks;
-    bool joint_v2 = false, joint_v2_prev = false;
+    bool joint_v2 = false;
     bool joint_chain = false;                   // ... with the MID part as column-parallel scans on column states (k_joint_midscan)
     std::vector<JointGroup> jgroups;
     bool all_strands_given = false;             // 2D: every read came with its strand, no probe needed
@@ -523,20 +504,8 @@ struct nra_batch {
     DevBuf<uint32_t> cell_first, cell_cnt;
     DevBuf<int8_t> strand_in, strand_out;
     bool have_strand_in = false;
-    // 2D routed grids: the column states the prefix sweep (at every k1 of keep_rows) and the extended reverse sweep (at
-    // every k2) left, kept for a later grid whose cells lie inside (nra_batch2d_invalidate / other strands drop them)
-    bool keep_valid = false, keep_pending = false;
-    std::vector<NraGridRow> keep_rows;
-    std::vector<NraGridRow> cur_rows;           // the current routed grid's rows (nra_batch2d_refine checks what a refinement can ask for)
-    int32_t cur_step1 = 0, cur_step2 = 0;
-    std::vector<int8_t> keep_strand;
-    std::vector<uint64_t> keep_state_off, keep_rs_off;
-    std::vector<int32_t> keep_ra_off;
     bool keep_off = false;                      // set for one retry: this cell list keeps nothing (the kept states did not fit)
     int joint_keep = 0;                         // this cell list: 0 = nothing kept, 1 = sweeps that keep, 2 = no sweeps, kept states
-    // 2D: the packed sweep of rev(R) up to the window is valid for this strand of the read (like lst_strand for L)
-    std::vector<int8_t> rpk_strand;
-    std::vector<std::pair<int32_t, int8_t>> rpk_pending;
     // 2D: flank sweeps enqueued ahead of the cell list (nra_batch2d_sweep_flanks): buffers of their own, alive as long as
     // the batch (the cell list's pool / reads / task arrays are rebuilt in place while these kernels run)
     DevBuf<uint8_t> warm_pool;
@@ -1499,77 +1468,35 @@ int nra_batch2d_create_reads(int device, const nra_joint_region_t* reg, int32_t 
     int rc = common_init(b, device, sc, flags);
     if (rc) return rc;
     b->scoring = *sc;
-    b->jr_left.assign(reg->left ? reg->left : "", (size_t)reg->left_len);
-    b->jr_unit1.assign(reg->unit1, (size_t)reg->unit1_len);
-    b->jr_mid.assign(reg->mid ? reg->mid : "", (size_t)reg->mid_len);
-    b->jr_unit2.assign(reg->unit2, (size_t)reg->unit2_len);
-    b->jr_right.assign(reg->right ? reg->right : "", (size_t)reg->right_len);
+    b->jr.left.assign(reg->left ? reg->left : "", (size_t)reg->left_len);
+    b->jr.unit1.assign(reg->unit1, (size_t)reg->unit1_len);
+    b->jr.mid.assign(reg->mid ? reg->mid : "", (size_t)reg->mid_len);
+    b->jr.unit2.assign(reg->unit2, (size_t)reg->unit2_len);
+    b->jr.right.assign(reg->right ? reg->right : "", (size_t)reg->right_len);
 
     PackedReads pr;
     rc = pack_reads(n_reads, seqs, seq_off, nullptr, 1, pr, NRA_MAX_QLEN);
     if (rc) return rc;
-    // Reads longer than one register block (3072 bases), or whose scores do not fit the int32 cells of the
-    // joint sweeps, are scored cell by cell in chained row blocks with int64 cells (rare: a long amplicon).
-    b->chained_reads.assign((size_t)n_reads, 0);
-    for (int32_t r = 0; r < n_reads; ++r)
-        b->chained_reads[r] = pr.reads[r].qlen > NRA_MAX_QLEN_1BLOCK || max_score(sc, pr.reads[r].qlen) > kScoreCapPk16;
-    b->lst_strand.assign((size_t)n_reads, 0);
-    uint64_t jpack_ints = 0;
-    {
-        // rows-per-lane bucket of every read (measured on config 3, 5000 reads, R = 13..28: folding buckets of
-        // fewer than 2048 reads into the next within 4 rows beats (1024, 2) and wider spans), and its partner
-        std::vector<std::vector<int32_t>> by_bucket((size_t)kNumR);
-        for (int32_t r = 0; r < n_reads; ++r)
-            if (pr.reads[r].qlen > 0 && !b->chained_reads[r]) by_bucket[rows_for_qlen(pr.reads[r].qlen)].push_back(r);
-        fold_small_buckets(by_bucket, 2048, 4);
-        b->jbucket.assign((size_t)n_reads, -1);
-        b->jpair_of.assign((size_t)n_reads, -1);
-        uint64_t ints = 0;
-        for (int bi = 0; bi < kNumR; ++bi) {
-            const auto& v = by_bucket[bi];
-            for (size_t i = 0; i < v.size(); i += 2) {
-                NraJointPairTask t{};
-                t.read_a = v[i]; t.read_b = i + 1 < v.size() ? v[i + 1] : -1;
-                t.state = ints;
-                ints += (uint64_t)NRA_JOINT_NPSTATE(kRList[bi]) * 64;
-                b->jpair_of[t.read_a] = (int32_t)b->jpairs.size();
-                if (t.read_b >= 0) b->jpair_of[t.read_b] = (int32_t)b->jpairs.size();
-                b->jpairs.push_back(t);
-            }
-            for (int32_t r : v) b->jbucket[r] = bi;
-        }
-        // the packed cells hold what the 1D sweeps hold (nra_pk16.h), without the doubling of the origin bit
-        const int o1 = sc->gap_open1 + sc->gap_ext1, o2 = sc->gap_open2 + sc->gap_ext2;
-        const bool fits = o1 >= sc->mismatch && o1 >= sc->sc_ambi && sc->match + o1 <= 127 && sc->gap_ext1 <= 256 &&
-                          sc->gap_ext2 <= 256 && o2 + sc->mismatch + sc->sc_ambi <= 700 &&
-                          (flags & (NRA_F_BRUTE_FORCE | NRA_F_NO_JOINT_PACK)) == 0 && ints * 4 <= (4ull << 30);
-        auto cols_ok = [&](int64_t flank) {
-            const int64_t c = NRA_JOINT_PACKED_COLS(flank);
-            return c >= NRA_JOINT_PACKED_MIN_COLS && max_score(sc, std::min<int64_t>(c, NRA_MAX_QLEN_1BLOCK)) <= 27000;
-        };
-        b->jpack_l = fits && ints > 0 && cols_ok(reg->left_len);
-        b->jpack_r = fits && ints > 0 && cols_ok(reg->right_len);
-        jpack_ints = ints;
-    }
+    plan_2d_reads(pr.reads, reg->left_len, reg->right_len, sc, flags, b->r2);
+    b->carried.init(n_reads);
+    const uint64_t jpack_ints = b->r2.jpack_ints;
     b->arena.expect(pr.q2bit.size() * 6 + (size_t)n_reads * 96 + (size_t)reg->left_len + (size_t)reg->right_len + (1u << 20) +
-                    ((b->jpack_l ? jpack_ints : 0) + (b->jpack_r ? jpack_ints : 0)) * 4);
+                    ((b->r2.jpack_l ? jpack_ints : 0) + (b->r2.jpack_r ? jpack_ints : 0)) * 4);
     HIP_TRY(b->q2bit.upload(pr.q2bit));
     HIP_TRY(b->qnmask.upload(pr.nmask));
     b->n_q2bit_words = pr.q2bit.size();
     b->reads_have_n = pr.has_n;
     b->host_reads = std::move(pr.reads);
-    b->rev_strand.assign((size_t)n_reads, 0);
-    b->rpk_strand.assign((size_t)n_reads, 0);
-    if (b->jpack_l) HIP_TRY(b->jlstate.alloc((size_t)jpack_ints));
-    if (b->jpack_r) HIP_TRY(b->jrstate.alloc((size_t)jpack_ints));
-    if ((b->jpack_l || b->jpack_r) && reg->left_len >= 1 && reg->right_len >= 2 && n_reads > 0) {
+    if (b->r2.jpack_l) HIP_TRY(b->jlstate.alloc((size_t)jpack_ints));
+    if (b->r2.jpack_r) HIP_TRY(b->jrstate.alloc((size_t)jpack_ints));
+    if ((b->r2.jpack_l || b->r2.jpack_r) && reg->left_len >= 1 && reg->right_len >= 2 && n_reads > 0) {
         // what flank sweeps ahead of a cell list read (nra_batch2d_sweep_flanks): L and rev(R) alone, the oriented reads,
         // the pair tasks -- buffers of the batch, not of a cell list
         std::vector<uint8_t> pool;
         bool has_n = b->reads_have_n;
         NraDevRegion d{};
-        d.p1_off = pool_append(pool, b->jr_left.data(), reg->left_len, nullptr, 0, 0, has_n);
-        std::string rr(b->jr_right);
+        d.p1_off = pool_append(pool, b->jr.left.data(), reg->left_len, nullptr, 0, 0, has_n);
+        std::string rr(b->jr.right);
         std::reverse(rr.begin(), rr.end());
         d.pr_off = pool_append(pool, rr.data(), reg->right_len, nullptr, 0, 0, has_n);
         d.p2_off = d.p3_off = (uint32_t)pool.size();
@@ -1579,7 +1506,7 @@ int nra_batch2d_create_reads(int device, const nra_joint_region_t* reg, int32_t 
         HIP_TRY(b->warm_pool.upload(pool));
         HIP_TRY(b->warm_region.upload(std::vector<NraDevRegion>(1, d)));
         HIP_TRY(b->warm_reads.alloc((size_t)n_reads));
-        HIP_TRY(b->warm_tasks.alloc(2 * b->jpairs.size()));
+        HIP_TRY(b->warm_tasks.alloc(2 * b->r2.jpairs.size()));
         b->warm_built = true;
     }
     HIP_TRY(b->jsnap.alloc(b->n_q2bit_words * 16 * 3));    // R side of the junction per read base: kept across cell lists
@@ -1596,72 +1523,6 @@ int nra_batch2d_create_reads(int device, const nra_joint_region_t* reg, int32_t 
 }  // extern "C"
 
 namespace {
-
-using GridRow = NraGridRow;
-// rows: the cells of every read.  keep: the repeat counts of every read the sweeps leave column states at, when these
-// are kept for a later, finer grid (same layout: k1lo, n1 / k2lo, n2 at step 1; a superset of the read's cells).
-struct JointGrid { int32_t step1, step2; const GridRow* rows; const GridRow* keep; };
-
-// first index i in [0, count] with start + i * step >= x  (numpy.searchsorted(grid, x, side="left") on the grid values)
-int32_t grid_lower_bound(int32_t start, int32_t step, int32_t count, double x)
-{
-    if (count <= 0) return 0;
-    double f = std::ceil((x - (double)start) / (double)step);
-    int64_t i = f < 0 ? 0 : (f > (double)count ? count : (int64_t)f);
-    while (i > 0 && (double)start + (double)(i - 1) * step >= x) --i;           // rounding of the quotient
-    while (i < count && (double)start + (double)i * step < x) ++i;
-    return (int32_t)i;
-}
-
-// The reference's routing of reads to the cells of one grid round (nanoRepeat_joint.py:397-409 round 2, :315-330
-// round 3): read r takes the grid values g of axis a with lo_a[r] <= g < hi_a[r]; none on one axis = no cells.
-int route_grid(int32_t n_reads, int32_t start1, int32_t step1, int32_t count1, const double* lo1, const double* hi1,
-               int32_t start2, int32_t step2, int32_t count2, const double* lo2, const double* hi2,
-               std::vector<GridRow>& rows, int64_t& n_cells, std::vector<GridRow>* keep = nullptr)
-{
-    if (n_reads < 0 || step1 <= 0 || step2 <= 0 || count1 < 0 || count2 < 0 || start1 < 0 || start2 < 0)
-        return fail(NRA_E_ARG, "bad grid (steps > 0, starts and counts >= 0)");
-    if (n_reads > 0 && (!lo1 || !hi1 || !lo2 || !hi2)) return fail(NRA_E_ARG, "NULL grid bound array");
-    if ((int64_t)start1 + (int64_t)step1 * count1 > 0x3fffffff || (int64_t)start2 + (int64_t)step2 * count2 > 0x3fffffff)
-        return fail(NRA_E_RANGE, "grid values too large");
-    rows.assign((size_t)n_reads, GridRow{0, 0, 0, 0});
-    n_cells = 0;
-    for (int32_t r = 0; r < n_reads; ++r) {
-        if (!(lo1[r] < hi1[r]) || !(lo2[r] < hi2[r])) continue;         // (also drops NaN bounds)
-        const int32_t a1 = grid_lower_bound(start1, step1, count1, lo1[r]), b1 = grid_lower_bound(start1, step1, count1, hi1[r]);
-        const int32_t a2 = grid_lower_bound(start2, step2, count2, lo2[r]), b2 = grid_lower_bound(start2, step2, count2, hi2[r]);
-        if (b1 <= a1 || b2 <= a2) continue;
-        rows[(size_t)r] = GridRow{start1 + a1 * step1, b1 - a1, start2 + a2 * step2, b2 - a2};
-        n_cells += (int64_t)(b1 - a1) * (b2 - a2);
-    }
-    if (keep) {
-        // What a finer grid inside the same bounds can ask of a read: every count k with lo <= k < hi -- and, the way the
-        // reference refines (within one coarse step of a size between the coarse grid's first and last value), nothing
-        // more than one step below the first or above the last of the read's values.  A unit-step axis keeps its own.
-        keep->assign((size_t)n_reads, GridRow{0, 0, 0, 0});
-        auto span = [](int32_t first, int32_t n, int32_t step, double lo, double hi, int32_t& a, int32_t& count) {
-            const int32_t last = first + (n - 1) * step;
-            int64_t ka = first, kb = last;
-            if (step > 1) {
-                const double cl = std::ceil(lo), ch = std::ceil(hi);
-                const int64_t klo = cl < 0 ? 0 : (cl > 1e9 ? (int64_t)1e9 : (int64_t)cl);
-                const int64_t khi = ch > 1e9 ? (int64_t)1e9 : (int64_t)ch - 1;
-                ka = std::max<int64_t>(std::max<int64_t>(klo, (int64_t)first - step), 0);
-                kb = std::min<int64_t>(khi, (int64_t)last + step - 1);
-                ka = std::min<int64_t>(ka, first); kb = std::max<int64_t>(kb, last);
-            }
-            a = (int32_t)ka; count = (int32_t)(kb - ka + 1);
-        };
-        for (int32_t r = 0; r < n_reads; ++r) {
-            const GridRow& g = rows[(size_t)r];
-            if (g.n1 <= 0 || g.n2 <= 0) continue;
-            GridRow& k = (*keep)[(size_t)r];
-            span(g.k1lo, g.n1, step1, lo1[r], hi1[r], k.k1lo, k.n1);
-            span(g.k2lo, g.n2, step2, lo2[r], hi2[r], k.k2lo, k.n2);
-        }
-    }
-    return NRA_OK;
-}
 
 int set_cells_common(nra_batch* b, const int8_t* read_strand, int64_t n_cells, const int32_t* cell_read,
                      const int32_t* cell_k1, const int32_t* cell_k2, const JointGrid* grid);
@@ -1724,7 +1585,7 @@ int nra_batch2d_set_grid(nra_batch_t* b, const int8_t* read_strand,
         // and libraries on the device): give the arena back and set the grid again without keeping -- a later, finer grid
         // then sweeps again, nra_batch2d_refine says NRA_E_STATE, the results are the same.
         b->keep_arena.release();
-        b->keep_valid = false;
+        b->carried.keep_valid = false;
         b->keep_off = true;
         rc = set_cells_common(b, read_strand, n, nullptr, nullptr, nullptr, &grid);
         b->keep_off = false;
@@ -1736,24 +1597,20 @@ int nra_batch2d_set_grid(nra_batch_t* b, const int8_t* read_strand,
 
 namespace {
 
-// A read's MID scans as several tasks of at most kMidscanChunk k1 values: a wave's scans are one dependent chain (load a
-// column state, 1 + |mid| columns of two lane scans each, store), so more, shorter waves hide it better than one wave per
-// read (config 3, round 3: 5 k1 values per read).  The pieces differ in where their lists, outputs and slots begin only.
-void push_midscan(std::vector<NraJointTask>& jtail, const NraJointTask& whole, uint64_t ints_per_k1)
+// the budget of the kept column states, in bytes
+// (NRA_JOINT_KEEP_BUDGET_GB in the environment overrides the built-in budget; 0 keeps nothing)
+uint64_t joint_keep_budget()
 {
-    const int kMidscanChunk = 3;            // config 3, device ms per step: whole reads 6.23, 1: 6.23, 2: 6.18, 3: 6.15, 4: 6.16, 6: 6.40
-    for (int32_t c = 0; c < whole.nk1; c += kMidscanChunk) {
-        NraJointTask t = whole;
-        t.k1_off = whole.k1_off + c; t.nk1 = std::min<int32_t>(kMidscanChunk, whole.nk1 - c);
-        t.out = whole.out + c; t.pstate = whole.pstate + (uint64_t)c * ints_per_k1;
-        jtail.push_back(t);
-    }
+    const char* budget_env = getenv("NRA_JOINT_KEEP_BUDGET_GB");
+    return budget_env ? (uint64_t)(atof(budget_env) * (double)(1ull << 30)) : (uint64_t)NRA_JOINT_KEEP_BUDGET;
 }
 
+// The phases of a cell list in their fixed order: wait and account, reset, the strand-only plan (plan_2d_strands), its
+// uploads, its kernels, the plan of the cells (plan_2d_cells), its uploads, the statistics.
 int set_cells_common(nra_batch* b, const int8_t* read_strand, int64_t n_cells, const int32_t* cell_read,
                      const int32_t* cell_k1, const int32_t* cell_k2, const JointGrid* grid)
 {
-    if (n_cells > 0x7ff00000ll) return fail(NRA_E_RANGE, "too many cells");
+    if (!cells_2d_countable(n_cells)) return fail(NRA_E_RANGE, "too many cells");
     HIP_TRY(hipSetDevice(b->device));
     if (b->ran) HIP_TRY(hipStreamSynchronize(b->stream));      // the previous list's kernels own the buffers
     if (b->flanks_enqueued) {                                  // ... also when only its first part was enqueued
@@ -1768,328 +1625,63 @@ int set_cells_common(nra_batch* b, const int8_t* read_strand, int64_t n_cells, c
     b->have_cells = false;
     b->ran = false;
     const bool had_warm = b->warm_pending;                     // flank sweeps enqueued ahead of this list (nra_batch2d_sweep_flanks)
-    b->rev_pending.clear();
-    b->lst_pending.clear();
-    b->rpk_pending.clear();
     b->cell_arena.reset();
     ArenaScope arena_scope(&b->cell_arena);
     b->buckets.clear();
     b->jgroups.clear();
     b->n_cands = n_cells;
     const int32_t n_reads = b->n_reads;
-    const int32_t flags = b->flags;
-    std::vector<NraDevRead> reads(b->host_reads);              // + the shadows of chained reads, below
     PhaseClock clk(g_debug_phases);
 
-    std::vector<uint32_t> first((size_t)n_reads, 0), cnt((size_t)n_reads, 0);
-    int32_t k1max = 0, k2max = 0;
-    if (grid) {
-        uint32_t c = 0;
-        for (int32_t r = 0; r < n_reads; ++r) {
-            const GridRow& g = grid->rows[(size_t)r];
-            first[r] = c; cnt[r] = (uint32_t)g.n1 * (uint32_t)g.n2;
-            c += cnt[r];
-            if (cnt[r]) {
-                k1max = std::max(k1max, g.k1lo + (g.n1 - 1) * grid->step1);
-                k2max = std::max(k2max, g.k2lo + (g.n2 - 1) * grid->step2);
-            }
-        }
-    } else
-    for (int64_t c = 0; c < n_cells; ++c) {
-        const int32_t r = cell_read[c];
-        if (r < 0 || r >= n_reads || (c > 0 && r < cell_read[c - 1]) || cell_k1[c] < 0 || cell_k2[c] < 0)
-            return fail(NRA_E_ARG, "cells must be grouped by read, k >= 0");
-        if (cnt[r] == 0) first[r] = (uint32_t)c;
-        cnt[r]++;
-        k1max = std::max(k1max, cell_k1[c]);
-        k2max = std::max(k2max, cell_k2[c]);
-    }
-    // k1 / k2 of a read's i-th listed cell
-    auto k1_of = [&](int32_t r, uint32_t i) -> int32_t {
-        if (!grid) return cell_k1[first[r] + i];
-        const GridRow& g = grid->rows[(size_t)r];
-        return g.k1lo + (int32_t)(i / (uint32_t)g.n2) * grid->step1;
+    Cells2D cl;
+    cl.read_strand = read_strand; cl.n_cells = n_cells; cl.grid = grid;
+    cl.cell_read = cell_read; cl.cell_k1 = cell_k1; cl.cell_k2 = cell_k2;
+    KeepInputs ki;
+    ki.budget = joint_keep_budget();
+    ki.keep_off = b->keep_off;
+    for (const Arena::Chunk& c : b->keep_arena.chunks) ki.held += c.size;
+    ki.device_free = [](uint64_t& free_b) {
+        size_t f = 0, total_b = 0;
+        if (hipMemGetInfo(&f, &total_b) != hipSuccess) return false;
+        free_b = f;
+        return true;
     };
-    auto k2_of = [&](int32_t r, uint32_t i) -> int32_t {
-        if (!grid) return cell_k2[first[r] + i];
-        const GridRow& g = grid->rows[(size_t)r];
-        return g.k2lo + (int32_t)(i % (uint32_t)g.n2) * grid->step2;
-    };
-    const int32_t left_len = (int32_t)b->jr_left.size(), unit1_len = (int32_t)b->jr_unit1.size(),
-                  mid_len = (int32_t)b->jr_mid.size(), unit2_len = (int32_t)b->jr_unit2.size(),
-                  right_len = (int32_t)b->jr_right.size();
-    const int64_t win = (int64_t)unit1_len * k1max + mid_len + (int64_t)unit2_len * k2max + 20;
-    if (6 * win >= 32768) return fail(NRA_E_RANGE, "repeat window too long for the 16-bit window score");
-    const int64_t tlmax = (int64_t)left_len + win - 20 + right_len;
-    if (tlmax > NRA_MAX_TLEN) return fail(NRA_E_RANGE, "template too long");
-
-    // ---- Kept column states (routed grids with every strand given, MID scans).  A grid's sweeps leave a column state at
-    // every repeat count a finer grid inside the same bounds can ask for (grid->keep), not only at its own values: such a
-    // later grid -- the reference's round 3 after round 2 -- then needs no flank, prefix or reverse sweep at all, only
-    // the MID scans and the combine.  joint_keep: 0 = nothing kept, 1 = this list sweeps and keeps, 2 = no sweeps.
-    int32_t k1max_pool = k1max, k2max_pool = k2max;
-    int keep = 0;
-    uint64_t keep_bytes = 0;
+    Plan2D plan;
     {
-        const bool brute_now = (flags & NRA_F_BRUTE_FORCE) != 0 || left_len < 1 || right_len < 2;
-        bool strands_all = read_strand != nullptr && n_reads > 0;
-        if (read_strand)
-            for (int32_t r = 0; r < n_reads; ++r) if (cnt[r] > 0 && read_strand[r] == 0) strands_all = false;
-        auto swept = [&](int32_t r) { return cnt[r] > 0 && reads[r].qlen > 0 && !b->chained_reads[r]; };
-        if (grid && grid->keep && !brute_now && strands_all && n_cells > 0 &&
-            (flags & (NRA_F_JOINT_TAILS | NRA_F_JOINT_NO_CHAIN | NRA_F_JOINT_NO_KEEP)) == 0) {
-            bool reuse = b->keep_valid && b->keep_rows.size() == (size_t)n_reads;
-            for (int32_t r = 0; reuse && r < n_reads; ++r) {
-                if (!swept(r)) continue;
-                const GridRow& g = grid->rows[(size_t)r];
-                const NraGridRow& k = b->keep_rows[(size_t)r];
-                if (b->keep_strand[(size_t)r] != read_strand[r] || k.n1 <= 0 || k.n2 <= 0 || g.k1lo < k.k1lo ||
-                    g.k1lo + (g.n1 - 1) * grid->step1 > k.k1lo + k.n1 - 1 || g.k2lo < k.k2lo ||
-                    g.k2lo + (g.n2 - 1) * grid->step2 > k.k2lo + k.n2 - 1)
-                    reuse = false;
-            }
-            if (reuse) {
-                keep = 2;
-                // a refinement may follow (nra_batch2d_refine): its MID scans read the template up to the last kept count
-                for (int32_t r = 0; r < n_reads; ++r)
-                    if (swept(r)) {
-                        const NraGridRow& k = b->keep_rows[(size_t)r];
-                        k1max_pool = std::max(k1max_pool, k.k1lo + k.n1 - 1); k2max_pool = std::max(k2max_pool, k.k2lo + k.n2 - 1);
-                    }
-            } else {
-                uint64_t bytes = 0;
-                int32_t k1hi = k1max, k2hi = k2max;
-                for (int32_t r = 0; r < n_reads; ++r) {
-                    if (!swept(r)) continue;
-                    const GridRow& k = grid->keep[(size_t)r];
-                    bytes += ((uint64_t)k.n1 * NRA_JOINT_NSTATE(kRList[b->jbucket[r]]) + (uint64_t)k.n2 * 3 * kRList[b->jbucket[r]]) * 256;
-                    k1hi = std::max(k1hi, k.k1lo + k.n1 - 1); k2hi = std::max(k2hi, k.k2lo + k.n2 - 1);
-                }
-                const int64_t tl_keep = (int64_t)left_len + (int64_t)unit1_len * k1hi + mid_len + (int64_t)unit2_len * k2hi + right_len;
-                // ... within the budget, and within half of what the device has left (what the arena holds already counts as free)
-                // (NRA_JOINT_KEEP_BUDGET_GB in the environment overrides the built-in budget; 0 keeps nothing)
-                const char* budget_env = getenv("NRA_JOINT_KEEP_BUDGET_GB");
-                const uint64_t budget = budget_env ? (uint64_t)(atof(budget_env) * (double)(1ull << 30)) : (uint64_t)NRA_JOINT_KEEP_BUDGET;
-                bool fits = bytes <= budget && tl_keep <= NRA_MAX_TLEN && !b->keep_off;
-                keep_bytes = bytes;
-                if (fits) {
-                    size_t held = 0, free_b = 0, total_b = 0;
-                    for (const Arena::Chunk& c : b->keep_arena.chunks) held += c.size;
-                    if (bytes > held) fits = hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes - held <= free_b / 2;
-                }
-                if (fits) { keep = 1; k1max_pool = k1hi; k2max_pool = k2hi; }
-            }
-        }
-        if (keep != 2) b->keep_valid = false;       // what was kept is replaced (1) or not looked at again (0)
-        b->keep_pending = keep == 1;
-        b->joint_keep = keep;
-        if (keep == 1) {
-            // what the arena holds is handed out again; if it is too small it goes back BEFORE the larger chunk is asked for
-            // (old and new together may not fit)
-            if (g_debug_phases)
-                fprintf(stderr, "[nra] kept column states: %.3f GB wanted, the arena holds %.3f GB in %zu chunks -> %s\n", (double)keep_bytes / 1073741824.0,
-                        (double)b->keep_arena.capacity() / 1073741824.0, b->keep_arena.chunks.size(),
-                        b->keep_arena.capacity() < keep_bytes + (2u << 20) ? "given back, asked for again" : "handed out again");
-            if (b->keep_arena.capacity() < keep_bytes + (2u << 20)) b->keep_arena.release();
-            else b->keep_arena.reset();
-            b->keep_rows.assign(grid->keep, grid->keep + n_reads);
-            b->keep_strand.assign(read_strand, read_strand + n_reads);
-            b->keep_state_off.assign((size_t)n_reads, 0);
-            b->keep_rs_off.assign((size_t)n_reads, 0);
-            b->keep_ra_off.assign((size_t)n_reads, 0);
-        }
+        const int rc1 = plan_2d_strands(b->jr, b->host_reads, b->reads_have_n, b->r2, b->flags, cl, ki, clk, b->carried,
+                                        b->pending, plan);
+        if (rc1) return rc1;
     }
-
-    clk.mark("2D cells: first/count");
-    std::vector<uint8_t> pool;
-    bool has_n = b->reads_have_n;
-    NraDevRegion d{};
-    d.p1_off = pool_append(pool, b->jr_left.data(), left_len, b->jr_unit1.data(), unit1_len, k1max_pool, has_n);
-    d.p2_off = pool_append(pool, b->jr_mid.data(), mid_len, b->jr_unit2.data(), unit2_len, k2max_pool, has_n);
-    d.p3_off = pool_append(pool, b->jr_right.data(), right_len, nullptr, 0, 0, has_n);
-    {   // rev(R) + rev(u2)^k2max: the reverse sweeps (the extended ones run on into the second repeat)
-        std::string rr(b->jr_right), ru(b->jr_unit2);
-        std::reverse(rr.begin(), rr.end());
-        std::reverse(ru.begin(), ru.end());
-        d.pr_off = pool_append(pool, rr.data(), right_len, ru.data(), unit2_len, k2max_pool, has_n);
+    const int keep = plan.keep;
+    b->joint_keep = keep;
+    if (keep == 1) {
+        // what the arena holds is handed out again; if it is too small it goes back BEFORE the larger chunk is asked for
+        // (old and new together may not fit)
+        if (g_debug_phases)
+            fprintf(stderr, "[nra] kept column states: %.3f GB wanted, the arena holds %.3f GB in %zu chunks -> %s\n", (double)plan.keep_bytes / 1073741824.0,
+                    (double)b->keep_arena.capacity() / 1073741824.0, b->keep_arena.chunks.size(),
+                    b->keep_arena.capacity() < plan.keep_bytes + (2u << 20) ? "given back, asked for again" : "handed out again");
+        if (b->keep_arena.capacity() < plan.keep_bytes + (2u << 20)) b->keep_arena.release();
+        else b->keep_arena.reset();
     }
-    d.l1 = left_len; d.m1 = unit1_len; d.l2 = mid_len; d.m2 = unit2_len; d.l3 = right_len;
-    pool.push_back(0);
-    b->has_n = has_n ? 1 : 0;
-    std::vector<NraDevRegion> dregs(1, d);
-
-    // (the rows-per-lane bucket of a read was fixed when the reads were packed)
-    // (measured and dropped: a bucket as 2 - 4 sub-buckets with kernel chains of their own -- the short kernels at the
-    // end of one chain beside the long ones of the next -- is slower, 7.1 -> 7.7 / 8.7 / 10.5 ms of device time on config 3)
-    const int kChainBucket = kNumR;
-    std::vector<std::vector<int32_t>> by_bucket((size_t)kChainBucket + 1);
-    bool empty_reads_listed = false;
-    for (int32_t r = 0; r < n_reads; ++r) {
-        if (cnt[r] > 0 && reads[r].qlen == 0) empty_reads_listed = true;
-        if (cnt[r] == 0 || reads[r].qlen == 0) continue;
-        by_bucket[b->chained_reads[r] ? kChainBucket : b->jbucket[r]].push_back(r);
-    }
-    const std::vector<int32_t>& chain_reads = by_bucket[kChainBucket];
-    std::vector<NraPairTask> pair_tasks;
-    std::vector<NraTask> queue_tasks, probe_tasks;
-    std::vector<int32_t> queue_count, probe_count;
-    std::vector<NraJointTask> jbwd, jpre, jtail;
-    std::vector<NraJointPairTask> jlpk, jrpk;
-    std::vector<uint8_t> pair_l((size_t)b->jpairs.size(), 0), pair_r((size_t)b->jpairs.size(), 0);
-    const int colsL = NRA_JOINT_PACKED_COLS(left_len), colsR = NRA_JOINT_PACKED_COLS(right_len);
-    std::vector<int32_t> k1list;
-    // junction decomposition needs a base left of the window and two bases of R
-    b->brute = (flags & NRA_F_BRUTE_FORCE) != 0 || left_len < 1 || right_len < 2;
-    // a routed grid: every read's cells are a full product (k1 values) x (one k2 progression) -> junction at the end
-    // of mid.  The state kept from earlier cell lists differs between the two forms: switching drops it.
-    b->joint_v2 = grid != nullptr && !b->brute && (flags & NRA_F_JOINT_TAILS) == 0;
-    b->joint_chain = b->joint_v2 && (flags & NRA_F_JOINT_NO_CHAIN) == 0;
-    // k_joint_combine writes every cell of its reads, found or not: the cell arrays need no clearing unless some
-    // cells belong to no combine task (empty reads, reads scored cell by cell)
-    b->cells_need_clear = !b->joint_v2 || empty_reads_listed || !chain_reads.empty();
-    if (b->joint_v2 != b->joint_v2_prev) {
-        std::fill(b->rev_strand.begin(), b->rev_strand.end(), (int8_t)0);
-        b->joint_v2_prev = b->joint_v2;
-    }
-    std::vector<NraJointCombineTask> jcomb;
-    std::vector<uint64_t> rs_off((size_t)n_reads, 0);
-    std::vector<int32_t> ra_off((size_t)n_reads, 0);
-    uint64_t rs_total = 0, fs_total = 0;
-    int64_t ra_total = 0, fb_total = 0;
-    // wave states of one group of reads (NRA_F_TEST_CHAIN: one read per group, to exercise the reuse)
-    // The buckets run concurrently, each in its own part of the state buffer.
-    size_t n_nonempty = 0;
-    for (const auto& v : by_bucket) n_nonempty += v.empty() ? 0 : 1;
-    const uint64_t state_cap = (flags & NRA_F_TEST_CHAIN) ? 1 : (uint64_t)NRA_JOINT_STATE_CAP_INTS / std::max<size_t>(n_nonempty, 1);
-    uint64_t state_base = 0;
-    b->all_strands_given = read_strand != nullptr && n_reads > 0;
-    if (read_strand)
-        for (int32_t r = 0; r < n_reads; ++r) if (cnt[r] > 0 && read_strand[r] == 0) b->all_strands_given = false;
-    int64_t alg_cells = 0;
-    std::vector<int32_t> ks;
-    std::vector<int> bucket_ids;                     // by_bucket index of every entry of b->buckets
-    if (!b->brute) {
-        jbwd.reserve((size_t)n_reads); jpre.reserve((size_t)n_reads); jcomb.reserve(b->joint_v2 ? (size_t)n_reads : 0);
-        jtail.reserve((size_t)n_reads * 2);
-    }
-
-    // ---- part 1: what depends on the reads and their strands only -- the reverse sweeps over R and the packed
-    // sweeps of the flanks outside the scoring window -- plus the strand probes.  With every strand given these
-    // kernels are enqueued right here, before the (longer) list of prefix and tail sweeps is built and uploaded:
-    // the host's share of a round then runs beside the device's first third of it.
-    for (int bi = kChainBucket; bi >= 0; --bi) {
-        if (by_bucket[bi].empty()) continue;
-        Bucket bk;
-        bk.chain = bi == kChainBucket;
-        bk.R = bk.chain ? NRA_CHAIN_R : kRList[bi];
-        bk.pair_off = pair_tasks.size();
-        bk.jbwd_off = jbwd.size();
-        bk.jlpk_off = jlpk.size(); bk.jrpk_off = jrpk.size();
-        bk.probe_off = probe_tasks.size();
-        const bool per_cell = b->brute || bk.chain;      // one DP per (read, cell) instead of the joint sweeps
-        for (int32_t r : by_bucket[bi]) {
-            if (!per_cell) {
-                // one reverse sweep over R per read and strand, kept for later cell lists of the batch
-                const int8_t given = read_strand ? read_strand[r] : 0;
-                const int32_t pi = b->jpair_of[r];
-                const NraJointPairTask& pair = b->jpairs[(size_t)pi];
-                const bool stale = given == 0 || b->rev_strand[r] != given;     // nothing kept for this read and strand
-                // the packed sweep of rev(R) up to the window: once per pair and strand, kept for later cell lists
-                auto packed_r = [&]() {
-                    if (pair_r[pi]) return;
-                    bool need = false;
-                    for (int32_t q : {pair.read_a, pair.read_b})
-                        if (q >= 0 && (read_strand == nullptr || read_strand[q] == 0 || b->rpk_strand[q] != read_strand[q])) need = true;
-                    if (!need) return;
-                    pair_r[pi] = 1; jrpk.push_back(pair); bk.cells_sweep += (int64_t)2 * 64 * bk.R * colsR;
-                    for (int32_t q : {pair.read_a, pair.read_b}) {
-                        if (q < 0) continue;
-                        b->rpk_strand[q] = 0;
-                        b->rpk_pending.push_back({q, read_strand ? read_strand[q] : (int8_t)0});
-                    }
-                };
-                if (keep == 2) {
-                    // every column state this list needs was kept: no sweep on either side
-                    rs_off[(size_t)r] = b->keep_rs_off[(size_t)r]; ra_off[(size_t)r] = b->keep_ra_off[(size_t)r];
-                } else if (b->joint_v2) {
-                    // the reverse sweep runs on over rev(u2)^k2hi and leaves a column state per k2 of the read (of its
-                    // kept range, keep == 1); the packed sweep of rev(R) up to the window is kept in any case
-                    const GridRow& gr = grid->rows[(size_t)r];
-                    const int32_t k2lo = keep == 1 ? grid->keep[(size_t)r].k2lo : gr.k2lo, k2n = keep == 1 ? grid->keep[(size_t)r].n2 : gr.n2,
-                                  k2step = keep == 1 ? 1 : grid->step2;
-                    NraJointTask tb{}; tb.read = r; tb.k2lo = k2lo; tb.k2step = k2step; tb.n2 = k2n;
-                    tb.state = rs_total; tb.out = (int32_t)ra_total;
-                    rs_off[(size_t)r] = rs_total; ra_off[(size_t)r] = (int32_t)ra_total;
-                    if (keep == 1) { b->keep_rs_off[(size_t)r] = rs_total; b->keep_ra_off[(size_t)r] = (int32_t)ra_total; }
-                    rs_total += (uint64_t)k2n * 3 * 64 * (uint64_t)bk.R; ra_total += k2n;
-                    if (b->jpack_r) {
-                        tb.resume = 1; tb.pstate = pair.state; tb.phalf = pair.read_b == r ? 1 : 0;
-                        packed_r();
-                    }
-                    jbwd.push_back(tb);
-                    bk.cells_sweep += joint_cells(bk.R, d.l3 - (b->jpack_r ? colsR : 0) + d.m2 * (k2lo + k2step * (k2n - 1)), reads[r].qlen);
-                    if (stale) { b->rev_strand[r] = 0; b->rev_pending.push_back({r, given}); }
-                } else if (stale) {
-                    NraJointTask tb{}; tb.read = r; tb.k2step = 1; tb.n2 = 1;
-                    if (b->jpack_r) {
-                        tb.resume = 1; tb.pstate = pair.state; tb.phalf = pair.read_b == r ? 1 : 0;
-                        packed_r();
-                    }
-                    jbwd.push_back(tb);
-                    bk.cells_sweep += joint_cells(bk.R, d.l3 - (b->jpack_r ? colsR : 0), reads[r].qlen);
-                    b->rev_strand[r] = 0;
-                    b->rev_pending.push_back({r, given});
-                }
-                // the L side up to the window: swept once per pair and strand, kept for later cell lists
-                if (keep != 2 && b->jpack_l && (given == 0 || b->lst_strand[r] != given) && !pair_l[pi]) {
-                    pair_l[pi] = 1; jlpk.push_back(pair); bk.cells_sweep += (int64_t)2 * 64 * bk.R * colsL;
-                    for (int32_t q : {pair.read_a, pair.read_b}) {
-                        if (q < 0) continue;
-                        b->lst_strand[q] = 0;
-                        b->lst_pending.push_back({q, read_strand ? read_strand[q] : (int8_t)0});
-                    }
-                }
-            }
-            // strand probe against the read's first listed cell: half A = template, half B = its revcomp
-            // (no probe runs when every strand is given)
-            if (!bk.chain) {
-                if (!b->all_strands_given) {
-                    NraPairTask t{};
-                    t.read = r; t.k1a = t.k1b = k1_of(r, 0); t.k2a = t.k2b = k2_of(r, 0);
-                    t.out_a = 2 * r; t.out_b = 2 * r + 1; t.flags = 3;     // B = reverse complement; raw scores
-                    pair_tasks.push_back(t);
-                    bk.cells_pair += 2 * sweep_cells(bk.R, d.l1 + d.m1 * t.k1a + d.l2 + d.m2 * t.k2a + d.l3);
-                }
-            } else {
-                // chained: the read and a reverse-complemented shadow of it against the same template
-                NraDevRead shadow = reads[r];
-                shadow.rc = 1;
-                const int32_t sh = (int32_t)reads.size();
-                reads.push_back(shadow);
-                probe_tasks.push_back(NraTask{r, k1_of(r, 0), k2_of(r, 0), 2 * r});
-                probe_tasks.push_back(NraTask{sh, k1_of(r, 0), k2_of(r, 0), 2 * r + 1});
-            }
-        }
-        bk.n_pair = (int)(pair_tasks.size() - bk.pair_off);
-        bk.n_jbwd = (int)(jbwd.size() - bk.jbwd_off);
-        bk.n_jlpk = (int)(jlpk.size() - bk.jlpk_off);
-        bk.n_jrpk = (int)(jrpk.size() - bk.jrpk_off);
-        bk.n_probe = (int)(probe_tasks.size() - bk.probe_off);
-        probe_count.push_back(bk.n_probe);
-        b->buckets.push_back(bk);
-        bucket_ids.push_back(bi);
-    }
+    b->has_n = plan.has_n ? 1 : 0;
+    b->brute = plan.brute;
+    b->joint_v2 = plan.joint_v2;
+    b->joint_chain = plan.joint_chain;
+    b->cells_need_clear = plan.cells_need_clear;
+    b->all_strands_given = plan.all_strands_given;
+    b->buckets = plan.buckets;                                 // (part 2 completes them, below)
     const size_t nb = b->buckets.size();
     clk.mark("2D cells: pool, strand-only tasks built");
     // one chunk for everything but the wave states, which get their own (all of it reused by the next cell list)
-    b->cell_arena.expect(b->n_q2bit_words * 16 * 13 + (size_t)n_cells * 72 + pool.size() + (size_t)n_reads * 256 + (8u << 20));
-    HIP_TRY(b->pool.upload(pool));
-    HIP_TRY(b->regions.upload(dregs));
-    HIP_TRY(b->reads.upload(reads));
-    HIP_TRY(b->reads_init.upload(reads));
-    HIP_TRY(b->pair_tasks.upload(pair_tasks));
-    HIP_TRY(b->probe_tasks.upload(probe_tasks));
-    HIP_TRY(b->probe_count.upload(probe_count));
+    b->cell_arena.expect(cell_arena_bytes(b->n_q2bit_words, n_cells, plan.pool.size(), n_reads));
+    HIP_TRY(b->pool.upload(plan.pool));
+    HIP_TRY(b->regions.upload(plan.dregs));
+    HIP_TRY(b->reads.upload(plan.reads));
+    HIP_TRY(b->reads_init.upload(plan.reads));
+    HIP_TRY(b->pair_tasks.upload(plan.pair_tasks));
+    HIP_TRY(b->probe_tasks.upload(plan.probe_tasks));
+    HIP_TRY(b->probe_count.upload(plan.probe_count));
     HIP_TRY(b->probe_dummy.alloc(2 * (size_t)n_reads));
     HIP_TRY(b->probe_score.alloc(2 * (size_t)n_reads));
     b->have_strand_in = read_strand != nullptr;
@@ -2097,23 +1689,20 @@ int set_cells_common(nra_batch* b, const int8_t* read_strand, int64_t n_cells, c
         std::vector<int8_t> v(read_strand, read_strand + n_reads);
         HIP_TRY(b->strand_in.upload(v));
     }
-    if (!chain_reads.empty()) {
-        size_t chain_cells = 0;
-        for (int32_t r : chain_reads) chain_cells += cnt[r];
-        b->chain_cap = (int)((tlmax + 127) / 64 * 64 + 64);
-        b->payload_strips = chain_strips(std::max(chain_cells, probe_tasks.size()), NRA_CHAIN_STRIPS,
-                                         (size_t)6 * 8 * (size_t)b->chain_cap);
+    if (plan.chain_cap > 0) {                                  // chained reads are listed
+        b->chain_cap = plan.chain_cap;
+        b->payload_strips = plan.payload_strips;
         HIP_TRY(b->chain_payload.alloc((size_t)b->payload_strips * 6 * (size_t)b->chain_cap));
     }
     if (!b->brute) {
-        HIP_TRY(b->jbwd_tasks.upload(jbwd));
-        HIP_TRY(b->jlpk_tasks.upload(jlpk));
-        HIP_TRY(b->jrpk_tasks.upload(jrpk));
+        HIP_TRY(b->jbwd_tasks.upload(plan.jbwd));
+        HIP_TRY(b->jlpk_tasks.upload(plan.jlpk));
+        HIP_TRY(b->jrpk_tasks.upload(plan.jrpk));
         if (b->joint_v2 && keep != 2) {
             ArenaScope kept(keep == 1 ? &b->keep_arena : &b->cell_arena);
-            if (keep == 1) b->keep_arena.expect((size_t)rs_total * 4 + (size_t)ra_total * 4 + (1u << 20));
-            HIP_TRY(b->jrs.alloc((size_t)rs_total));
-            HIP_TRY(b->jra.alloc((size_t)ra_total));
+            if (keep == 1) b->keep_arena.expect((size_t)plan.rs_total * 4 + (size_t)plan.ra_total * 4 + (1u << 20));
+            HIP_TRY(b->jrs.alloc((size_t)plan.rs_total));
+            HIP_TRY(b->jra.alloc((size_t)plan.ra_total));
         }
     }
     // events and streams: kept from one cell list to the next, more taken from the pool when needed
@@ -2136,201 +1725,29 @@ int set_cells_common(nra_batch* b, const int8_t* read_strand, int64_t n_cells, c
     }
     clk.mark("2D cells: strand-only kernels enqueued");
 
-    // ---- part 2: the sweeps that depend on the cell list
-    for (size_t bidx = 0; bidx < nb; ++bidx) {
-        const int bi = bucket_ids[bidx];
-        Bucket& bk = b->buckets[bidx];
-        bk.queue_off = queue_tasks.size();
-        bk.comb_off = jcomb.size();
-        const bool per_cell = b->brute || bk.chain;
-        const uint64_t slot = (uint64_t)NRA_JOINT_NSTATE(bk.R) * 64;
-        JointGroup g; g.R = bk.R; g.bucket = (int)bidx; g.pre_off = jpre.size(); g.tail_off = jtail.size();
-        uint64_t used = 0, state_max = 0;
-        const size_t bucket_pre0 = jpre.size(), bucket_tail0 = jtail.size();
-        for (int32_t r : by_bucket[bi]) {
-            if (!per_cell) {
-                // one prefix sweep over L + u1^k1max per read that leaves the wave state at each of the read's k1
-                // values; one tail sweep per run of cells with the same k1 and k2 in arithmetic progression (how
-                // the grid rounds list them)
-                const NraJointPairTask& pair = b->jpairs[(size_t)b->jpair_of[r]];
-                ks.clear();                                      // the read's distinct k1 values, ascending
-                if (grid) {
-                    const GridRow& gr = grid->rows[(size_t)r];
-                    for (int32_t i = 0; i < gr.n1; ++i) ks.push_back(gr.k1lo + i * grid->step1);
-                    if (keep != 0) {
-                        // kept column states: the prefix sweep (keep == 1; none at all, keep == 2) leaves one at EVERY count
-                        // of the read's kept range, the MID scans take the grid's own from among them
-                        const NraGridRow kr = keep == 1 ? grid->keep[(size_t)r] : b->keep_rows[(size_t)r];
-                        const uint64_t q3 = (uint64_t)3 * (uint64_t)reads[r].qlen;
-                        NraJointTask t{}; t.read = r; t.k1_off = (int32_t)k1list.size(); t.nk1 = gr.n1;
-                        t.k1 = kr.k1lo; t.k2step = 1;
-                        t.out = (int32_t)fb_total; t.pstate = fs_total;
-                        k1list.insert(k1list.end(), ks.begin(), ks.end());
-                        bk.cells_sweep += (int64_t)64 * bk.R * gr.n1 * (1 + d.l2);
-                        if (keep == 1) {
-                            NraJointTask tp{}; tp.read = r; tp.k1_off = (int32_t)k1list.size(); tp.nk1 = kr.n1;
-                            tp.state = used; tp.k2step = 1;
-                            if (b->jpack_l) { tp.resume = 1; tp.pstate = pair.state; tp.phalf = pair.read_b == r ? 1 : 0; }
-                            jpre.push_back(tp);
-                            for (int32_t i = 0; i < kr.n1; ++i) k1list.push_back(kr.k1lo + i);
-                            bk.cells_sweep += (int64_t)64 * bk.R * (d.l1 + d.m1 * (kr.k1lo + kr.n1 - 1) - 1 - (b->jpack_l ? colsL : 0));
-                            bk.cells_sweep += (int64_t)64 * bk.R * (1 + std::min(63, std::max(reads[r].qlen - 1, 0) / bk.R));   // its drain
-                            t.state = used;                         // (bucket-relative like tp.state: both move to the bucket's base below)
-                            used += slot * (uint64_t)kr.n1;
-                            state_max = std::max(state_max, used);
-                        } else
-                            t.state = b->keep_state_off[(size_t)r] | (1ull << 63);      // absolute already (marked; unmarked below)
-                        push_midscan(jtail, t, q3);
-                        NraJointCombineTask ct{};
-                        ct.read = r; ct.n1 = gr.n1; ct.n2 = gr.n2; ct.out = (int32_t)first[r];
-                        ct.fb = (int32_t)fb_total; ct.ra = ra_off[(size_t)r]; ct.fs = fs_total; ct.rs = rs_off[(size_t)r];
-                        ct.rs_first = gr.k2lo - kr.k2lo; ct.rs_stride = grid->step2; ct.rs_plane = 64 * bk.R;
-                        jcomb.push_back(ct);
-                        fs_total += (uint64_t)gr.n1 * q3; fb_total += gr.n1;
-                        // algorithmic cells (closed form, as below)
-                        {
-                            const int64_t n1 = gr.n1, n2 = gr.n2;
-                            const int64_t sum_k1 = n1 * gr.k1lo + (int64_t)grid->step1 * n1 * (n1 - 1) / 2;
-                            const int64_t sum_k2 = n2 * gr.k2lo + (int64_t)grid->step2 * n2 * (n2 - 1) / 2;
-                            alg_cells += (int64_t)reads[r].qlen * (n1 * n2 * ((int64_t)d.l1 + d.l2 + d.l3) + d.m1 * sum_k1 * n2 + d.m2 * sum_k2 * n1);
-                        }
-                        continue;
-                    }
-                } else {
-                    ks.assign(cell_k1 + first[r], cell_k1 + first[r] + cnt[r]);
-                    if (!std::is_sorted(ks.begin(), ks.end())) std::sort(ks.begin(), ks.end());
-                    ks.erase(std::unique(ks.begin(), ks.end()), ks.end());
-                }
-                if (used > 0 && used + slot * ks.size() > state_cap) {      // close the group (never with kept states: budgeted above)
-                    g.n_pre = (int)(jpre.size() - g.pre_off); g.n_tail = (int)(jtail.size() - g.tail_off);
-                    b->jgroups.push_back(g);
-                    g.pre_off = jpre.size(); g.tail_off = jtail.size();
-                    used = 0;
-                }
-                NraJointTask tp{}; tp.read = r; tp.k1_off = (int32_t)k1list.size(); tp.nk1 = (int32_t)ks.size();
-                tp.state = used; tp.k2step = 1;
-                if (b->jpack_l) { tp.resume = 1; tp.pstate = pair.state; tp.phalf = pair.read_b == r ? 1 : 0; }
-                jpre.push_back(tp);
-                bk.cells_sweep += (int64_t)64 * bk.R * (d.l1 + d.m1 * ks.back() - 1 - (b->jpack_l ? colsL : 0));
-                if (b->joint_v2) {
-                    // one MID sweep per k1 (the last prefix column + mid; leaves its column state and B(k1)), and the
-                    // read's combine task: n1 x n2 cells from the column states on either side of the junction
-                    const GridRow& gr = grid->rows[(size_t)r];
-                    const uint64_t q3 = (uint64_t)3 * (uint64_t)reads[r].qlen;
-                    if (b->joint_chain) {
-                        // the MID part of all the read's k1 in one wave, column by column (k_joint_midscan)
-                        NraJointTask t{}; t.read = r; t.k1_off = tp.k1_off; t.nk1 = tp.nk1;
-                        t.k1 = gr.k1lo; t.k2step = grid->step1;          // slot i of `state` holds k1lo + i * step1
-                        t.out = (int32_t)fb_total; t.state = used; t.pstate = fs_total;
-                        push_midscan(jtail, t, q3);
-                        bk.cells_sweep += (int64_t)64 * bk.R * gr.n1 * (1 + d.l2);
-                        bk.cells_sweep += (int64_t)64 * bk.R * (1 + std::min(63, std::max(reads[r].qlen - 1, 0) / bk.R));   // the prefix sweep's own drain
-                    } else
-                    for (int32_t i = 0; i < gr.n1; ++i) {
-                        NraJointTask t{}; t.read = r; t.k1 = ks[(size_t)i]; t.k2step = 1;
-                        t.out = (int32_t)(fb_total + i);
-                        t.state = used + slot * (uint64_t)i;
-                        t.pstate = fs_total + (uint64_t)i * q3;
-                        jtail.push_back(t);
-                        bk.cells_sweep += joint_cells(bk.R, 1 + d.l2, reads[r].qlen);
-                    }
-                    NraJointCombineTask ct{};
-                    ct.read = r; ct.n1 = gr.n1; ct.n2 = gr.n2; ct.out = (int32_t)first[r];
-                    ct.fb = (int32_t)fb_total; ct.ra = ra_off[(size_t)r]; ct.fs = fs_total; ct.rs = rs_off[(size_t)r];
-                    ct.rs_first = 0; ct.rs_stride = 1; ct.rs_plane = 64 * bk.R;
-                    jcomb.push_back(ct);
-                    fs_total += (uint64_t)gr.n1 * q3; fb_total += gr.n1;
-                } else if (grid) {
-                    // one tail sweep per k1: the read's k2 values are one arithmetic progression
-                    const GridRow& gr = grid->rows[(size_t)r];
-                    for (int32_t i = 0; i < gr.n1; ++i) {
-                        NraJointTask t{}; t.read = r; t.k1 = ks[(size_t)i]; t.k2lo = gr.k2lo; t.k2step = grid->step2; t.n2 = gr.n2;
-                        t.out = (int32_t)(first[r] + (uint32_t)i * (uint32_t)gr.n2);
-                        t.state = used + slot * (uint64_t)i;
-                        jtail.push_back(t);
-                        bk.cells_sweep += joint_cells(bk.R, 1 + d.l2 + d.m2 * (t.k2lo + t.k2step * (t.n2 - 1)), reads[r].qlen);
-                    }
-                } else
-                for (uint32_t c = first[r]; c < first[r] + cnt[r];) {
-                    NraJointTask t{}; t.read = r; t.k1 = cell_k1[c]; t.k2lo = cell_k2[c]; t.k2step = 1; t.n2 = 1;
-                    t.out = (int32_t)c;
-                    uint32_t e = c + 1;
-                    if (e < first[r] + cnt[r] && cell_k1[e] == t.k1 && cell_k2[e] > t.k2lo) {
-                        t.k2step = cell_k2[e] - t.k2lo;
-                        while (e < first[r] + cnt[r] && cell_k1[e] == t.k1 &&
-                               cell_k2[e] == t.k2lo + t.k2step * (int32_t)(e - c)) ++e;
-                    }
-                    t.n2 = (int32_t)(e - c);
-                    t.state = used + slot * (uint64_t)(std::lower_bound(ks.begin(), ks.end(), t.k1) - ks.begin());
-                    jtail.push_back(t);
-                    bk.cells_sweep += joint_cells(bk.R, 1 + d.l2 + d.m2 * (t.k2lo + t.k2step * (t.n2 - 1)), reads[r].qlen);
-                    c = e;
-                }
-                k1list.insert(k1list.end(), ks.begin(), ks.end());
-                used += slot * ks.size();
-                state_max = std::max(state_max, used);
-            }
-            // algorithmic cells: the rectangle of every (read, cell) alignment
-            if (grid && !per_cell) {
-                // a product grid: the sum of the template lengths in closed form
-                const GridRow& gr = grid->rows[(size_t)r];
-                const int64_t n1 = gr.n1, n2 = gr.n2;
-                const int64_t sum_k1 = n1 * gr.k1lo + (int64_t)grid->step1 * n1 * (n1 - 1) / 2;
-                const int64_t sum_k2 = n2 * gr.k2lo + (int64_t)grid->step2 * n2 * (n2 - 1) / 2;
-                alg_cells += (int64_t)reads[r].qlen * (n1 * n2 * ((int64_t)d.l1 + d.l2 + d.l3) + d.m1 * sum_k1 * n2 + d.m2 * sum_k2 * n1);
-            } else {
-                int64_t tl_sum = 0;
-                for (uint32_t i = 0; i < cnt[r]; ++i) {
-                    const int32_t k1 = k1_of(r, i), k2 = k2_of(r, i);
-                    const int tl = d.l1 + d.m1 * k1 + d.l2 + d.m2 * k2 + d.l3;
-                    tl_sum += tl;
-                    if (per_cell) {
-                        queue_tasks.push_back(NraTask{r, k1, k2, (int32_t)(first[r] + i)});
-                        bk.cells_queue += sweep_cells(bk.R, tl);
-                    }
-                }
-                alg_cells += (int64_t)reads[r].qlen * tl_sum;
-            }
-        }
-        if (!per_cell) {
-            g.n_pre = (int)(jpre.size() - g.pre_off); g.n_tail = (int)(jtail.size() - g.tail_off);
-            if (g.n_pre > 0 || g.n_tail > 0) b->jgroups.push_back(g);
-            for (size_t i = bucket_pre0; i < jpre.size(); ++i) {
-                jpre[i].state += state_base;
-                if (keep == 1) b->keep_state_off[(size_t)jpre[i].read] = jpre[i].state;
-            }
-            for (size_t i = bucket_tail0; i < jtail.size(); ++i) {
-                if (jtail[i].state >> 63) jtail[i].state &= ~(1ull << 63);      // a kept state: absolute
-                else jtail[i].state += state_base;
-            }
-            state_base += state_max;
-        }
-        bk.n_queue = (int)(queue_tasks.size() - bk.queue_off);
-        bk.queue_cap = (size_t)bk.n_queue;
-        bk.n_comb = (int)(jcomb.size() - bk.comb_off);
-        queue_count.push_back(bk.n_queue);
-    }
+    plan_2d_cells(b->host_reads, b->r2, cl, b->n_q2bit_words, had_warm ? b->warm_cells : 0, b->carried, plan);
+    b->buckets = std::move(plan.buckets);
+    b->jgroups = std::move(plan.jgroups);
 
     clk.mark("2D cells: prefix and tail sweeps built");
-    HIP_TRY(b->queue_tasks.upload(queue_tasks));
-    HIP_TRY(b->queue_count.upload(queue_count));
+    HIP_TRY(b->queue_tasks.upload(plan.queue_tasks));
+    HIP_TRY(b->queue_count.upload(plan.queue_count));
     if (!b->brute) {
-        HIP_TRY(b->jpre_tasks.upload(jpre));
-        HIP_TRY(b->jtail_tasks.upload(jtail));
-        HIP_TRY(b->jk1list.upload(k1list));
+        HIP_TRY(b->jpre_tasks.upload(plan.jpre));
+        HIP_TRY(b->jtail_tasks.upload(plan.jtail));
+        HIP_TRY(b->jk1list.upload(plan.k1list));
         if (keep != 2) {
             ArenaScope kept(keep == 1 ? &b->keep_arena : &b->cell_arena);
-            if (keep == 1) b->keep_arena.expect((size_t)state_base * 4 + (1u << 20));
-            HIP_TRY(b->jstate.alloc((size_t)state_base));
+            if (keep == 1) b->keep_arena.expect((size_t)plan.state_base * 4 + (1u << 20));
+            HIP_TRY(b->jstate.alloc((size_t)plan.state_base));
         }
         if (b->joint_v2) {
-            HIP_TRY(b->jfs.alloc((size_t)fs_total));
-            HIP_TRY(b->jfb.alloc((size_t)fb_total));
-            HIP_TRY(b->jcomb_tasks.upload(jcomb));
+            HIP_TRY(b->jfs.alloc((size_t)plan.fs_total));
+            HIP_TRY(b->jfb.alloc((size_t)plan.fb_total));
+            HIP_TRY(b->jcomb_tasks.upload(plan.jcomb));
         }
     }
-    b->cur_rows.clear();
-    if (grid) { b->cur_rows.assign(grid->rows, grid->rows + n_reads); b->cur_step1 = grid->step1; b->cur_step2 = grid->step2; }
+    b->carried.set_current(grid, n_reads);
     b->grid_step1 = b->grid_step2 = 0;
     if (grid) {                                        // the selector computes k1 / k2 of a cell from the read's row
         std::vector<GridRow> rows(grid->rows, grid->rows + n_reads);
@@ -2340,8 +1757,8 @@ int set_cells_common(nra_batch* b, const int8_t* read_strand, int64_t n_cells, c
         std::vector<int32_t> v(cell_k1, cell_k1 + n_cells); HIP_TRY(b->cell_k1.upload(v));
         std::vector<int32_t> w(cell_k2, cell_k2 + n_cells); HIP_TRY(b->cell_k2.upload(w));
     }
-    HIP_TRY(b->cell_first.upload(first));
-    HIP_TRY(b->cell_cnt.upload(cnt));
+    HIP_TRY(b->cell_first.upload(plan.first));
+    HIP_TRY(b->cell_cnt.upload(plan.cnt));
     HIP_TRY(b->cand_score.alloc((size_t)n_cells));     // cell_score
     HIP_TRY(b->cand_tstart.alloc((size_t)n_cells));    // cell_wscore
     clk.mark("2D cells: device buffers, H2D");
@@ -2350,17 +1767,11 @@ int set_cells_common(nra_batch* b, const int8_t* read_strand, int64_t n_cells, c
         if (rc1) return rc1;
     }
 
-    b->stats.n_alignments = n_cells;
-    b->stats.algorithmic_cells = alg_cells;
-    int64_t ex = 0;
-    for (const Bucket& bk : b->buckets) ex += bk.cells_pair + bk.cells_queue + bk.cells_sweep;
-    if (had_warm) ex += b->warm_cells;
-    b->stats.executed_cells = ex;
-    b->stats.algorithmic_bytes = (int64_t)b->n_q2bit_words * 4 + (int64_t)pool.size() + n_cells * 8 + (int64_t)n_reads * 25;
-    int64_t packed_ints = 0;
-    for (const Bucket& bk : b->buckets) packed_ints += (int64_t)(bk.n_jlpk + bk.n_jrpk) * NRA_JOINT_NPSTATE(bk.R) * 64;
-    b->stats.intermediate_bytes = b->brute ? 0 : 2 * ((int64_t)state_base * 4 + packed_ints * 4 +
-                                                      (b->joint_v2 ? (int64_t)(rs_total + fs_total) * 4 : (int64_t)b->n_q2bit_words * 16 * 3 * 4));
+    b->stats.n_alignments = plan.stats.n_alignments;
+    b->stats.algorithmic_cells = plan.stats.algorithmic_cells;
+    b->stats.executed_cells = plan.stats.executed_cells;
+    b->stats.algorithmic_bytes = plan.stats.algorithmic_bytes;
+    b->stats.intermediate_bytes = plan.stats.intermediate_bytes;
     b->have_cells = true;
     return NRA_OK;
 }
@@ -2373,10 +1784,7 @@ extern "C" {
 int nra_batch2d_invalidate(nra_batch_t* b)
 {
     if (!b || b->kind != 2) return fail(NRA_E_ARG, "not a 2D batch");
-    std::fill(b->rev_strand.begin(), b->rev_strand.end(), (int8_t)0);
-    std::fill(b->lst_strand.begin(), b->lst_strand.end(), (int8_t)0);
-    std::fill(b->rpk_strand.begin(), b->rpk_strand.end(), (int8_t)0);
-    b->keep_valid = false;
+    b->carried.invalidate();
     return NRA_OK;
 }
 
@@ -2390,8 +1798,8 @@ int nra_batch2d_sweep_flanks(nra_batch_t* b, const int8_t* read_strand)
     if (!b || b->kind != 2) return fail(NRA_E_ARG, "not a 2D batch");
     const int32_t n_reads = b->n_reads;
     if (n_reads > 0 && !read_strand) return fail(NRA_E_ARG, "NULL strand array");
-    const int32_t left_len = (int32_t)b->jr_left.size(), right_len = (int32_t)b->jr_right.size();
-    if ((b->flags & NRA_F_BRUTE_FORCE) != 0 || left_len < 1 || right_len < 2 || (!b->jpack_l && !b->jpack_r) || n_reads == 0)
+    const int32_t left_len = (int32_t)b->jr.left.size(), right_len = (int32_t)b->jr.right.size();
+    if (!sweeps_flanks_ahead(b->r2, b->flags, left_len, right_len, n_reads))
         return NRA_OK;                                         // nothing this batch sweeps ahead of time
     HIP_TRY(hipSetDevice(b->device));
     if (b->ran) HIP_TRY(hipStreamSynchronize(b->stream));      // an earlier list's kernels read the flank states
@@ -2408,39 +1816,12 @@ int nra_batch2d_sweep_flanks(nra_batch_t* b, const int8_t* read_strand)
     // the reads as the kernels orient them (what k_pick_strand leaves in the cell list's own copy)
     std::vector<NraDevRead> reads(b->host_reads.begin(), b->host_reads.begin() + n_reads);
     for (int32_t r = 0; r < n_reads; ++r) reads[(size_t)r].rc = read_strand[r] < 0 ? 1 : 0;
-    // per rows-per-lane bucket (pairs are listed bucket by bucket): the pairs whose reads all come with a strand and
-    // whose state is not valid for it
-    struct Part { int R; size_t off, n_l, n_r; };
-    std::vector<Part> parts;
-    std::vector<NraJointPairTask> mt;              // L- and R-side tasks of a pair next to each other; L marked in bit 63 of `state`
-    std::vector<std::pair<int32_t, int8_t>> l_done, r_done;
-    for (size_t i = 0; i < b->jpairs.size();) {
-        const int bi = b->jbucket[(size_t)b->jpairs[i].read_a];
-        Part part{kRList[bi], mt.size(), 0, 0};
-        for (; i < b->jpairs.size() && b->jbucket[(size_t)b->jpairs[i].read_a] == bi; ++i) {
-            const NraJointPairTask& pair = b->jpairs[i];
-            bool all = true, stale_l = false, stale_r = false;
-            for (int32_t q : {pair.read_a, pair.read_b}) {
-                if (q < 0) continue;
-                if (read_strand[q] == 0) all = false;
-                if (b->lst_strand[(size_t)q] != read_strand[q]) stale_l = true;
-                if (b->rpk_strand[(size_t)q] != read_strand[q]) stale_r = true;
-            }
-            if (!all) continue;
-            for (int32_t q : {pair.read_a, pair.read_b}) {
-                if (q < 0) continue;
-                if (b->jpack_l && stale_l) l_done.push_back({q, read_strand[q]});
-                if (b->jpack_r && stale_r) r_done.push_back({q, read_strand[q]});
-            }
-            if (b->jpack_l && stale_l) { NraJointPairTask t = pair; t.state |= 1ull << 63; mt.push_back(t); part.n_l++; }
-            if (b->jpack_r && stale_r) { mt.push_back(pair); part.n_r++; }
-        }
-        if (part.n_l || part.n_r) parts.push_back(part);
-    }
+    FlankPlan fp;
+    plan_2d_flanks(b->r2, b->carried, read_strand, left_len, right_len, fp);
+    const std::vector<FlankPart>& parts = fp.parts;
     if (parts.empty()) return NRA_OK;
-    std::reverse(parts.begin(), parts.end());                  // the longest reads first, like the cell lists' buckets
     HIP_TRY(copy_h2d(b->warm_reads.p, reads.data(), reads.size() * sizeof(NraDevRead)));
-    HIP_TRY(copy_h2d(b->warm_tasks.p, mt.data(), mt.size() * sizeof(NraJointPairTask)));
+    HIP_TRY(copy_h2d(b->warm_tasks.p, fp.tasks.data(), fp.tasks.size() * sizeof(NraJointPairTask)));
     const size_t np = parts.size();
     while (b->bstreams.size() < 2 * np) { hipStream_t q; HIP_TRY(g_handles.stream(b->device, &q)); b->bstreams.push_back(q); }
     while (b->warm_ev.size() < 2 * np) { hipEvent_t e; HIP_TRY(g_handles.event(b->device, false, &e)); b->warm_ev.push_back(e); }
@@ -2451,10 +1832,8 @@ int nra_batch2d_sweep_flanks(nra_batch_t* b, const int8_t* read_strand)
     HIP_TRY(hipEventRecord(b->fork2_ev, st));
     int ev = 2;
     b->n_score_ev = 0; b->n_ext_ev = 0;
-    const int colsL = NRA_JOINT_PACKED_COLS(left_len), colsR = NRA_JOINT_PACKED_COLS(right_len);
-    int64_t cells = 0;
     for (size_t i = 0; i < np; ++i) {
-        const Part& pt = parts[i];
+        const FlankPart& pt = parts[i];
         hipStream_t qa = b->bstreams[2 * i], qb = b->bstreams[2 * i + 1];
         HIP_TRY(hipStreamWaitEvent(qa, b->fork2_ev, 0));
         HIP_TRY(hipStreamWaitEvent(qb, b->fork2_ev, 0));
@@ -2466,17 +1845,15 @@ int nra_batch2d_sweep_flanks(nra_batch_t* b, const int8_t* read_strand)
                                          b->warm_region.p, b->warm_pool.p, b->q2bit.p, b->qnmask.p, b->sp, -1, b->jrstate.p, b->jlstate.p));
         HIP_TRY(hipEventRecord(b->ev[ev++], qa));
         b->n_score_ev++;
-        cells += (int64_t)pt.n_l * 2 * 64 * pt.R * colsL + (int64_t)pt.n_r * 2 * 64 * pt.R * colsR;
         HIP_TRY(hipEventRecord(b->warm_ev[2 * i], qa));
         HIP_TRY(hipEventRecord(b->warm_ev[2 * i + 1], qa));
     }
     b->warm_R.clear();
-    for (const Part& pt : parts) b->warm_R.push_back(pt.R);
+    for (const FlankPart& pt : parts) b->warm_R.push_back(pt.R);
     b->ev_next = ev;
     b->warm_pending = true;
-    b->warm_cells = cells;
-    for (const auto& pr2 : l_done) b->lst_strand[(size_t)pr2.first] = pr2.second;
-    for (const auto& pr2 : r_done) b->rpk_strand[(size_t)pr2.first] = pr2.second;
+    b->warm_cells = fp.cells;
+    commit_2d_flanks(b->carried, fp);
     return NRA_OK;
 }
 
@@ -2692,13 +2069,7 @@ int run_2d(nra_batch* b)
     }
     // the reverse sweeps enqueued above stay valid for later cell lists of this batch (given strands only:
     // a probed strand is not known on the host)
-    for (const auto& pr2 : b->rev_pending) b->rev_strand[(size_t)pr2.first] = pr2.second;
-    b->rev_pending.clear();
-    for (const auto& pr2 : b->lst_pending) b->lst_strand[(size_t)pr2.first] = pr2.second;
-    b->lst_pending.clear();
-    for (const auto& pr2 : b->rpk_pending) b->rpk_strand[(size_t)pr2.first] = pr2.second;
-    b->rpk_pending.clear();
-    if (b->keep_pending) { b->keep_valid = true; b->keep_pending = false; }      // ... and so do the column states
+    commit_2d(b->carried, b->pending);
     HIP_TRY(hipEventRecord(b->phase_ev[1], st));
     LAUNCH_TRY(nra_launch_select_2d(st, b->n_reads, b->cell_first.p, b->cell_cnt.p, b->cell_k1.p, b->cell_k2.p,
                                     b->grid_step1 > 0 ? b->grid_rows.p : nullptr, b->grid_step1, b->grid_step2,
@@ -2737,94 +2108,40 @@ int nra_batch2d_refine(nra_batch_t* b, int32_t buf1, int32_t buf2, const double*
     if (buf1 <= 0 || buf2 <= 0 || buf1 > 4096 || buf2 > 4096) return fail(NRA_E_ARG, "bad refinement buffers");
     const int32_t n_reads = b->n_reads;
     if (n_reads > 0 && (!lo1 || !hi1 || !lo2 || !hi2)) return fail(NRA_E_ARG, "NULL bound array");
-    if (!b->ran || b->accounted || b->refined || !b->joint_v2 || !b->joint_chain || b->joint_keep == 0 || !b->keep_valid ||
-        b->brute || !b->all_strands_given || b->keep_rows.size() != (size_t)n_reads)
-        return fail(NRA_E_STATE, "no refinement: it follows nra_batch_run of a routed grid (nra_batch2d_set_grid, every strand "
-                                 "given) whose column states are kept, before anything waits for that run");
-    for (const Bucket& bk : b->buckets)
-        if (bk.chain) return fail(NRA_E_STATE, "no refinement: reads beyond one register block are scored cell by cell");
-    // Every count a read's refinement can ask for -- within buf of a size between its first and last grid value, inside
-    // [lo, hi) -- has to be among the counts column states were kept at.  True by construction behind the grid that kept
-    // them when buf = its steps and [lo, hi) = its bounds; not necessarily behind a grid that itself ran from states an
-    // EARLIER grid kept, or with other buffers / bounds: then the caller takes the two-call path.
-    if (b->cur_rows.size() != (size_t)n_reads) return fail(NRA_E_STATE, "no refinement: the current cell list is not a routed grid");
-    for (int32_t r = 0; r < n_reads; ++r) {
-        const NraGridRow& g = b->cur_rows[(size_t)r];
-        const NraGridRow& k = b->keep_rows[(size_t)r];
-        if (g.n1 <= 0 || g.n2 <= 0 || k.n1 <= 0 || k.n2 <= 0) continue;
-        auto fits = [](int32_t first, int32_t n, int32_t step, int32_t buf, double lo, double hi, int32_t klo, int32_t kn) {
-            if (!(lo < hi)) return true;
-            const int64_t last = (int64_t)first + (int64_t)(n - 1) * step;
-            const double cl = std::ceil(lo), ch = std::ceil(hi);
-            const int64_t need_lo = std::max<int64_t>({cl < 0 ? 0 : (cl > 1e9 ? (int64_t)1e9 : (int64_t)cl), (int64_t)first - buf, 0});
-            const int64_t need_hi = std::min<int64_t>(ch > 1e9 ? (int64_t)1e9 : (int64_t)ch - 1, last + buf - 1);
-            return need_hi < need_lo || (need_lo >= klo && need_hi <= (int64_t)klo + kn - 1);
-        };
-        if (!fits(g.k1lo, g.n1, b->cur_step1, buf1, lo1[r], hi1[r], k.k1lo, k.n1) ||
-            !fits(g.k2lo, g.n2, b->cur_step2, buf2, lo2[r], hi2[r], k.k2lo, k.n2))
-            return fail(NRA_E_STATE, "no refinement: a read's refinement could ask for repeat counts no column state was kept at");
+    {
+        const Forms2D forms{b->joint_keep, b->brute, b->joint_v2, b->joint_chain, b->all_strands_given};
+        const int rc = check_2d_refine(b->ran && !b->accounted && !b->refined, forms, b->carried, b->buckets, n_reads, buf1, buf2,
+                                       lo1, hi1, lo2, hi2);
+        if (rc) return rc;
     }
     HIP_TRY(hipSetDevice(b->device));
     ArenaScope arena_scope(&b->cell_arena);
     const int cap1 = 2 * buf1, cap2 = 2 * buf2;
     const int64_t cap = (int64_t)cap1 * cap2;
-    if (cap * n_reads > 0x7ff00000ll) return fail(NRA_E_RANGE, "too many cells");
+    if (!cells_2d_countable(cap * n_reads)) return fail(NRA_E_RANGE, "too many cells");
     const size_t nb = b->buckets.size();
-    const int kChunk = 3;                       // k1 values per MID-scan task (push_midscan)
-
-    // static tasks: what a read's refinement needs whatever its round-2 size turns out to be
-    std::vector<std::vector<NraJointTask>> mid(nb);
-    std::vector<std::vector<NraJointCombineTask>> comb(nb);
-    std::vector<int> bucket_of_R((size_t)NRA_MAX_R + 1, -1);
-    for (size_t i = 0; i < nb; ++i) bucket_of_R[(size_t)b->buckets[i].R] = (int)i;
-    std::vector<uint32_t> first((size_t)n_reads);
-    std::vector<int32_t> rowspad((size_t)n_reads, 0);
-    uint64_t fs_total = 0; int64_t fb_total = 0;
-    for (int32_t r = 0; r < n_reads; ++r) {
-        first[(size_t)r] = (uint32_t)((int64_t)r * cap);
-        const NraGridRow& k = b->keep_rows[(size_t)r];
-        if (k.n1 <= 0 || k.n2 <= 0 || b->host_reads[(size_t)r].qlen <= 0 || b->chained_reads[(size_t)r]) continue;
-        const int R = kRList[b->jbucket[(size_t)r]];
-        const int bi = bucket_of_R[(size_t)R];
-        if (bi < 0) return fail(NRA_E_STATE, "no refinement: a read's bucket did not run");
-        rowspad[(size_t)r] = 64 * R;
-        const uint64_t q3 = (uint64_t)3 * (uint64_t)b->host_reads[(size_t)r].qlen;
-        for (int c = 0; c < cap1; c += kChunk) {
-            NraJointTask t{}; t.read = r; t.k1_off = c; t.nk1 = std::min(kChunk, cap1 - c);
-            t.k1 = k.k1lo; t.k2step = 1; t.state = b->keep_state_off[(size_t)r];
-            t.pstate = fs_total + (uint64_t)c * q3; t.out = (int32_t)(fb_total + c);
-            mid[(size_t)bi].push_back(t);
-        }
-        NraJointCombineTask ct{};
-        ct.read = r; ct.out = (int32_t)first[(size_t)r]; ct.fb = (int32_t)fb_total; ct.ra = b->keep_ra_off[(size_t)r];
-        ct.fs = fs_total; ct.rs = b->keep_rs_off[(size_t)r]; ct.rs_first = k.k2lo; ct.rs_stride = 1; ct.rs_plane = 64 * R;
-        comb[(size_t)bi].push_back(ct);
-        fs_total += (uint64_t)cap1 * q3; fb_total += cap1;
-    }
-    std::vector<NraJointTask> mid_all; std::vector<NraJointCombineTask> comb_all;
-    std::vector<size_t> mid_off(nb), comb_off(nb);
-    for (size_t i = 0; i < nb; ++i) {
-        mid_off[i] = mid_all.size(); comb_off[i] = comb_all.size();
-        mid_all.insert(mid_all.end(), mid[i].begin(), mid[i].end());
-        comb_all.insert(comb_all.end(), comb[i].begin(), comb[i].end());
+    RefinePlan rp;
+    {
+        const int rc = plan_2d_refine(b->host_reads, b->r2, b->carried, b->buckets, buf1, buf2, rp);
+        if (rc) return rc;
     }
     std::vector<double> bounds((size_t)4 * (size_t)std::max(n_reads, 1), 0.0);
     for (int32_t r = 0; r < n_reads; ++r) {
         bounds[(size_t)r] = lo1[r]; bounds[(size_t)n_reads + r] = hi1[r];
         bounds[(size_t)2 * n_reads + r] = lo2[r]; bounds[(size_t)3 * n_reads + r] = hi2[r];
     }
-    b->cell_arena.expect((size_t)fs_total * 4 + (size_t)cap * n_reads * 8 + (size_t)n_reads * 128 + (4u << 20));
+    b->cell_arena.expect(refine_arena_bytes(rp.fs_total, cap, n_reads));
     HIP_TRY(b->rf_bounds.upload(bounds));
-    HIP_TRY(b->rf_keep.upload(b->keep_rows));
-    HIP_TRY(b->rf_first.upload(first));
-    HIP_TRY(b->rf_rowspad.upload(rowspad));
-    HIP_TRY(b->rf_mid_tasks.upload(mid_all));
-    HIP_TRY(b->rf_comb_tasks.upload(comb_all));
+    HIP_TRY(b->rf_keep.upload(b->carried.keep_rows));
+    HIP_TRY(b->rf_first.upload(rp.first));
+    HIP_TRY(b->rf_rowspad.upload(rp.rowspad));
+    HIP_TRY(b->rf_mid_tasks.upload(rp.mid));
+    HIP_TRY(b->rf_comb_tasks.upload(rp.comb));
     HIP_TRY(b->rf_rows.alloc((size_t)std::max(n_reads, 1)));
     HIP_TRY(b->rf_cnt.alloc((size_t)std::max(n_reads, 1)));
     HIP_TRY(b->rf_words.alloc(4));
-    HIP_TRY(b->rf_fs.alloc((size_t)fs_total));
-    HIP_TRY(b->rf_fb.alloc((size_t)fb_total));
+    HIP_TRY(b->rf_fs.alloc((size_t)rp.fs_total));
+    HIP_TRY(b->rf_fb.alloc((size_t)rp.fb_total));
     // the refinement's cells: read-major, `cap` entries a read (its n1 x n2 cells first, k1-major)
     HIP_TRY(b->rf_cell_score.alloc((size_t)(cap * n_reads)));
     HIP_TRY(b->rf_cell_wscore.alloc((size_t)(cap * n_reads)));
@@ -2848,18 +2165,18 @@ int nra_batch2d_refine(nra_batch_t* b, int32_t buf1, int32_t buf2, const double*
     HIP_TRY(hipEventRecord(b->fork2_ev, st));
     for (size_t i = 0; i < nb; ++i) {
         const Bucket& bk = b->buckets[i];
-        const int n_mid = (int)mid[i].size(), n_comb = (int)comb[i].size();
+        const int n_mid = (int)(rp.mid_off[i + 1] - rp.mid_off[i]), n_comb = (int)(rp.comb_off[i + 1] - rp.comb_off[i]);
         if (n_mid == 0) continue;
         hipStream_t qb = b->bstreams[2 * i + 1];
         HIP_TRY(hipStreamWaitEvent(qb, b->fork2_ev, 0));
         HIP_TRY(hipEventRecord(b->ev[ev++], qb));
-        LAUNCH_TRY(nra_launch_joint_midscan(bk.R, b->has_n, qb, n_mid, b->rf_mid_tasks.p + mid_off[i], b->reads.p, b->regions.p,
+        LAUNCH_TRY(nra_launch_joint_midscan(bk.R, b->has_n, qb, n_mid, b->rf_mid_tasks.p + rp.mid_off[i], b->reads.p, b->regions.p,
                                             b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, nullptr, b->jstate.p, b->rf_fs.p,
                                             b->rf_fb.p, b->rf_rows.p));
         HIP_TRY(hipEventRecord(b->ev[ev++], qb));
         b->n_score_ev++;
         HIP_TRY(hipEventRecord(b->ev[ev++], qb));
-        LAUNCH_TRY(nra_launch_joint_combine(qb, n_comb, b->rf_comb_tasks.p + comb_off[i], b->reads.p, b->sp, b->rf_fs.p, b->jrs.p,
+        LAUNCH_TRY(nra_launch_joint_combine(qb, n_comb, b->rf_comb_tasks.p + rp.comb_off[i], b->reads.p, b->sp, b->rf_fs.p, b->jrs.p,
                                             b->rf_fb.p, b->jra.p, b->rf_cell_score.p, b->rf_cell_wscore.p, b->rf_rows.p));
         HIP_TRY(hipEventRecord(b->ev[ev++], qb));
         b->n_score_ev++;
@@ -2874,6 +2191,28 @@ int nra_batch2d_refine(nra_batch_t* b, int32_t buf1, int32_t buf2, const double*
     b->ev_next = ev;
     b->refined = true; b->refine_read = false;
     return NRA_OK;
+}
+int64_t nra_plan2d_digest(const nra_joint_region_t* reg, int32_t n_reads, const char* seqs, const int64_t* seq_off,
+                          const nra_scoring_t* sc, int32_t flags, const nra_plan2d_step_t* steps, int32_t n_steps,
+                          char* buf, int64_t cap)
+{
+    if (!reg || n_reads < 0 || n_steps < 0 || (n_steps > 0 && !steps)) return fail(NRA_E_ARG, "bad region / counts");
+    if (n_reads > 0 && (!seqs || !seq_off)) return fail(NRA_E_ARG, "NULL input array");
+    if (!scoring_ok(sc)) return fail(NRA_E_ARG, "scoring parameters out of range");
+    if (reg->left_len < 0 || reg->right_len < 0 || reg->mid_len < 0 || reg->unit1_len <= 0 ||
+        reg->unit2_len <= 0 || !reg->unit1 || !reg->unit2)
+        return fail(NRA_E_ARG, "bad joint region");
+    if (cap < 0 || (cap > 0 && !buf)) return fail(NRA_E_ARG, "bad buffer");
+    PackedReads pr;
+    const int rc = pack_reads(n_reads, seqs, seq_off, nullptr, 1, pr, NRA_MAX_QLEN);
+    if (rc) return rc;
+    const std::string text = plan_2d_digest(reg, pr.reads, pr.has_n, pr.q2bit.size(), sc, flags, steps, n_steps);
+    if (cap > 0) {
+        const size_t n = std::min(text.size(), (size_t)cap - 1);
+        memcpy(buf, text.data(), n);
+        buf[n] = 0;
+    }
+    return (int64_t)text.size() + 1;
 }
 
 int nra_batch2d_fetch(nra_batch_t* b, int8_t* read_strand, int32_t* cell_score, int32_t* cell_wscore,

@@ -632,39 +632,6 @@ int plan_1d(const nra_region_t* regions, int32_t n_regions, const std::vector<Nr
 }
 
 // ---- digest -------------------------------------------------------------------------------------
-namespace {
-
-// 64-bit FNV-1a over values fed field by field (struct padding never enters)
-struct Fnv {
-    uint64_t h = 1469598103934665603ull;
-    void bytes(const void* p, size_t n)
-    {
-        const unsigned char* s = static_cast<const unsigned char*>(p);
-        for (size_t i = 0; i < n; ++i) { h ^= s[i]; h *= 1099511628211ull; }
-    }
-    template <class T> void put(T v) { bytes(&v, sizeof v); }
-};
-
-struct Digest {
-    std::string s;
-    void line(const char* key, const std::string& value) { s += key; s += ' '; s += value; s += '\n'; }
-    void num(const char* key, int64_t v) { line(key, std::to_string(v)); }
-    template <class T, class F> void array(const char* key, const std::vector<T>& v, F feed)
-    {
-        Fnv f;
-        for (const T& x : v) feed(f, x);
-        char buf[64];
-        snprintf(buf, sizeof buf, "%zu %016llx", v.size(), (unsigned long long)f.h);
-        line(key, buf);
-    }
-    template <class T> void array(const char* key, const std::vector<T>& v)
-    {
-        array(key, v, [](Fnv& f, const T& x) { f.put(x); });
-    }
-};
-
-}  // namespace
-
 std::string plan_1d_digest(const Plan1D& p)
 {
     Digest d;
