@@ -5,6 +5,19 @@
 
 #define WAVE 64
 
+// The fields of a kernel's NraSeqArgs as locals, under the names the kernels read them by (k_score_pk16, k_trace_fill).
+#define NRA_SEQ_LOCALS(a)                                  \
+    const NraDevRead* __restrict__ reads = (a).reads;       \
+    const NraDevRegion* __restrict__ regions = (a).regions; \
+    const uint8_t* __restrict__ pool = (a).pool;            \
+    const uint32_t* __restrict__ q2bit = (a).q2bit;         \
+    const uint32_t* __restrict__ qnmask = (a).qnmask;       \
+    const NraScoreParams& sp = (a).sp;
+// ... and, in a launcher, as the arguments of a kernel that keeps parameters of its own, in the order all of them take
+// the six: with `const T* __restrict__` on its own parameters a kernel reads a task's read and region records with
+// scalar loads, which pointers that arrive inside a struct do not get (profiles/sweep_args_code_objects.txt)
+#define NRA_SEQ_FIELDS(a) (a).reads, (a).regions, (a).pool, (a).q2bit, (a).qnmask, (a).sp
+
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 

@@ -564,6 +564,17 @@ struct nra_batch {
     }
 };
 
+// The kernels' shared arguments from the batch's buffers as they are now.  Built at the top of a run function, never
+// kept: the 2D batch reallocates pool and regions with every cell list.
+static inline NraSeqArgs seq_args(const nra_batch* b)
+{
+    return NraSeqArgs{b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp};
+}
+static inline NraSweepArgs sweep_args(const nra_batch* b)
+{
+    return NraSweepArgs{seq_args(b), b->kmin.p, b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p, b->cand_score.p, b->cand_flag.p};
+}
+
 namespace {
 
 // ---- host worker threads --------------------------------------------------------------
@@ -1074,6 +1085,8 @@ static bool clears_extents_1d(const nra_batch* b) { return NRA_LEAN_CLEARS == 0 
 static int run_1d(nra_batch* b)
 {
     hipStream_t st = b->stream;
+    const NraSweepArgs sw = sweep_args(b);
+    const NraSeqArgs& seq = sw.seq;
     const size_t nb = b->buckets.size();
     const bool all_ext = (b->flags & NRA_F_ALL_EXTENTS) != 0;
     const size_t nc = (size_t)b->n_cands;
@@ -1123,13 +1136,9 @@ static int run_1d(nra_batch* b)
         // The exact re-sweep of a tainted bucket's flagged tasks: today's two launches, behind the tainted
         // sweeps on the bucket's stream; every other wave leaves at once.  It rewrites the tasks' R side, A and outputs.
         auto resweep = [&](const Bucket& bk, hipStream_t q, int32_t* redo) {
-            int rc2 = nra_launch_sweep_ring_bwd(bk.R, b->has_n, bk.half, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off, b->reads.p,
-                                                b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p, b->kmax.p,
-                                                b->coff.p, b->snap.p, b->read_a1d.p, 0, redo);
+            int rc2 = nra_launch_sweep_ring_bwd(bk.R, b->has_n, bk.half, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off, sw, 0, redo);
             if (rc2) return rc2;
-            return nra_launch_sweep_ring_fwd(bk.R, b->has_n, bk.half, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off, b->reads.p,
-                                             b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p, b->kmax.p,
-                                             b->coff.p, b->snap.p, b->read_a1d.p, b->cand_score.p, b->cand_flag.p, 0, redo);
+            return nra_launch_sweep_ring_fwd(bk.R, b->has_n, bk.half, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off, sw, 0, redo);
         };
         // (the order the buckets' chains are launched in makes no difference: 5.50 - 5.61 ms either way on config 2;
         // a bucket's tasks as 2 / 3 / 4 groups with chains of their own are slower: 5.65 -> 6.0 / 5.9 / 7.6 ms)
@@ -1160,9 +1169,7 @@ static int run_1d(nra_batch* b)
                 // second one is empty)
                 LAUNCH_TRY(nra_launch_sweep_ringq(bk.R, b->has_n, bk.half, q, bk.n_quanta, b->q_list.p + bk.q_off, bk.q_steps, bk.n_sweep,
                                                   b->q_words.p + 1 + i, b->q_words.p + b->q_arrivals_off + bk.q_task_off, b->q_words.p,
-                                                  b->q_state.p + bk.q_state_off, b->sweep_tasks.p + bk.sweep_off, b->reads.p,
-                                                  b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p, b->kmax.p,
-                                                  b->coff.p, b->snap.p, b->read_a1d.p, b->cand_score.p, b->cand_flag.p,
+                                                  b->q_state.p + bk.q_state_off, b->sweep_tasks.p + bk.sweep_off, sw,
                                                   bk.taint ? b->relax_c : 0, redo, b->sat_steps, b->sat_count.p + 4 * i));
                 if (bk.taint) LAUNCH_TRY(resweep(bk, q, redo));
                 HIP_TRY(hipEventRecord(b->ev[ev++], q));
@@ -1176,25 +1183,18 @@ static int run_1d(nra_batch* b)
             if (bk.mt) {
                 for (const auto& g : bk.mt_groups)
                     LAUNCH_TRY(nra_launch_sweep_ringmt_bwd(bk.R, b->has_n, bk.wide ? 1 : 0, q, g.second, b->chain_blocks.p + g.first,
-                                                           b->mt_words.p + 2 + i, b->sweep_tasks.p + bk.sweep_off, b->reads.p,
-                                                           b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p,
-                                                           b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p,
+                                                           b->mt_words.p + 2 + i, b->sweep_tasks.p + bk.sweep_off, sw,
                                                            b->mt_strips.p + bk.strip_off * 5 * (size_t)b->chain_cap, b->chain_cap,
                                                            next_epoch(), b->mt_giveup));
             } else if (bk.ring && bk.chain)
                 LAUNCH_TRY(nra_launch_sweep_ringchain_bwd(bk.R, b->has_n, bk.wide ? 1 : 0, q, bk.n_sweep,
-                                                          b->sweep_tasks.p + bk.sweep_off, b->reads.p, b->regions.p, b->pool.p,
-                                                          b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p, b->kmax.p, b->coff.p,
-                                                          b->snap.p, b->read_a1d.p, strips, b->chain_cap, bk.n_strips));
+                                                          b->sweep_tasks.p + bk.sweep_off, sw, strips, b->chain_cap, bk.n_strips));
             else if (bk.ring)
-                LAUNCH_TRY(nra_launch_sweep_ring_bwd(bk.R, b->has_n, bk.half, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off,
-                                                     b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp,
-                                                     b->kmin.p, b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p, relax_c, redo));
+                LAUNCH_TRY(nra_launch_sweep_ring_bwd(bk.R, b->has_n, bk.half, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off, sw,
+                                                     relax_c, redo));
             else
-                LAUNCH_TRY(nra_launch_sweep_bwd(bk.R, b->has_n, bk.chain ? 1 : 0, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off,
-                                                b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp,
-                                                b->kmin.p, b->kmax.p, b->coff.p, b->snap.p,
-                                                b->read_a1d.p, strips, b->chain_cap, bk.n_strips));
+                LAUNCH_TRY(nra_launch_sweep_bwd(bk.R, b->has_n, bk.chain ? 1 : 0, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off, sw,
+                                                strips, b->chain_cap, bk.n_strips));
             HIP_TRY(hipEventRecord(b->ev[ev++], q));
             HIP_TRY(hipEventRecord(b->ev[ev++], q));
             if (bk.mt && mt_first) {
@@ -1205,28 +1205,17 @@ static int run_1d(nra_batch* b)
             if (bk.mt) {
                 for (const auto& g : bk.mt_groups)
                     LAUNCH_TRY(nra_launch_sweep_ringmt_fwd(bk.R, b->has_n, bk.wide ? 1 : 0, q, g.second, b->chain_blocks.p + g.first,
-                                                           b->mt_words.p + 2 + i, b->sweep_tasks.p + bk.sweep_off, b->reads.p,
-                                                           b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p,
-                                                           b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p, b->cand_score.p,
-                                                           b->cand_flag.p,
+                                                           b->mt_words.p + 2 + i, b->sweep_tasks.p + bk.sweep_off, sw,
                                                            b->mt_strips.p + bk.strip_off * 5 * (size_t)b->chain_cap, b->chain_cap,
                                                            next_epoch(), b->mt_giveup));
             } else if (bk.ring && bk.chain)
                 LAUNCH_TRY(nra_launch_sweep_ringchain_fwd(bk.R, b->has_n, bk.wide ? 1 : 0, q, bk.n_sweep,
-                                                          b->sweep_tasks.p + bk.sweep_off, b->reads.p, b->regions.p, b->pool.p,
-                                                          b->q2bit.p, b->qnmask.p, b->sp, b->kmin.p, b->kmax.p, b->coff.p,
-                                                          b->snap.p, b->read_a1d.p, b->cand_score.p, b->cand_flag.p,
-                                                          strips, b->chain_cap, bk.n_strips));
+                                                          b->sweep_tasks.p + bk.sweep_off, sw, strips, b->chain_cap, bk.n_strips));
             else if (bk.ring)
-                LAUNCH_TRY(nra_launch_sweep_ring_fwd(bk.R, b->has_n, bk.half, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off,
-                                                     b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp,
-                                                     b->kmin.p, b->kmax.p, b->coff.p, b->snap.p, b->read_a1d.p,
-                                                     b->cand_score.p, b->cand_flag.p, relax_c, redo));
+                LAUNCH_TRY(nra_launch_sweep_ring_fwd(bk.R, b->has_n, bk.half, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off, sw,
+                                                     relax_c, redo));
             else
-                LAUNCH_TRY(nra_launch_sweep_fwd(bk.R, b->has_n, bk.chain ? 1 : 0, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off,
-                                                b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp,
-                                                b->kmin.p, b->kmax.p, b->coff.p, b->snap.p,
-                                                b->read_a1d.p, b->cand_score.p, b->cand_flag.p,
+                LAUNCH_TRY(nra_launch_sweep_fwd(bk.R, b->has_n, bk.chain ? 1 : 0, q, bk.n_sweep, b->sweep_tasks.p + bk.sweep_off, sw,
                                                 strips, b->chain_cap, bk.n_strips));
             if (bk.taint) LAUNCH_TRY(resweep(bk, q, redo));
             HIP_TRY(hipEventRecord(b->ev[ev++], q));
@@ -1239,14 +1228,10 @@ static int run_1d(nra_batch* b)
             const Bucket& bk = b->buckets[i];
             HIP_TRY(hipEventRecord(b->ev[ev++], st));
             if (!all_ext) {
-                LAUNCH_TRY(nra_launch_score_pk16(bk.R, b->has_n, st, bk.n_pair, b->pair_tasks.p + bk.pair_off,
-                                                 b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p,
-                                                 b->sp, b->cand_score.p));
+                LAUNCH_TRY(nra_launch_score_pk16(bk.R, b->has_n, st, bk.n_pair, b->pair_tasks.p + bk.pair_off, seq, b->cand_score.p));
             } else {
                 LAUNCH_TRY(nra_launch_payload_origin(bk.R, b->has_n, st, std::min(bk.n_queue, max_waves),
-                                                  b->queue_tasks.p + bk.queue_off, b->queue_count.p + i,
-                                                  b->reads.p, b->regions.p, b->pool.p,
-                                                  b->q2bit.p, b->qnmask.p, b->sp, b->cand_score.p,
+                                                  b->queue_tasks.p + bk.queue_off, b->queue_count.p + i, seq, b->cand_score.p,
                                                   b->cand_tstart.p, b->cand_tend.p, nullptr, 0, 0));
             }
             HIP_TRY(hipEventRecord(b->ev[ev++], st));
@@ -1268,9 +1253,7 @@ static int run_1d(nra_batch* b)
             // chained reads: int64 cells (scores and extents of any size)
             LAUNCH_TRY(nra_launch_payload_origin(bk.chain ? bk.payload_R : bk.R, b->has_n, st,
                                               (int)std::min<size_t>(bk.queue_cap, bk.chain ? (size_t)b->payload_strips : (size_t)max_waves),
-                                              b->queue_tasks.p + bk.queue_off, b->tie_count.p + i,
-                                              b->reads.p, b->regions.p, b->pool.p,
-                                              b->q2bit.p, b->qnmask.p, b->sp, b->cand_score.p,
+                                              b->queue_tasks.p + bk.queue_off, b->tie_count.p + i, seq, b->cand_score.p,
                                               b->cand_tstart.p, b->cand_tend.p,
                                               bk.chain ? b->chain_payload.p : nullptr, b->chain_cap, bk.chain ? 1 : 0));
             HIP_TRY(hipEventRecord(b->ev[ev++], st));
@@ -1827,6 +1810,9 @@ int nra_batch2d_sweep_flanks(nra_batch_t* b, const int8_t* read_strand)
     while (b->warm_ev.size() < 2 * np) { hipEvent_t e; HIP_TRY(g_handles.event(b->device, false, &e)); b->warm_ev.push_back(e); }
     while (b->ev.size() < 2 + 4 * np + 2) { hipEvent_t e; HIP_TRY(g_handles.event(b->device, true, &e)); b->ev.push_back(e); }
     hipStream_t st = b->stream;
+    // these sweeps read buffers of their own: the cell list's are rebuilt while they run
+    NraSeqArgs warm = seq_args(b);
+    warm.reads = b->warm_reads.p; warm.regions = b->warm_region.p; warm.pool = b->warm_pool.p;
     HIP_TRY(hipEventRecord(b->ev[0], st));
     HIP_TRY(hipEventRecord(b->phase_ev[0], st));
     HIP_TRY(hipEventRecord(b->fork2_ev, st));
@@ -1841,8 +1827,8 @@ int nra_batch2d_sweep_flanks(nra_batch_t* b, const int8_t* read_strand)
         // (prefix sweeps; extended reverse sweeps) carry about the same work and meet again in the cells, so neither side's
         // waves should be the older ones (two launches: the first one's waves issue first, its side finishes 1.4 ms ahead)
         HIP_TRY(hipEventRecord(b->ev[ev++], qa));
-        LAUNCH_TRY(nra_launch_joint_pk16(pt.R, b->warm_has_n, qa, (int)(pt.n_l + pt.n_r), b->warm_tasks.p + pt.off, b->warm_reads.p,
-                                         b->warm_region.p, b->warm_pool.p, b->q2bit.p, b->qnmask.p, b->sp, -1, b->jrstate.p, b->jlstate.p));
+        LAUNCH_TRY(nra_launch_joint_pk16(pt.R, b->warm_has_n, qa, (int)(pt.n_l + pt.n_r), b->warm_tasks.p + pt.off, warm, -1,
+                                         b->jrstate.p, b->jlstate.p));
         HIP_TRY(hipEventRecord(b->ev[ev++], qa));
         b->n_score_ev++;
         HIP_TRY(hipEventRecord(b->warm_ev[2 * i], qa));
@@ -1887,6 +1873,7 @@ namespace {
 int run_2d_flanks(nra_batch* b)
 {
     hipStream_t st = b->stream;
+    const NraSeqArgs seq = seq_args(b);
     const size_t nb = b->buckets.size();
     const size_t nr = std::max<size_t>((size_t)b->n_reads, 1);
     int ev = 2;
@@ -1917,17 +1904,14 @@ int run_2d_flanks(nra_batch* b)
             HIP_TRY(hipStreamWaitEvent(q, b->fork_ev, 0));
             HIP_TRY(hipEventRecord(b->ev[ev++], q));
             if (bk.chain) {
-                NraScoreParams raw = b->sp;
-                raw.min_score = 0;               // the probe compares raw scores
+                NraSeqArgs raw = seq;
+                raw.sp.min_score = 0;            // the probe compares raw scores
                 LAUNCH_TRY(nra_launch_payload_origin(bk.R, b->has_n, q, std::min(bk.n_probe, b->payload_strips),
                                                      b->probe_tasks.p + bk.probe_off, b->probe_count.p + i,
-                                                     b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p,
                                                      raw, b->probe_score.p, b->probe_dummy.p, nullptr,
                                                      b->chain_payload.p, b->chain_cap, 1));
             } else
-            LAUNCH_TRY(nra_launch_score_pk16(bk.R, b->has_n, q, bk.n_pair, b->pair_tasks.p + bk.pair_off,
-                                             b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p,
-                                             b->sp, b->probe_score.p));
+            LAUNCH_TRY(nra_launch_score_pk16(bk.R, b->has_n, q, bk.n_pair, b->pair_tasks.p + bk.pair_off, seq, b->probe_score.p));
             HIP_TRY(hipEventRecord(b->ev[ev++], q));
             b->n_ext_ev++;
             HIP_TRY(hipEventRecord(b->bdone[3 * i + 2], q));
@@ -1950,27 +1934,23 @@ int run_2d_flanks(nra_batch* b)
             // combine) is the longer one (config 3: 7.3 -> 7.1 ms of device time against the R side first)
             if (bk.n_jlpk > 0) {
                 HIP_TRY(hipEventRecord(b->ev[ev++], qb));
-                LAUNCH_TRY(nra_launch_joint_pk16(bk.R, b->has_n, qb, bk.n_jlpk, b->jlpk_tasks.p + bk.jlpk_off, b->reads.p,
-                                                 b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, 1, b->jlstate.p, nullptr));
+                LAUNCH_TRY(nra_launch_joint_pk16(bk.R, b->has_n, qb, bk.n_jlpk, b->jlpk_tasks.p + bk.jlpk_off, seq, 1, b->jlstate.p, nullptr));
                 HIP_TRY(hipEventRecord(b->ev[ev++], qb));
                 b->n_score_ev++;
             }
             if (bk.n_jrpk > 0) {
                 HIP_TRY(hipEventRecord(b->ev[ev++], qa));
-                LAUNCH_TRY(nra_launch_joint_pk16(bk.R, b->has_n, qa, bk.n_jrpk, b->jrpk_tasks.p + bk.jrpk_off, b->reads.p,
-                                                 b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, 0, b->jrstate.p, nullptr));
+                LAUNCH_TRY(nra_launch_joint_pk16(bk.R, b->has_n, qa, bk.n_jrpk, b->jrpk_tasks.p + bk.jrpk_off, seq, 0, b->jrstate.p, nullptr));
                 HIP_TRY(hipEventRecord(b->ev[ev++], qa));
                 b->n_score_ev++;
             }
             HIP_TRY(hipEventRecord(b->ev[ev++], qa));
             if (b->joint_v2)
-                LAUNCH_TRY(nra_launch_joint_bwd_ext(bk.R, b->has_n, qa, bk.n_jbwd, b->jbwd_tasks.p + bk.jbwd_off,
-                                                    b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p,
-                                                    b->sp, b->jrs.p, b->jra.p, b->jrstate.p));
+                LAUNCH_TRY(nra_launch_joint_bwd_ext(bk.R, b->has_n, qa, bk.n_jbwd, b->jbwd_tasks.p + bk.jbwd_off, seq, b->jrs.p, b->jra.p,
+                                                    b->jrstate.p));
             else
-            LAUNCH_TRY(nra_launch_joint_bwd(bk.R, b->has_n, qa, bk.n_jbwd, b->jbwd_tasks.p + bk.jbwd_off,
-                                            b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p,
-                                            b->sp, b->jsnap.p, b->jread_a.p, b->jrstate.p));
+            LAUNCH_TRY(nra_launch_joint_bwd(bk.R, b->has_n, qa, bk.n_jbwd, b->jbwd_tasks.p + bk.jbwd_off, seq, b->jsnap.p, b->jread_a.p,
+                                            b->jrstate.p));
             HIP_TRY(hipEventRecord(b->ev[ev++], qa));
             b->n_score_ev++;
             HIP_TRY(hipEventRecord(b->bdone[3 * i], qa));
@@ -1989,6 +1969,7 @@ int run_2d(nra_batch* b)
     }
     b->flanks_enqueued = false;          // (a second nra_batch_run of the same cell list starts over)
     hipStream_t st = b->stream;
+    const NraSeqArgs seq = seq_args(b);
     const size_t nb = b->buckets.size();
     const size_t nc = std::max<size_t>((size_t)b->n_cands, 1);
     int ev = b->ev_next;
@@ -2004,9 +1985,7 @@ int run_2d(nra_batch* b)
         if (!b->brute && !bk.chain) continue;
         HIP_TRY(hipEventRecord(b->ev[ev++], st));
         LAUNCH_TRY(nra_launch_payload_window(bk.R, b->has_n, st, std::min(bk.n_queue, bk.chain ? b->payload_strips : max_waves),
-                                          b->queue_tasks.p + bk.queue_off, b->queue_count.p + i,
-                                          b->reads.p, b->regions.p, b->pool.p,
-                                          b->q2bit.p, b->qnmask.p, b->sp, b->cand_score.p,
+                                          b->queue_tasks.p + bk.queue_off, b->queue_count.p + i, seq, b->cand_score.p,
                                           b->cand_tstart.p, nullptr, bk.chain ? b->chain_payload.p : nullptr,
                                           bk.chain ? b->chain_cap : 0, bk.chain ? 1 : 0));
         HIP_TRY(hipEventRecord(b->ev[ev++], st));
@@ -2026,31 +2005,25 @@ int run_2d(nra_batch* b)
                 if (g.bucket != (int)i) continue;
                 HIP_TRY(hipEventRecord(b->ev[ev++], qb));
                 if (b->joint_chain)
-                    LAUNCH_TRY(nra_launch_joint_prefix_cols(g.R, b->has_n, qb, g.n_pre, b->jpre_tasks.p + g.pre_off,
-                                                            b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p,
-                                                            b->sp, b->jk1list.p, b->jstate.p, b->jlstate.p));
+                    LAUNCH_TRY(nra_launch_joint_prefix_cols(g.R, b->has_n, qb, g.n_pre, b->jpre_tasks.p + g.pre_off, seq, b->jk1list.p,
+                                                            b->jstate.p, b->jlstate.p));
                 else
-                LAUNCH_TRY(nra_launch_joint_prefix(g.R, b->has_n, qb, g.n_pre, b->jpre_tasks.p + g.pre_off,
-                                                   b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p,
-                                                   b->sp, b->jk1list.p, b->jstate.p, b->jlstate.p));
+                LAUNCH_TRY(nra_launch_joint_prefix(g.R, b->has_n, qb, g.n_pre, b->jpre_tasks.p + g.pre_off, seq, b->jk1list.p,
+                                                   b->jstate.p, b->jlstate.p));
                 HIP_TRY(hipEventRecord(b->ev[ev++], qb));
                 b->n_score_ev++;
                 if (first && !b->joint_v2) HIP_TRY(hipStreamWaitEvent(qb, b->bdone[3 * i], 0));     // the tails read the R side
                 first = false;
                 HIP_TRY(hipEventRecord(b->ev[ev++], qb));
                 if (b->joint_chain)
-                    LAUNCH_TRY(nra_launch_joint_midscan(g.R, b->has_n, qb, g.n_tail, b->jtail_tasks.p + g.tail_off,
-                                                         b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p,
-                                                         b->sp, b->jk1list.p, b->jstate.p, b->jfs.p, b->jfb.p, nullptr));
+                    LAUNCH_TRY(nra_launch_joint_midscan(g.R, b->has_n, qb, g.n_tail, b->jtail_tasks.p + g.tail_off, seq, b->jk1list.p,
+                                                         b->jstate.p, b->jfs.p, b->jfb.p, nullptr));
                 else if (b->joint_v2)
-                    LAUNCH_TRY(nra_launch_joint_mid(g.R, b->has_n, qb, g.n_tail, b->jtail_tasks.p + g.tail_off,
-                                                    b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p,
-                                                    b->sp, b->jstate.p, b->jfs.p, b->jfb.p));
+                    LAUNCH_TRY(nra_launch_joint_mid(g.R, b->has_n, qb, g.n_tail, b->jtail_tasks.p + g.tail_off, seq, b->jstate.p,
+                                                    b->jfs.p, b->jfb.p));
                 else
-                LAUNCH_TRY(nra_launch_joint_tail(g.R, b->has_n, qb, g.n_tail, b->jtail_tasks.p + g.tail_off,
-                                                 b->reads.p, b->regions.p, b->pool.p, b->q2bit.p, b->qnmask.p,
-                                                 b->sp, b->jstate.p, b->jsnap.p, b->jread_a.p, b->cand_score.p,
-                                                 b->cand_tstart.p));
+                LAUNCH_TRY(nra_launch_joint_tail(g.R, b->has_n, qb, g.n_tail, b->jtail_tasks.p + g.tail_off, seq, b->jstate.p,
+                                                 b->jsnap.p, b->jread_a.p, b->cand_score.p, b->cand_tstart.p));
                 HIP_TRY(hipEventRecord(b->ev[ev++], qb));
                 b->n_score_ev++;
             }
@@ -2152,6 +2125,7 @@ int nra_batch2d_refine(nra_batch_t* b, int32_t buf1, int32_t buf2, const double*
     }
 
     hipStream_t st = b->stream;
+    const NraSeqArgs seq = seq_args(b);
     int ev = b->ev_next;
     const size_t nc = (size_t)std::max<int64_t>(cap * n_reads, 1);
     HIP_TRY(hipMemsetAsync(b->rf_words.p, 0, 4 * sizeof(int64_t), st));
@@ -2170,9 +2144,8 @@ int nra_batch2d_refine(nra_batch_t* b, int32_t buf1, int32_t buf2, const double*
         hipStream_t qb = b->bstreams[2 * i + 1];
         HIP_TRY(hipStreamWaitEvent(qb, b->fork2_ev, 0));
         HIP_TRY(hipEventRecord(b->ev[ev++], qb));
-        LAUNCH_TRY(nra_launch_joint_midscan(bk.R, b->has_n, qb, n_mid, b->rf_mid_tasks.p + rp.mid_off[i], b->reads.p, b->regions.p,
-                                            b->pool.p, b->q2bit.p, b->qnmask.p, b->sp, nullptr, b->jstate.p, b->rf_fs.p,
-                                            b->rf_fb.p, b->rf_rows.p));
+        LAUNCH_TRY(nra_launch_joint_midscan(bk.R, b->has_n, qb, n_mid, b->rf_mid_tasks.p + rp.mid_off[i], seq, nullptr, b->jstate.p,
+                                            b->rf_fs.p, b->rf_fb.p, b->rf_rows.p));
         HIP_TRY(hipEventRecord(b->ev[ev++], qb));
         b->n_score_ev++;
         HIP_TRY(hipEventRecord(b->ev[ev++], qb));
@@ -2411,13 +2384,12 @@ int nra_align_pairs(int device, int32_t n_seqs, const char* seqs, const int64_t*
     HIP_TRY(hipMemset(d_score.p, 0xff, (size_t)n_pairs * 4));
     HIP_TRY(hipMemset(d_ts.p, 0xff, (size_t)n_pairs * 4));
     HIP_TRY(hipMemset(d_te.p, 0xff, (size_t)n_pairs * 4));
-    const NraScoreParams sp = to_params(*sc);
+    const NraSeqArgs seq{d_reads.p, d_regs.p, d_pool.p, d_q2.p, d_nm.p, to_params(*sc)};     // this call's own buffers
     for (size_t i = 0; i < groups.size(); ++i) {
         const Group& g = groups[i];
         LAUNCH_TRY(nra_launch_payload_origin(g.R, ps.has_n ? 1 : 0, nullptr,
                                              std::min(counts[i], g.chain ? pair_strips : 256 * 16),
-                                             d_tasks.p + offs[i], d_counts.p + i, d_reads.p, d_regs.p,
-                                             d_pool.p, d_q2.p, d_nm.p, sp, d_score.p, d_ts.p, d_te.p,
+                                             d_tasks.p + offs[i], d_counts.p + i, seq, d_score.p, d_ts.p, d_te.p,
                                              g.chain ? d_chain.p : nullptr, g.chain ? chain_cap : 0, g.wide ? 1 : 0));
     }
     HIP_TRY(hipDeviceSynchronize());
@@ -2534,21 +2506,20 @@ int align_cigar_pairs(int device, int32_t n_seqs, const char* seqs, const int64_
         HIP_TRY(hipMemsetAsync(d_words.p, 0, 4 * sizeof(int32_t), nullptr));
         HIP_TRY(hipMemsetAsync(d_strips.p, 0, ((size_t)strip_granules + 1) * 8, nullptr));
     }
-    const NraScoreParams sp = to_params(*sc);
+    const NraSeqArgs seq{d_reads.p, d_regs.p, d_pool.p, d_q2.p, d_nm.p, to_params(*sc)};     // this call's own buffers
     int n_block_launches = 0;
     for (const Launch& L : launches) {
         const size_t off = L.off;
         if (L.blocks) {
             LAUNCH_TRY(nra_launch_trace_fill_mt(L.R, ps.has_n ? 1 : 0, L.wide ? 1 : 0, nullptr, L.n_blocks,
-                                                d_blocks.p + L.blk_off, d_words.p + n_block_launches, d_tasks.p + off,
-                                                d_reads.p, d_regs.p, d_pool.p, d_q2.p, d_nm.p, sp, d_trace.p, d_best.p,
-                                                d_strips.p, 1u, d_words.p + 3));
+                                                d_blocks.p + L.blk_off, d_words.p + n_block_launches, d_tasks.p + off, seq,
+                                                d_trace.p, d_best.p, d_strips.p, 1u, d_words.p + 3));
             LAUNCH_TRY(nra_launch_trace_best(nullptr, L.count, d_tasks.p + off, d_reads.p, block_rows, L.wide ? 1 : 0,
-                                             d_best.p, sp, d_fill.p + off * 5));
+                                             d_best.p, seq.sp, d_fill.p + off * 5));
             ++n_block_launches;
         } else {
-            LAUNCH_TRY(nra_launch_trace_fill(L.R, ps.has_n ? 1 : 0, nullptr, L.count, d_tasks.p + off,
-                                             d_reads.p, d_regs.p, d_pool.p, d_q2.p, d_nm.p, sp, d_trace.p, d_fill.p + off * 5));
+            LAUNCH_TRY(nra_launch_trace_fill(L.R, ps.has_n ? 1 : 0, nullptr, L.count, d_tasks.p + off, seq, d_trace.p,
+                                             d_fill.p + off * 5));
         }
         LAUNCH_TRY(nra_launch_trace_back(nullptr, L.count, d_tasks.p + off, d_reads.p, d_regs.p, d_trace.p,
                                          d_fill.p + off * 5, d_ops.p, d_back.p + off * 3));

@@ -158,6 +158,35 @@ struct NraScoreParams {
     int32_t min_score;
 };
 
+// What every sequence kernel reads (1D and joint sweeps, payload and score kernels, trace fills): the reads and regions
+// of the batch, the code pool, the 2-bit query pool with its N mask, and the scores.  Passed by value to the launchers
+// (every nra_launch_* below that scores sequences takes one); a launch that needs another field copies the struct and
+// replaces that field.  Most kernels keep parameters of their own, filled from these fields (nra_device.h).
+struct NraSeqArgs {
+    const NraDevRead* reads;
+    const NraDevRegion* regions;
+    const uint8_t* pool;
+    const uint32_t* q2bit;
+    const uint32_t* qnmask;
+    NraScoreParams sp;
+};
+
+// ... and what every 1D sweep adds: per read its candidate window [kmin, kmax] and the offset of its candidates (coff);
+// the R-side snapshots and A (read_a) that the reverse sweeps write and the forward sweeps read; the candidates' scores
+// and flank verdicts that the forward sweeps write (a reverse launcher nulls these two in its copy).  What differs from
+// launch to launch -- tasks and their number, relax_c, redo, the quanta words, strips, epochs, give-up words -- stays a
+// parameter of its own.
+struct NraSweepArgs {
+    NraSeqArgs seq;
+    const int32_t* kmin;
+    const int32_t* kmax;
+    const uint32_t* coff;
+    int32_t* snap;
+    int32_t* read_a;
+    int32_t* cand_score;
+    uint8_t* cand_flag;
+};
+
 // rows-per-lane instantiations (a read of qlen rows uses the smallest R with 64*R >= qlen)
 #ifndef NRA_R_LIST
 #define NRA_R_LIST(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) \
@@ -661,26 +690,17 @@ int nra_launch_read_methylation(hipStream_t st, int n_grid, int n_reads, const N
 
 // launchers (nra_kernels.hip).  All asynchronous on `st`; return hipError_t as int.
 int nra_launch_score_pk16(int R, int has_n, hipStream_t st, int n_tasks,
-                          const NraPairTask* tasks, const NraDevRead* reads,
-                          const NraDevRegion* regions, const uint8_t* pool,
-                          const uint32_t* q2bit, const uint32_t* qnmask,
-                          NraScoreParams sp, int32_t* out_score);
+                          const NraPairTask* tasks, NraSeqArgs seq, int32_t* out_score);
 
 // payload kernels walk a device-side queue of *count tasks with a grid stride.  ORIGIN outputs (score, tstart,
 // tend); WINDOW outputs (score, wscore).  chain_buf != NULL: row-block chaining (n_waves strips of
 // 6 * chain_cap cells each); wide: int64 cells (R = NRA_WIDE_R_SMALL / NRA_WIDE_R_LARGE, or chained)
 int nra_launch_payload_origin(int R, int has_n, hipStream_t st, int n_waves,
-                              const NraTask* tasks, const int32_t* count,
-                              const NraDevRead* reads, const NraDevRegion* regions,
-                              const uint8_t* pool, const uint32_t* q2bit, const uint32_t* qnmask,
-                              NraScoreParams sp,
+                              const NraTask* tasks, const int32_t* count, NraSeqArgs seq,
                               int32_t* out_score, int32_t* out_p, int32_t* out_tend,
                               void* chain_buf, int chain_cap, int wide);
 int nra_launch_payload_window(int R, int has_n, hipStream_t st, int n_waves,
-                              const NraTask* tasks, const int32_t* count,
-                              const NraDevRead* reads, const NraDevRegion* regions,
-                              const uint8_t* pool, const uint32_t* q2bit, const uint32_t* qnmask,
-                              NraScoreParams sp,
+                              const NraTask* tasks, const int32_t* count, NraSeqArgs seq,
                               int32_t* out_score, int32_t* out_p, int32_t* out_tend,
                               void* chain_buf, int chain_cap, int wide);
 
@@ -688,18 +708,9 @@ int nra_launch_payload_window(int R, int has_n, hipStream_t st, int n_waves,
 // (per read: read_a); the forward sweep combines and writes Score(k) + the flank-test verdict (0 fail,
 // 1 pass, 2 ambiguous).  chain: int32 cells, one read per task, min(n_tasks, n_strips) waves
 int nra_launch_sweep_bwd(int R, int has_n, int chain, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
-                         const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                         const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                         const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                         int32_t* snap,
-                         int32_t* read_a, int32_t* chain_buf, int chain_cap, int n_strips);
+                         NraSweepArgs a, int32_t* chain_buf, int chain_cap, int n_strips);
 int nra_launch_sweep_fwd(int R, int has_n, int chain, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
-                         const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                         const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                         const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                         int32_t* snap,
-                         int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int32_t* chain_buf,
-                         int chain_cap, int n_strips);
+                         NraSweepArgs a, int32_t* chain_buf, int chain_cap, int n_strips);
 
 // the same sweeps with the lane-to-lane hand-off through an LDS ring (k_sweep_ring: one read block per wave,
 // forward sweep skewed by the unit length so that the junction combine runs on every m-th step only);
@@ -710,15 +721,9 @@ int nra_launch_sweep_fwd(int R, int has_n, int chain, hipStream_t st, int n_task
 #define NRA_SWEEP_RING_MAX_M 8
 #define NRA_RING32_MAX_R 24
 int nra_launch_sweep_ring_bwd(int R, int has_n, int half, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
-                              const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                              const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                              const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                              int32_t* snap, int32_t* read_a, int relax_c, int32_t* redo);
+                              NraSweepArgs a, int relax_c, int32_t* redo);
 int nra_launch_sweep_ring_fwd(int R, int has_n, int half, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
-                              const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                              const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                              const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                              int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo);
+                              NraSweepArgs a, int relax_c, int32_t* redo);
 // relax_c > 0 (these and the quanta launcher): the taint scheme -- the anchor columns up to
 // relax_c bases from the junction run the relaxed cell, and redo[task] is set where that may have reached an output;
 // relax_c <= 0 and redo non-null: the exact sweeps of the flagged tasks only (the re-sweep); both 0 / null: the exact sweeps.
@@ -768,12 +773,8 @@ int nra_launch_sweep_ring_fwd(int R, int has_n, int half, hipStream_t st, int n_
 #define NRA_Q_STEPS_REV(l3, half) ((l3) + ((half) ? 31 : 63))
 #define NRA_Q_STEPS_FWD(l1, m, kmax, half) ((l1) + (m) * (kmax) + ((half) ? 31 : 63) * (m))
 int nra_launch_sweep_ringq(int R, int has_n, int half, hipStream_t st, int n_quanta, const uint32_t* qlist, int qsteps, int n_tasks, int32_t* ticket,
-                           int32_t* arrivals, int32_t* giveup, int32_t* qstate, const NraSweepTask* tasks,
-                           const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                           const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                           const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                           int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo,
-                           int sat_steps, int32_t* sat_count);
+                           int32_t* arrivals, int32_t* giveup, int32_t* qstate, const NraSweepTask* tasks, NraSweepArgs a,
+                           int relax_c, int32_t* redo, int sat_steps, int32_t* sat_count);
 
 // chained LDS-ring sweeps (k_sweep_ringchain): reads of more than NRA_RING_CHAIN_MIN_ROWS rows as row blocks of
 // 64 * NRA_RING_CHAIN_R; wide = 0: two reads per wave in packed int16, 1: one read per wave in int32 cells.
@@ -790,69 +791,38 @@ int nra_launch_sweep_ringq(int R, int has_n, int half, hipStream_t st, int n_qua
                                                // rows per lane, one wave per SIMD (the batch takes the cheaper form: nra_batch1d_create)
 #define NRA_RING_MT_R_MIN 12                   // ... down to 12: the host takes the height that pads a bucket's reads least
 int nra_launch_sweep_ringchain_bwd(int R, int has_n, int wide, hipStream_t st, int n_tasks,
-                                   const NraSweepTask* tasks, const NraDevRead* reads,
-                                   const NraDevRegion* regions, const uint8_t* pool,
-                                   const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                   const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                   int32_t* snap, int32_t* read_a, int32_t* chain_buf, int chain_cap, int n_strips);
+                                   const NraSweepTask* tasks, NraSweepArgs a, int32_t* chain_buf, int chain_cap, int n_strips);
 int nra_launch_sweep_ringchain_fwd(int R, int has_n, int wide, hipStream_t st, int n_tasks,
-                                   const NraSweepTask* tasks, const NraDevRead* reads,
-                                   const NraDevRegion* regions, const uint8_t* pool,
-                                   const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                   const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                   int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag,
-                                   int32_t* chain_buf, int chain_cap, int n_strips);
+                                   const NraSweepTask* tasks, NraSweepArgs a, int32_t* chain_buf, int chain_cap, int n_strips);
 
 // chained LDS-ring sweeps with the row blocks of a read as concurrent waves (k_sweep_ringmt).  `ticket`: one int32
 // (zeroed by the launcher); `strips`: n strips x 5 x chain_cap granules, zeroed once; `epoch`: unique per launch,
 // never 0; `error`: launch-wide give-up word (zeroed by the host before the run, read back after it)
 int nra_launch_sweep_ringmt_bwd(int R, int has_n, int wide, hipStream_t st, int n_blocks,
                                 const NraChainBlock* blocks, int32_t* ticket, const NraSweepTask* tasks,
-                                const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                int32_t* snap, int32_t* read_a, uint64_t* strips, int chain_cap,
-                                uint32_t epoch, int32_t* error);
+                                NraSweepArgs a, uint64_t* strips, int chain_cap, uint32_t epoch, int32_t* error);
 int nra_launch_sweep_ringmt_fwd(int R, int has_n, int wide, hipStream_t st, int n_blocks,
                                 const NraChainBlock* blocks, int32_t* ticket, const NraSweepTask* tasks,
-                                const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag,
-                                uint64_t* strips, int chain_cap, uint32_t epoch, int32_t* error);
+                                NraSweepArgs a, uint64_t* strips, int chain_cap, uint32_t epoch, int32_t* error);
 
 // 2D junction decomposition (nra_joint.hip)
-int nra_launch_joint_bwd(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks,
-                         const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                         const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
+int nra_launch_joint_bwd(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks, NraSeqArgs seq,
                          int32_t* snap, int32_t* read_a, const int32_t* pstate);
-int nra_launch_joint_prefix(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks,
-                            const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                            const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
+int nra_launch_joint_prefix(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks, NraSeqArgs seq,
                             const int32_t* k1list, int32_t* state, const int32_t* pstate);
 // packed int16 sweep of the payload-free columns (dir 1: L, dir 0: rev(R)), two reads per wave; dir < 0: both sides in one
 // launch, an L-side task marked in bit 63 of its state index and leaving its state at pstate_l
-int nra_launch_joint_pk16(int R, int has_n, hipStream_t st, int n_tasks, const NraJointPairTask* tasks,
-                          const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                          const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp, int dir,
+int nra_launch_joint_pk16(int R, int has_n, hipStream_t st, int n_tasks, const NraJointPairTask* tasks, NraSeqArgs seq, int dir,
                           int32_t* pstate, int32_t* pstate_l);
 // junction at the end of mid: extended reverse sweeps, MID sweeps, the per-cell combine
-int nra_launch_joint_bwd_ext(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks,
-                             const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                             const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
+int nra_launch_joint_bwd_ext(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks, NraSeqArgs seq,
                              int32_t* rsnap, int32_t* ra, const int32_t* pstate);
-int nra_launch_joint_mid(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks,
-                         const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                         const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
+int nra_launch_joint_mid(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks, NraSeqArgs seq,
                          int32_t* state, int32_t* fsnap, int32_t* fb);
 // ... with the MID part as column-parallel scans (k_joint_midscan): the prefix sweep leaves column states (each lane on its own step)
-int nra_launch_joint_prefix_cols(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks,
-                                 const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                 const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
+int nra_launch_joint_prefix_cols(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks, NraSeqArgs seq,
                                  const int32_t* k1list, int32_t* state, const int32_t* pstate);
-int nra_launch_joint_midscan(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks,
-                             const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                             const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
+int nra_launch_joint_midscan(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks, NraSeqArgs seq,
                              const int32_t* k1list, const int32_t* state, int32_t* fsnap, int32_t* fb,
                              const NraGridRow* rows);
 int nra_launch_joint_combine(hipStream_t st, int n_tasks, const NraJointCombineTask* tasks, const NraDevRead* reads,
@@ -864,25 +834,19 @@ int nra_launch_joint_refine_route(hipStream_t st, int n_reads, const uint8_t* st
                                   const double* lo2, const double* hi2, int buf1, int buf2, const NraGridRow* keep,
                                   NraGridRow* rows, uint32_t* cell_cnt, const int32_t* rowspad, const NraDevRead* reads,
                                   const NraDevRegion* regions, unsigned long long* words);
-int nra_launch_joint_tail(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks,
-                          const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                          const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
+int nra_launch_joint_tail(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks, NraSeqArgs seq,
                           int32_t* state, int32_t* snap, int32_t* read_a, int32_t* cell_score,
                           int32_t* cell_wscore);
 
 // alignment paths (nra_trace.hip)
-int nra_launch_trace_fill(int R, int has_n, hipStream_t st, int n_tasks, const NraTraceTask* tasks,
-                          const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                          const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
+int nra_launch_trace_fill(int R, int has_n, hipStream_t st, int n_tasks, const NraTraceTask* tasks, NraSeqArgs seq,
                           uint8_t* trace, int32_t* out);
 int nra_launch_trace_back(hipStream_t st, int n_tasks, const NraTraceTask* tasks, const NraDevRead* reads,
                           const NraDevRegion* regions, const uint8_t* trace, const int32_t* fill_out,
                           uint8_t* ops, int32_t* out);
 int nra_launch_trace_fill_mt(int R, int has_n, int wide, hipStream_t st, int n_blocks, const NraTraceBlock* blocks,
-                             int32_t* ticket, const NraTraceTask* tasks, const NraDevRead* reads,
-                             const NraDevRegion* regions, const uint8_t* pool, const uint32_t* q2bit,
-                             const uint32_t* qnmask, NraScoreParams sp, uint8_t* trace, int32_t* blk_best,
-                             uint64_t* strips, uint32_t epoch, int32_t* error);
+                             int32_t* ticket, const NraTraceTask* tasks, NraSeqArgs seq, uint8_t* trace,
+                             int32_t* blk_best, uint64_t* strips, uint32_t epoch, int32_t* error);
 int nra_launch_trace_best(hipStream_t st, int n_tasks, const NraTraceTask* tasks, const NraDevRead* reads,
                           int block_rows, int wide, const int32_t* blk_best, NraScoreParams sp, int32_t* out);
 

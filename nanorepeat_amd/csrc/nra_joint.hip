@@ -538,9 +538,7 @@ __global__ __launch_bounds__(WAVE) void k_joint_pk16(int n_tasks, const NraJoint
 
 // ------------------------------------------------------------------------------------
 template <int DIR>
-static int launch_joint(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks,
-                        const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                        const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
+static int launch_joint(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks, NraSeqArgs seq,
                         const int32_t* k1list, int32_t* state,
                         int32_t* snap, int32_t* read_a, int32_t* cell_score, int32_t* cell_wscore,
                         const int32_t* pstate)
@@ -548,8 +546,8 @@ static int launch_joint(int R, int has_n, hipStream_t st, int n_tasks, const Nra
     if (n_tasks <= 0) return 0;
 #define CASE(r)                                                                                     \
     case r:                                                                                         \
-        if (has_n) k_joint_sweep<r, true, DIR><<<n_tasks, WAVE, 0, st>>>(n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, k1list, state, snap, read_a, cell_score, cell_wscore, pstate); \
-        else k_joint_sweep<r, false, DIR><<<n_tasks, WAVE, 0, st>>>(n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, k1list, state, snap, read_a, cell_score, cell_wscore, pstate);       \
+        if (has_n) k_joint_sweep<r, true, DIR><<<n_tasks, WAVE, 0, st>>>(n_tasks, tasks, NRA_SEQ_FIELDS(seq), k1list, state, snap, read_a, cell_score, cell_wscore, pstate); \
+        else k_joint_sweep<r, false, DIR><<<n_tasks, WAVE, 0, st>>>(n_tasks, tasks, NRA_SEQ_FIELDS(seq), k1list, state, snap, read_a, cell_score, cell_wscore, pstate);       \
         break;
     switch (R) {
         NRA_R_LIST(CASE)
@@ -560,33 +558,27 @@ static int launch_joint(int R, int has_n, hipStream_t st, int n_tasks, const Nra
 }
 
 #if NRA_HAS_PART(7)
-extern "C" int nra_launch_joint_bwd(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks,
-                                    const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                    const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
+extern "C" int nra_launch_joint_bwd(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks, NraSeqArgs seq,
                                     int32_t* snap, int32_t* read_a, const int32_t* pstate)
 {
-    return launch_joint<0>(R, has_n, st, n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, nullptr, nullptr,
+    return launch_joint<0>(R, has_n, st, n_tasks, tasks, seq, nullptr, nullptr,
                            snap, read_a, nullptr, nullptr, pstate);
 }
 #endif
 #if NRA_HAS_PART(8)
-extern "C" int nra_launch_joint_prefix(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks,
-                                       const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                       const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
+extern "C" int nra_launch_joint_prefix(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks, NraSeqArgs seq,
                                        const int32_t* k1list, int32_t* state, const int32_t* pstate)
 {
-    return launch_joint<1>(R, has_n, st, n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, k1list, state,
+    return launch_joint<1>(R, has_n, st, n_tasks, tasks, seq, k1list, state,
                            nullptr, nullptr, nullptr, nullptr, pstate);
 }
 #endif
 #if NRA_HAS_PART(10)
-extern "C" int nra_launch_joint_tail(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks,
-                                     const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                     const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
+extern "C" int nra_launch_joint_tail(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks, NraSeqArgs seq,
                                      int32_t* state, int32_t* snap, int32_t* read_a, int32_t* cell_score,
                                      int32_t* cell_wscore)
 {
-    return launch_joint<2>(R, has_n, st, n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, nullptr, state,
+    return launch_joint<2>(R, has_n, st, n_tasks, tasks, seq, nullptr, state,
                            snap, read_a, cell_score, cell_wscore, nullptr);
 }
 #endif
@@ -756,27 +748,23 @@ __global__ __launch_bounds__(WAVE) void k_joint_midscan(int n_tasks, const NraJo
 }
 
 #if NRA_HAS_PART(22)
-extern "C" int nra_launch_joint_prefix_cols(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks,
-                                            const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                            const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
+extern "C" int nra_launch_joint_prefix_cols(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks, NraSeqArgs seq,
                                             const int32_t* k1list, int32_t* state, const int32_t* pstate)
 {
-    return launch_joint<5>(R, has_n, st, n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, k1list, state,
+    return launch_joint<5>(R, has_n, st, n_tasks, tasks, seq, k1list, state,
                            nullptr, nullptr, nullptr, nullptr, pstate);
 }
 #endif
 #if NRA_HAS_PART(23)
-extern "C" int nra_launch_joint_midscan(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks,
-                                        const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                        const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
+extern "C" int nra_launch_joint_midscan(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks, NraSeqArgs seq,
                                         const int32_t* k1list, const int32_t* state, int32_t* fsnap, int32_t* fb,
                                         const NraGridRow* rows)
 {
     if (n_tasks <= 0) return 0;
 #define CASE(r)                                                                                     \
     case r:                                                                                         \
-        if (has_n) k_joint_midscan<r, true><<<n_tasks, WAVE, 0, st>>>(n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, k1list, state, fsnap, fb, rows); \
-        else k_joint_midscan<r, false><<<n_tasks, WAVE, 0, st>>>(n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, k1list, state, fsnap, fb, rows);       \
+        if (has_n) k_joint_midscan<r, true><<<n_tasks, WAVE, 0, st>>>(n_tasks, tasks, NRA_SEQ_FIELDS(seq), k1list, state, fsnap, fb, rows); \
+        else k_joint_midscan<r, false><<<n_tasks, WAVE, 0, st>>>(n_tasks, tasks, NRA_SEQ_FIELDS(seq), k1list, state, fsnap, fb, rows);       \
         break;
     switch (R) {
         NRA_R_LIST(CASE)
@@ -787,22 +775,18 @@ extern "C" int nra_launch_joint_midscan(int R, int has_n, hipStream_t st, int n_
 }
 #endif
 #if NRA_HAS_PART(20)
-extern "C" int nra_launch_joint_bwd_ext(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks,
-                                        const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                        const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
+extern "C" int nra_launch_joint_bwd_ext(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks, NraSeqArgs seq,
                                         int32_t* rsnap, int32_t* ra, const int32_t* pstate)
 {
-    return launch_joint<3>(R, has_n, st, n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, nullptr, nullptr,
+    return launch_joint<3>(R, has_n, st, n_tasks, tasks, seq, nullptr, nullptr,
                            rsnap, ra, nullptr, nullptr, pstate);
 }
 #endif
 #if NRA_HAS_PART(21)
-extern "C" int nra_launch_joint_mid(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks,
-                                    const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                    const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
+extern "C" int nra_launch_joint_mid(int R, int has_n, hipStream_t st, int n_tasks, const NraJointTask* tasks, NraSeqArgs seq,
                                     int32_t* state, int32_t* fsnap, int32_t* fb)
 {
-    return launch_joint<4>(R, has_n, st, n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, nullptr, state,
+    return launch_joint<4>(R, has_n, st, n_tasks, tasks, seq, nullptr, state,
                            fsnap, fb, nullptr, nullptr, nullptr);
 }
 
@@ -988,16 +972,14 @@ extern "C" int nra_launch_joint_refine_route(hipStream_t st, int n_reads, const 
 }
 #endif
 #if NRA_HAS_PART(17)
-extern "C" int nra_launch_joint_pk16(int R, int has_n, hipStream_t st, int n_tasks, const NraJointPairTask* tasks,
-                                     const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                     const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp, int dir,
+extern "C" int nra_launch_joint_pk16(int R, int has_n, hipStream_t st, int n_tasks, const NraJointPairTask* tasks, NraSeqArgs seq, int dir,
                                      int32_t* pstate, int32_t* pstate_l)
 {
     if (n_tasks <= 0) return 0;
 #define CASE(r)                                                                                     \
     case r:                                                                                         \
-        if (has_n) k_joint_pk16<r, true><<<n_tasks, WAVE, 0, st>>>(n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, dir, pstate, pstate_l); \
-        else k_joint_pk16<r, false><<<n_tasks, WAVE, 0, st>>>(n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, dir, pstate, pstate_l);       \
+        if (has_n) k_joint_pk16<r, true><<<n_tasks, WAVE, 0, st>>>(n_tasks, tasks, NRA_SEQ_FIELDS(seq), dir, pstate, pstate_l); \
+        else k_joint_pk16<r, false><<<n_tasks, WAVE, 0, st>>>(n_tasks, tasks, NRA_SEQ_FIELDS(seq), dir, pstate, pstate_l);       \
         break;
     switch (R) {
         NRA_R_LIST(CASE)

@@ -42,14 +42,10 @@
 // k_score_pk16: two candidates per wave, packed int16
 // ------------------------------------------------------------------------------------
 template <int R, bool HAS_N>
-__global__ __launch_bounds__(WAVE) void k_score_pk16(int n_tasks, const NraPairTask* __restrict__ tasks,
-                                                     const NraDevRead* __restrict__ reads,
-                                                     const NraDevRegion* __restrict__ regions,
-                                                     const uint8_t* __restrict__ pool,
-                                                     const uint32_t* __restrict__ q2bit,
-                                                     const uint32_t* __restrict__ qnmask,
-                                                     NraScoreParams sp, int32_t* __restrict__ out_score)
+__global__ __launch_bounds__(WAVE) void k_score_pk16(int n_tasks, const NraPairTask* __restrict__ tasks, NraSeqArgs seq,
+                                                     int32_t* __restrict__ out_score)
 {
+    NRA_SEQ_LOCALS(seq)
     const int task = blockIdx.x;
     if (task >= n_tasks) return;
     const int lane = threadIdx.x;
@@ -488,16 +484,13 @@ __global__ __launch_bounds__(WAVE) void k_select_2d(int n_reads, const uint32_t*
 // ------------------------------------------------------------------------------------
 #if NRA_HAS_PART(1)
 extern "C" int nra_launch_score_pk16(int R, int has_n, hipStream_t st, int n_tasks,
-                                     const NraPairTask* tasks, const NraDevRead* reads,
-                                     const NraDevRegion* regions, const uint8_t* pool,
-                                     const uint32_t* q2bit, const uint32_t* qnmask,
-                                     NraScoreParams sp, int32_t* out_score)
+                                     const NraPairTask* tasks, NraSeqArgs seq, int32_t* out_score)
 {
     if (n_tasks <= 0) return 0;
 #define CASE(r)                                                                                     \
     case r:                                                                                         \
-        if (has_n) k_score_pk16<r, true><<<n_tasks, WAVE, 0, st>>>(n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, out_score); \
-        else k_score_pk16<r, false><<<n_tasks, WAVE, 0, st>>>(n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, out_score);       \
+        if (has_n) k_score_pk16<r, true><<<n_tasks, WAVE, 0, st>>>(n_tasks, tasks, seq, out_score);   \
+        else k_score_pk16<r, false><<<n_tasks, WAVE, 0, st>>>(n_tasks, tasks, seq, out_score);        \
         break;
     switch (R) {
         NRA_R_LIST(CASE)
@@ -514,12 +507,10 @@ extern "C" int nra_launch_score_pk16(int R, int has_n, hipStream_t st, int n_tas
 // NRA_CHAIN_R / NRA_CHAIN_R_TEST (chained); int32 cells: every R unchained, chained as above
 template <int MODE>
 static int launch_payload(int R, int has_n, int wide, hipStream_t st, int n_waves, const NraTask* tasks,
-                          const int32_t* count, const NraDevRead* reads,
-                          const NraDevRegion* regions, const uint8_t* pool, const uint32_t* q2bit,
-                          const uint32_t* qnmask, NraScoreParams sp, int32_t* out_score,
+                          const int32_t* count, NraSeqArgs seq, int32_t* out_score,
                           int32_t* out_p, int32_t* out_tend, void* chain_buf = nullptr, int chain_cap = 0)
 {
-#define PARGS tasks, count, reads, regions, pool, q2bit, qnmask, sp, out_score, out_p, out_tend, chain_buf, chain_cap
+#define PARGS tasks, count, NRA_SEQ_FIELDS(seq), out_score, out_p, out_tend, chain_buf, chain_cap
 #define LAUNCH(CELL, r, chain)                                                                      \
     do {                                                                                            \
         if (has_n) k_payload<CELL, r, true, MODE, chain><<<n_waves, WAVE, 0, st>>>(PARGS);          \
@@ -550,26 +541,22 @@ static int launch_payload(int R, int has_n, int wide, hipStream_t st, int n_wave
 
 #if NRA_HAS_PART(2)
 extern "C" int nra_launch_payload_origin(int R, int has_n, hipStream_t st, int n_waves,
-                                         const NraTask* tasks, const int32_t* count,
-                                         const NraDevRead* reads, const NraDevRegion* regions,
-                                         const uint8_t* pool, const uint32_t* q2bit, const uint32_t* qnmask,
-                                         NraScoreParams sp, int32_t* out_score, int32_t* out_p,
+                                         const NraTask* tasks, const int32_t* count, NraSeqArgs seq,
+                                         int32_t* out_score, int32_t* out_p,
                                          int32_t* out_tend, void* chain_buf, int chain_cap, int wide)
 {
     if (n_waves <= 0) return 0;
-    return launch_payload<0>(R, has_n, wide, st, n_waves, tasks, count, reads, regions, pool, q2bit, qnmask, sp, out_score, out_p, out_tend, chain_buf, chain_cap);
+    return launch_payload<0>(R, has_n, wide, st, n_waves, tasks, count, seq, out_score, out_p, out_tend, chain_buf, chain_cap);
 }
 #endif
 #if NRA_HAS_PART(3)
 extern "C" int nra_launch_payload_window(int R, int has_n, hipStream_t st, int n_waves,
-                                         const NraTask* tasks, const int32_t* count,
-                                         const NraDevRead* reads, const NraDevRegion* regions,
-                                         const uint8_t* pool, const uint32_t* q2bit, const uint32_t* qnmask,
-                                         NraScoreParams sp, int32_t* out_score, int32_t* out_p,
+                                         const NraTask* tasks, const int32_t* count, NraSeqArgs seq,
+                                         int32_t* out_score, int32_t* out_p,
                                          int32_t* out_tend, void* chain_buf, int chain_cap, int wide)
 {
     if (n_waves <= 0) return 0;
-    return launch_payload<1>(R, has_n, wide, st, n_waves, tasks, count, reads, regions, pool, q2bit, qnmask, sp, out_score, out_p, out_tend, chain_buf, chain_cap);
+    return launch_payload<1>(R, has_n, wide, st, n_waves, tasks, count, seq, out_score, out_p, out_tend, chain_buf, chain_cap);
 }
 #endif
 #endif  // parts 2, 3

@@ -45,6 +45,10 @@
 #endif
 #define NRA_HAS_PART(n) (NRA_PART == 0 || NRA_PART == (n))
 
+// The fields of a launcher's NraSweepArgs in the order the kernels below take them (the kernels keep parameters of their
+// own: NRA_SEQ_FIELDS, nra_device.h).
+#define SWEEP_FIELDS(a) NRA_SEQ_FIELDS((a).seq), (a).kmin, (a).kmax, (a).coff, (a).snap, (a).read_a, (a).cand_score, (a).cand_flag
+
 #define FLAG_BOUNDARY 0x00000080      // bit 7 of table byte 0
 #define FLAG_SNAPSHOT 0x00008000      // bit 7 of table byte 1 (reverse sweep)
 #define FLAG_INREP    0x80008000      // bits 7 of table bytes 1 and 3 (forward sweep, origin bit): column >= |L|
@@ -1569,15 +1573,12 @@ __global__ __launch_bounds__(WAVE, 3) void k_sweep_ringmt(int n_blocks, const Nr
 // launchers
 // ------------------------------------------------------------------------------------
 template <int DIR>
-static int launch_sweep(int R, int has_n, int chain, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
-                        const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                        const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                        const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                        int32_t* snap, int32_t* read_a,
-                        int32_t* cand_score, uint8_t* cand_flag, int32_t* chain_buf, int chain_cap, int n_strips)
+static int launch_sweep(int R, int has_n, int chain, hipStream_t st, int n_tasks, const NraSweepTask* tasks, NraSweepArgs a,
+                        int32_t* chain_buf, int chain_cap, int n_strips)
 {
     if (n_tasks <= 0) return 0;
-#define ARGS n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag, chain_buf, chain_cap
+    if (DIR == 0) { a.cand_score = nullptr; a.cand_flag = nullptr; }      // a reverse sweep has no candidate outputs
+#define ARGS n_tasks, tasks, SWEEP_FIELDS(a), chain_buf, chain_cap
     if (chain) {      // row-block chaining: only the instantiations long reads (and the tests) use
         if (n_strips <= 0) return (int)hipErrorInvalidValue;
         const int n_waves = n_tasks < n_strips ? n_tasks : n_strips;
@@ -1606,15 +1607,13 @@ static int launch_sweep(int R, int has_n, int chain, hipStream_t st, int n_tasks
 
 // the LDS-ring sweeps; HALF: the half-wave kernels, two read pairs per wave (R <= NRA_RING32_MAX_R)
 template <int DIR, bool HALF>
-int launch_sweep_ring(int R, int has_n, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
-                      const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                      const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                      const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                      int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo)
+int launch_sweep_ring(int R, int has_n, hipStream_t st, int n_tasks, const NraSweepTask* tasks, NraSweepArgs a, int relax_c,
+                      int32_t* redo)
 {
     if (n_tasks <= 0) return 0;
+    if (DIR == 0) { a.cand_score = nullptr; a.cand_flag = nullptr; }
     const int grid = HALF ? n_tasks : (n_tasks + SWEEP_RING_WPB - 1) / SWEEP_RING_WPB;
-#define ARGS n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag, relax_c, redo
+#define ARGS n_tasks, tasks, SWEEP_FIELDS(a), relax_c, redo
 #define LAUNCH(r, n, t)                                                                         \
     {                                                                                           \
         if constexpr (HALF) k_sweep_ring32<r, n, DIR, t><<<grid, WAVE, 0, st>>>(ARGS);         \
@@ -1638,15 +1637,11 @@ int launch_sweep_ring(int R, int has_n, hipStream_t st, int n_tasks, const NraSw
 
 template <bool HALF>
 int launch_sweep_ringq(int R, int has_n, hipStream_t st, int n_quanta, const uint32_t* qlist, int qsteps, int n_tasks, int32_t* ticket,
-                       int32_t* arrivals, int32_t* giveup, int32_t* qstate, const NraSweepTask* tasks,
-                       const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                       const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                       const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                       int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo,
-                       int sat_steps, int32_t* sat_count)
+                       int32_t* arrivals, int32_t* giveup, int32_t* qstate, const NraSweepTask* tasks, NraSweepArgs a,
+                       int relax_c, int32_t* redo, int sat_steps, int32_t* sat_count)
 {
     if (n_quanta <= 0) return 0;
-#define ARGS n_quanta, qlist, qsteps, n_tasks, ticket, arrivals, giveup, qstate, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag, relax_c, redo, sat_steps, sat_count
+#define ARGS n_quanta, qlist, qsteps, n_tasks, ticket, arrivals, giveup, qstate, tasks, SWEEP_FIELDS(a), relax_c, redo, sat_steps, sat_count
 #define CASE(r)                                                                                                          \
     case r:                                                                                                              \
         if constexpr (HALF && r > NRA_RING32_MAX_R) return (int)hipErrorInvalidValue;                                   \
@@ -1686,56 +1681,37 @@ extern template NRA_SPEC(launch_sweep_ringq<true>);
 
 #if NRA_HAS_PART(11)
 extern "C" int nra_launch_sweep_ring_bwd(int R, int has_n, int half, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
-                                         const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                         const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                         const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                         int32_t* snap, int32_t* read_a, int relax_c, int32_t* redo)
+                                         NraSweepArgs a, int relax_c, int32_t* redo)
 {
-    return (half ? launch_sweep_ring<0, true> : launch_sweep_ring<0, false>)(R, has_n, st, n_tasks, tasks, reads, regions, pool, q2bit,
-                                                                              qnmask, sp, kmin, kmax, coff, snap, read_a, nullptr,
-                                                                              nullptr, relax_c, redo);
+    return (half ? launch_sweep_ring<0, true> : launch_sweep_ring<0, false>)(R, has_n, st, n_tasks, tasks, a, relax_c, redo);
 }
 #endif
 #if NRA_HAS_PART(12)
 extern "C" int nra_launch_sweep_ring_fwd(int R, int has_n, int half, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
-                                         const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                         const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                         const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                         int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag,
-                                         int relax_c, int32_t* redo)
+                                         NraSweepArgs a, int relax_c, int32_t* redo)
 {
-    return (half ? launch_sweep_ring<1, true> : launch_sweep_ring<1, false>)(R, has_n, st, n_tasks, tasks, reads, regions, pool, q2bit,
-                                                                              qnmask, sp, kmin, kmax, coff, snap, read_a, cand_score,
-                                                                              cand_flag, relax_c, redo);
+    return (half ? launch_sweep_ring<1, true> : launch_sweep_ring<1, false>)(R, has_n, st, n_tasks, tasks, a, relax_c, redo);
 }
 #endif
 #if NRA_HAS_PART(25)
 extern "C" int nra_launch_sweep_ringq(int R, int has_n, int half, hipStream_t st, int n_quanta, const uint32_t* qlist, int qsteps,
                                       int n_tasks, int32_t* ticket, int32_t* arrivals, int32_t* giveup, int32_t* qstate,
-                                      const NraSweepTask* tasks, const NraDevRead* reads, const NraDevRegion* regions,
-                                      const uint8_t* pool, const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                      const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                      int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int relax_c, int32_t* redo,
-                                      int sat_steps, int32_t* sat_count)
+                                      const NraSweepTask* tasks, NraSweepArgs a, int relax_c, int32_t* redo, int sat_steps,
+                                      int32_t* sat_count)
 {
     return (half ? launch_sweep_ringq<true> : launch_sweep_ringq<false>)(R, has_n, st, n_quanta, qlist, qsteps, n_tasks, ticket, arrivals,
-                                                                          giveup, qstate, tasks, reads, regions, pool, q2bit, qnmask,
-                                                                          sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag,
-                                                                          relax_c, redo, sat_steps, sat_count);
+                                                                          giveup, qstate, tasks, a, relax_c, redo, sat_steps, sat_count);
 }
 #endif
 
 template <int DIR>
 static int launch_sweep_ringchain(int R, int has_n, int wide, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
-                                  const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                  const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                  const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                  int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag,
-                                  int32_t* chain_buf, int chain_cap, int n_strips)
+                                  NraSweepArgs a, int32_t* chain_buf, int chain_cap, int n_strips)
 {
     if (n_tasks <= 0) return 0;
+    if (DIR == 0) { a.cand_score = nullptr; a.cand_flag = nullptr; }
     const int grid = n_tasks < n_strips ? n_tasks : n_strips;
-#define ARGS n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag, chain_buf, chain_cap
+#define ARGS n_tasks, tasks, SWEEP_FIELDS(a), chain_buf, chain_cap
 #define LAUNCH(r)                                                                                        \
     do {                                                                                                 \
         if (wide) { if (has_n) k_sweep_ringchain<r, true, DIR, true><<<grid, WAVE, 0, st>>>(ARGS);      \
@@ -1753,44 +1729,32 @@ static int launch_sweep_ringchain(int R, int has_n, int wide, hipStream_t st, in
 
 #if NRA_HAS_PART(13)
 extern "C" int nra_launch_sweep_ringchain_bwd(int R, int has_n, int wide, hipStream_t st, int n_tasks,
-                                              const NraSweepTask* tasks, const NraDevRead* reads,
-                                              const NraDevRegion* regions, const uint8_t* pool,
-                                              const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                              const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                              int32_t* snap, int32_t* read_a, int32_t* chain_buf, int chain_cap,
+                                              const NraSweepTask* tasks, NraSweepArgs a, int32_t* chain_buf, int chain_cap,
                                               int n_strips)
 {
-    return launch_sweep_ringchain<0>(R, has_n, wide, st, n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin,
-                                     kmax, coff, snap, read_a, nullptr, nullptr, chain_buf, chain_cap, n_strips);
+    return launch_sweep_ringchain<0>(R, has_n, wide, st, n_tasks, tasks, a, chain_buf, chain_cap, n_strips);
 }
 #endif
 #if NRA_HAS_PART(14)
 extern "C" int nra_launch_sweep_ringchain_fwd(int R, int has_n, int wide, hipStream_t st, int n_tasks,
-                                              const NraSweepTask* tasks, const NraDevRead* reads,
-                                              const NraDevRegion* regions, const uint8_t* pool,
-                                              const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                              const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                              int32_t* snap, int32_t* read_a, int32_t* cand_score,
-                                              uint8_t* cand_flag, int32_t* chain_buf, int chain_cap, int n_strips)
+                                              const NraSweepTask* tasks, NraSweepArgs a, int32_t* chain_buf, int chain_cap,
+                                              int n_strips)
 {
-    return launch_sweep_ringchain<1>(R, has_n, wide, st, n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin,
-                                     kmax, coff, snap, read_a, cand_score, cand_flag, chain_buf, chain_cap, n_strips);
+    return launch_sweep_ringchain<1>(R, has_n, wide, st, n_tasks, tasks, a, chain_buf, chain_cap, n_strips);
 }
 #endif
 
 template <int DIR>
 static int launch_sweep_ringmt(int R, int has_n, int wide, hipStream_t st, int n_blocks, const NraChainBlock* blocks,
-                               int32_t* ticket, const NraSweepTask* tasks, const NraDevRead* reads,
-                               const NraDevRegion* regions, const uint8_t* pool, const uint32_t* q2bit,
-                               const uint32_t* qnmask, NraScoreParams sp, const int32_t* kmin, const int32_t* kmax,
-                               const uint32_t* coff, int32_t* snap, int32_t* read_a, int32_t* cand_score,
-                               uint8_t* cand_flag, uint64_t* strips, int chain_cap, uint32_t epoch, int32_t* error)
+                               int32_t* ticket, const NraSweepTask* tasks, NraSweepArgs a, uint64_t* strips, int chain_cap,
+                               uint32_t epoch, int32_t* error)
 {
     if (n_blocks <= 0) return 0;
     if (epoch == 0) return (int)hipErrorInvalidValue;
+    if (DIR == 0) { a.cand_score = nullptr; a.cand_flag = nullptr; }
     hipError_t e = hipMemsetAsync(ticket, 0, sizeof(int32_t), st);
     if (e != hipSuccess) return (int)e;
-#define ARGS n_blocks, blocks, ticket, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag, (nra_u64*)strips, chain_cap, epoch, error
+#define ARGS n_blocks, blocks, ticket, tasks, SWEEP_FIELDS(a), (nra_u64*)strips, chain_cap, epoch, error
 #define LAUNCH(r)                                                                                        \
     do {                                                                                                 \
         if (wide) { if (has_n) k_sweep_ringmt<r, true, DIR, true><<<n_blocks, WAVE, 0, st>>>(ARGS);      \
@@ -1815,52 +1779,31 @@ static int launch_sweep_ringmt(int R, int has_n, int wide, hipStream_t st, int n
 #if NRA_HAS_PART(18)
 extern "C" int nra_launch_sweep_ringmt_bwd(int R, int has_n, int wide, hipStream_t st, int n_blocks,
                                            const NraChainBlock* blocks, int32_t* ticket, const NraSweepTask* tasks,
-                                           const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                           const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                           const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                           int32_t* snap, int32_t* read_a, uint64_t* strips, int chain_cap,
-                                           uint32_t epoch, int32_t* error)
+                                           NraSweepArgs a, uint64_t* strips, int chain_cap, uint32_t epoch, int32_t* error)
 {
-    return launch_sweep_ringmt<0>(R, has_n, wide, st, n_blocks, blocks, ticket, tasks, reads, regions, pool, q2bit, qnmask,
-                                  sp, kmin, kmax, coff, snap, read_a, nullptr, nullptr, strips, chain_cap, epoch, error);
+    return launch_sweep_ringmt<0>(R, has_n, wide, st, n_blocks, blocks, ticket, tasks, a, strips, chain_cap, epoch, error);
 }
 #endif
 #if NRA_HAS_PART(19)
 extern "C" int nra_launch_sweep_ringmt_fwd(int R, int has_n, int wide, hipStream_t st, int n_blocks,
                                            const NraChainBlock* blocks, int32_t* ticket, const NraSweepTask* tasks,
-                                           const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                           const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                           const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                           int32_t* snap, int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag,
-                                           uint64_t* strips, int chain_cap, uint32_t epoch, int32_t* error)
+                                           NraSweepArgs a, uint64_t* strips, int chain_cap, uint32_t epoch, int32_t* error)
 {
-    return launch_sweep_ringmt<1>(R, has_n, wide, st, n_blocks, blocks, ticket, tasks, reads, regions, pool, q2bit, qnmask,
-                                  sp, kmin, kmax, coff, snap, read_a, cand_score, cand_flag, strips, chain_cap, epoch, error);
+    return launch_sweep_ringmt<1>(R, has_n, wide, st, n_blocks, blocks, ticket, tasks, a, strips, chain_cap, epoch, error);
 }
 #endif
 
 #if NRA_HAS_PART(5)
 extern "C" int nra_launch_sweep_bwd(int R, int has_n, int chain, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
-                                    const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                    const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                    const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                    int32_t* snap,
-                                    int32_t* read_a, int32_t* chain_buf, int chain_cap, int n_strips)
+                                    NraSweepArgs a, int32_t* chain_buf, int chain_cap, int n_strips)
 {
-    return launch_sweep<0>(R, has_n, chain, st, n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax,
-                           coff, snap, read_a, nullptr, nullptr, chain_buf, chain_cap, n_strips);
+    return launch_sweep<0>(R, has_n, chain, st, n_tasks, tasks, a, chain_buf, chain_cap, n_strips);
 }
 #endif
 #if NRA_HAS_PART(6)
 extern "C" int nra_launch_sweep_fwd(int R, int has_n, int chain, hipStream_t st, int n_tasks, const NraSweepTask* tasks,
-                                    const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                    const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                    const int32_t* kmin, const int32_t* kmax, const uint32_t* coff,
-                                    int32_t* snap,
-                                    int32_t* read_a, int32_t* cand_score, uint8_t* cand_flag, int32_t* chain_buf,
-                                    int chain_cap, int n_strips)
+                                    NraSweepArgs a, int32_t* chain_buf, int chain_cap, int n_strips)
 {
-    return launch_sweep<1>(R, has_n, chain, st, n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, kmin, kmax,
-                           coff, snap, read_a, cand_score, cand_flag, chain_buf, chain_cap, n_strips);
+    return launch_sweep<1>(R, has_n, chain, st, n_tasks, tasks, a, chain_buf, chain_cap, n_strips);
 }
 #endif

@@ -32,15 +32,11 @@
 #define T_EQ 0x80         // the two bases are equal ('=' rather than 'X')
 
 template <int R, bool HAS_N>
-__global__ __launch_bounds__(WAVE) void k_trace_fill(int n_tasks, const NraTraceTask* __restrict__ tasks,
-                                                     const NraDevRead* __restrict__ reads,
-                                                     const NraDevRegion* __restrict__ regions,
-                                                     const uint8_t* __restrict__ pool,
-                                                     const uint32_t* __restrict__ q2bit,
-                                                     const uint32_t* __restrict__ qnmask,
-                                                     NraScoreParams sp, uint8_t* __restrict__ trace,
+__global__ __launch_bounds__(WAVE) void k_trace_fill(int n_tasks, const NraTraceTask* __restrict__ tasks, NraSeqArgs seq,
+                                                     uint8_t* __restrict__ trace,
                                                      int32_t* __restrict__ out)   // 5 per task: score, tstart, tend, best_i, best_j
 {
+    NRA_SEQ_LOCALS(seq)
     const int task = blockIdx.x;
     if (task >= n_tasks) return;
     const int lane = threadIdx.x;
@@ -411,15 +407,13 @@ __global__ void k_trace_best(int n_tasks, const NraTraceTask* __restrict__ tasks
 
 #if NRA_HAS_PART(9)
 extern "C" int nra_launch_trace_fill(int R, int has_n, hipStream_t st, int n_tasks, const NraTraceTask* tasks,
-                                     const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                     const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                     uint8_t* trace, int32_t* out)
+                                     NraSeqArgs seq, uint8_t* trace, int32_t* out)
 {
     if (n_tasks <= 0) return 0;
 #define CASE(r)                                                                                     \
     case r:                                                                                         \
-        if (has_n) k_trace_fill<r, true><<<n_tasks, WAVE, 0, st>>>(n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, trace, out); \
-        else k_trace_fill<r, false><<<n_tasks, WAVE, 0, st>>>(n_tasks, tasks, reads, regions, pool, q2bit, qnmask, sp, trace, out);       \
+        if (has_n) k_trace_fill<r, true><<<n_tasks, WAVE, 0, st>>>(n_tasks, tasks, seq, trace, out); \
+        else k_trace_fill<r, false><<<n_tasks, WAVE, 0, st>>>(n_tasks, tasks, seq, trace, out);      \
         break;
     switch (R) {
         NRA_R_LIST(CASE)
@@ -441,15 +435,13 @@ extern "C" int nra_launch_trace_back(hipStream_t st, int n_tasks, const NraTrace
 // the strips and the error word belong to the call; `ticket` is zeroed here, ahead of the launch
 extern "C" int nra_launch_trace_fill_mt(int R, int has_n, int wide, hipStream_t st, int n_blocks,
                                         const NraTraceBlock* blocks, int32_t* ticket, const NraTraceTask* tasks,
-                                        const NraDevRead* reads, const NraDevRegion* regions, const uint8_t* pool,
-                                        const uint32_t* q2bit, const uint32_t* qnmask, NraScoreParams sp,
-                                        uint8_t* trace, int32_t* blk_best, uint64_t* strips, uint32_t epoch,
-                                        int32_t* error)
+                                        NraSeqArgs seq, uint8_t* trace, int32_t* blk_best, uint64_t* strips,
+                                        uint32_t epoch, int32_t* error)
 {
     if (n_blocks <= 0) return 0;
     hipError_t e = hipMemsetAsync(ticket, 0, sizeof(int32_t), st);
     if (e != hipSuccess) return (int)e;
-#define ARGS n_blocks, blocks, ticket, tasks, reads, regions, pool, q2bit, qnmask, sp, trace, blk_best, (nra_tu64*)strips, epoch, error
+#define ARGS n_blocks, blocks, ticket, tasks, NRA_SEQ_FIELDS(seq), trace, blk_best, (nra_tu64*)strips, epoch, error
 #define CASE(r)                                                                                      \
     case r:                                                                                          \
         if (wide) { if (has_n) k_trace_fill_mt<r, true, true><<<n_blocks, WAVE, 0, st>>>(ARGS);      \
