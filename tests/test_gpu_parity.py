@@ -405,23 +405,40 @@ def test_long_cores_chained_int32_sweeps_equal_oracle(capi, oracle):
     assert (g["status"] == 0).all() and g["best_score"][2] > 32767
 
 
-def test_large_row_counts_park_the_junction_in_agprs(capi, oracle):
-    """Reads of 1.7-3.0 kb take 28-48 rows per lane in the packed sweeps: the forward sweep then keeps the R
-    side of the junction in accumulation registers.  Two reads per bucket (pairs) plus a single, N bases."""
-    rng = np.random.default_rng(91)
-    L, R = synth.rand_seq(rng, 400), synth.rand_seq(rng, 400)
-    reads, kmin, kmax = [], [], []
-    for k_true in (300, 310, 350, 360, 440, 450, 520, 530, 560):          # cores of 1.7 ... 3.0 kb
-        s = synth.apply_errors(rng, L[-100:] + "TATTG" * k_true + R[:100], "hifi")
-        if k_true == 440:
-            s = s[:700] + "NN" + s[702:]
-        reads.append(s[:3072]); kmin.append(k_true - 6); kmax.append(k_true + 6)
+def test_large_row_counts_park_the_junction_in_agprs(capi, oracle, monkeypatch):
+    """Reads of 1.7-3.0 kb take 28-48 rows per lane in the packed one-block sweeps: the forward sweep of the LDS-ring
+    kernels then keeps the R side of the junction in accumulation registers.  Two reads per bucket (pairs) plus a
+    single, N bases.
+
+    Since the fitted row-block model, so few reads of this length plan as ONE chained bucket of row blocks
+    (k_sweep_ringmt, 12 rows per lane) under flags 0 and NRA_F_TIE_EXTENTS, and NRA_F_DPP_SWEEP runs k_sweep_pk16, which
+    parks nothing: the first three legs are the row-block and DPP check they have become.  The legs under
+    NRA_CHAIN_FROM = 3072 (the variable's presence switches the model off) run what the test is named for; the plan of
+    the same inputs and environment says so (ring buckets of 28, 32, 40 and 48 rows per lane, no chain)."""
+    import sweep_class_cases as S
+    d = S.agpr_test_inputs()
+    regions, reads, kmin, kmax = d["regions"], d["reads"], d["kmin"], d["kmax"]
     assert max(len(r) for r in reads) > 2900
-    o = oracle.round3_1d([(L, "TATTG", R)], reads, kmin, kmax)
+    o = oracle.round3_1d(regions, reads, kmin, kmax)
+    monkeypatch.delenv("NRA_CHAIN_FROM", raising=False)
     for flags in (0, capi.F_TIE_EXTENTS, capi.F_DPP_SWEEP):
-        g = capi.round3_1d([(L, "TATTG", R)], reads, kmin, kmax, flags=flags)
+        g = capi.round3_1d(regions, reads, kmin, kmax, flags=flags)
         for k in ("best_score", "sum_k", "n_ties", "status", "cand_score"):
             assert np.array_equal(g[k], o[k]), (flags, k, g[k][:8], o[k][:8])
+    monkeypatch.setenv("NRA_CHAIN_FROM", "3072")
+    ties = o["cand_tstart"] >= 0
+    for flags in (0, capi.F_TIE_EXTENTS, capi.F_NO_QUANTA):
+        _, buckets = S.plan_1d(d, flags)
+        assert [b["R"] for b in buckets] == [48, 40, 32, 28], (flags, buckets)
+        assert all(b["ring"] and not b["chain"] and not b["mt"] and not b["half"] for b in buckets), (flags, buckets)
+        assert all(b["quanta"] == (flags != capi.F_NO_QUANTA) for b in buckets), (flags, buckets)
+        g = capi.round3_1d(regions, reads, kmin, kmax, flags=flags)
+        for k in ("best_score", "sum_k", "n_ties", "status", "cand_score"):
+            assert np.array_equal(g[k], o[k]), ("NRA_CHAIN_FROM", flags, k, g[k][:8], o[k][:8])
+        if flags & capi.F_TIE_EXTENTS:
+            assert np.array_equal(g["cand_tstart"][ties], o["cand_tstart"][ties])
+            assert np.array_equal(g["cand_tend"][ties], o["cand_tend"][ties])
+    monkeypatch.delenv("NRA_CHAIN_FROM")
 
 
 def test_joint_resident_reads_across_cell_lists(capi, oracle):
