@@ -1046,6 +1046,84 @@ int nra_sketch_pairs(int device, int32_t n_seqs, const char* seqs, const int64_t
                      int32_t k, int32_t min_shared, int64_t* n_pairs, int32_t* pair_a, int32_t* pair_b,
                      int32_t* pair_shared, int32_t* sketch_size, nra_sketch_stats_t* stats);
 
+/* ---- Placement: where short query sequences (the flanks of discovered loci) lie on a target that is streamed past
+ * them (seed and vote; no counterpart in the reference)
+ *
+ * All of it is integer arithmetic; the result depends on neither the order of the queries, nor the order or the cut of
+ * the chunks, nor the other queries except through max_occ.
+ *
+ * Windows, valid windows, code, canon and periodic windows (periods 1..6) are the anchor screen's.  k is odd, 11..15, so
+ * no window is its own reverse complement; a valid window w is forward when code(w) == canon(w).
+ *
+ * Postings.  Every valid window of query q at position j that is not periodic is a posting (q, j, f), f its forward
+ * bit, under the key canon(w).  A key with more than max_occ postings over all queries (a k-mer twice in one query
+ * counts twice) has none: it is not in the index.
+ *
+ * Target windows.  nra_place_scan gives bases [pos0, pos0 + n) of contig `contig`, a label >= 0 of the caller's
+ * choice.  Every window that lies wholly inside the chunk is a target window (t, i, g): contig t, contig position i of
+ * its first base, forward bit g.  The caller overlaps successive chunks of a contig by k - 1 bases so that every window
+ * of the contig is given exactly once; A WINDOW GIVEN TWICE COUNTS TWICE.  occ(c) is the number of valid target windows
+ * with canon c over all scans of the handle.
+ *
+ * Hits.  A target window (t, i, g) and a posting (q, j, f) of its canon make a hit on strand s = 0 when f == g, else 1,
+ * with the start diagonal d = i - j for s = 0 and d = i + j + k - len(q) for s = 1: the contig position on which base 0
+ * of the query (of its reverse complement for s = 1) falls; it may be negative.  A hit counts when
+ * occ(canon) <= max_target_occ.
+ *
+ * Votes.  v(q, t, s, b) = the counting hits with floor(d / bin) in {b, b + 1}, floor towards minus infinity: the bins
+ * overlap, so that a diagonal drifting over a bin edge is not split.  The result is every (q, t, s, b) with
+ * v >= min_votes, ordered by (q, t, s, b).
+ *
+ * The handle keeps the target windows of every index key until the key has more than NRA_PLACE_OCC_CEILING of them;
+ * max_target_occ above that ceiling is NRA_E_RANGE.  DESIGN.md section 31. */
+#define NRA_PLACE_MAX_QUERY    2048      /* bases of a query */
+#define NRA_PLACE_MAX_QUERIES  1048576
+#define NRA_PLACE_MAX_POS      (1 << 30) /* pos0 + n of a chunk */
+#define NRA_PLACE_OCC_CEILING  1024      /* the largest max_target_occ of nra_place_candidates */
+#define NRA_PLACE_MAX_HITS     (1 << 26) /* target windows a handle keeps */
+
+typedef struct nra_place nra_place_t;
+
+typedef struct nra_place_stats {
+    int64_t n_keys;            /* distinct canonical k-mers in the index */
+    int64_t n_postings;        /* their postings */
+    int64_t n_masked_periodic; /* distinct periodic k-mers of the queries, left out */
+    int64_t n_masked_max_occ;  /* distinct k-mers with more than max_occ postings, left out */
+    int64_t index_bytes;       /* device bytes of the table and the occurrence counters */
+    int64_t target_bases;      /* the sum of n over the scans (the k - 1 overlaps counted each time) */
+    int64_t n_target_windows;  /* valid target windows */
+    int64_t n_hits_kept;       /* hits of the keys with occ <= NRA_PLACE_OCC_CEILING */
+    int64_t n_keys_over;       /* keys with occ > max_target_occ of the last nra_place_candidates (0 before one) */
+    int64_t n_chunks;          /* nra_place_scan calls that succeeded */
+    int64_t tile_windows;      /* target windows per workgroup of k_place_hits */
+    double  build_ms;          /* host time of the index build in nra_place_create */
+    double  kernel_ms;         /* k_place_hits, summed over the scans (HIP events) */
+    double  upload_ms;         /* host: the copies of the chunks to the device, summed (wall clock) */
+    double  reduce_ms;         /* host: the last nra_place_candidates (wall clock) */
+} nra_place_stats_t;
+
+/* query q = bytes [seq_off[q], seq_off[q+1]) of `seqs`.  k even or outside 11..15, max_occ outside 1..255, a negative
+ * count, offsets that decrease or a NULL array that is needed are NRA_E_ARG; more than 1 048 576 queries, a query of
+ * more than 2048 bases or more than 2^26 postings are NRA_E_RANGE; all before the device is touched.  Empty queries,
+ * queries shorter than k and n_queries = 0 are fine.  Builds the index on the host and keeps its table on the device. */
+int nra_place_create(int device, int32_t n_queries, const char* seqs, const int64_t* seq_off, int32_t k,
+                     int32_t max_occ, nra_place_t** out);
+/* One chunk of one contig (above).  A negative contig, pos0 or n, or NULL bases with n > 0, are NRA_E_ARG;
+ * pos0 + n > 2^30 is NRA_E_RANGE; both leave the handle as it was.  n = 0 and chunks shorter than k are fine.  When the
+ * handle would keep more than NRA_PLACE_MAX_HITS target windows the call returns NRA_E_RANGE (lower max_occ: fewer
+ * repeated k-mers stay in the index) and every later scan or candidates call on the handle returns NRA_E_STATE. */
+int nra_place_scan(nra_place_t* h, int32_t contig, int64_t pos0, const char* bases, int64_t n);
+/* The candidates of everything scanned so far.  bin in 1..4096, max_target_occ in 1..65535 (else NRA_E_ARG) and at most
+ * NRA_PLACE_OCC_CEILING (else NRA_E_RANGE), min_votes >= 1.  On entry *n_cand is the capacity of the five arrays, on
+ * return the number of candidates; with too small a capacity nothing is written, *n_cand is the number needed and the
+ * call returns NRA_E_RANGE.  It changes nothing but the stats: it may be called again with other values, and more
+ * chunks may be scanned after it. */
+int nra_place_candidates(nra_place_t* h, int32_t bin, int32_t max_target_occ, int32_t min_votes, int64_t* n_cand,
+                         int32_t* cand_query, int32_t* cand_contig, int32_t* cand_strand, int32_t* cand_bin,
+                         int32_t* cand_votes);
+int nra_place_stats(nra_place_t* h, nra_place_stats_t* st);
+int nra_place_destroy(nra_place_t* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,7 +41,8 @@ EXPORTS = ("nra_abi_version", "nra_version", "nra_last_error", "nra_device_count
            "nra_read_structure", "nra_tract_motifs", "nra_extend_tracts", "nra_mixture_fit", "nra_mixture_bootstrap",
            "nra_tract_consensus", "nra_allele_split", "nra_flank_phase", "nra_tract_segments", "nra_tract_periods",
            "nra_censored_fit", "nra_censored_posteriors", "nra_censored_bootstrap", "nra_read_methylation",
-           "nra_scan_repeats", "nra_sketch_pairs")
+           "nra_scan_repeats", "nra_sketch_pairs",
+           "nra_place_create", "nra_place_scan", "nra_place_candidates", "nra_place_stats", "nra_place_destroy")
 
 
 E_RANGE = -3      # NRA_E_RANGE
@@ -118,6 +119,16 @@ class ScanStats(C.Structure):
 class SketchStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_windows", "n_kmers", "n_compared", "n_tiles")] + \
                [(n, C.c_double) for n in ("kernel_ms", "sketch_ms", "pairs_ms", "upload_ms", "sort_ms")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class PlaceStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_keys", "n_postings", "n_masked_periodic", "n_masked_max_occ", "index_bytes",
+                                         "target_bases", "n_target_windows", "n_hits_kept", "n_keys_over", "n_chunks",
+                                         "tile_windows")] + \
+               [(n, C.c_double) for n in ("build_ms", "kernel_ms", "upload_ms", "reduce_ms")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -268,6 +279,16 @@ def load():
     lib.nra_sketch_pairs.restype = C.c_int
     lib.nra_sketch_pairs.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, pi32, C.c_int32, C.c_int32, pi64, pi32, pi32,
                                      pi32, pi32, C.POINTER(SketchStats)]
+    lib.nra_place_create.restype = C.c_int
+    lib.nra_place_create.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, C.c_int32, C.c_int32, C.POINTER(vp)]
+    lib.nra_place_scan.restype = C.c_int
+    lib.nra_place_scan.argtypes = [vp, C.c_int32, C.c_int64, C.c_char_p, C.c_int64]
+    lib.nra_place_candidates.restype = C.c_int
+    lib.nra_place_candidates.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, pi64, pi32, pi32, pi32, pi32, pi32]
+    lib.nra_place_stats.restype = C.c_int
+    lib.nra_place_stats.argtypes = [vp, C.POINTER(PlaceStats)]
+    lib.nra_place_destroy.restype = C.c_int
+    lib.nra_place_destroy.argtypes = [vp]
     lib.nra_tract_periods.restype = C.c_int
     lib.nra_tract_periods.argtypes = [C.c_int, C.c_int32, C.c_char_p, pi64, C.c_int32, pi32, pi32]
     _LIB = lib
@@ -977,6 +998,58 @@ def sketch_pairs(seqs, groups, k=13, min_shared=1, device=0, capacity=None):
         out["sketch_size"] = size
         out["stats"] = st.as_dict()
         return out
+
+
+PLACE_KEYS = ("query", "contig", "strand", "bin", "votes")
+PLACE_MAX_QUERY = 2048        # NRA_PLACE_MAX_QUERY
+PLACE_MAX_QUERIES = 1 << 20   # NRA_PLACE_MAX_QUERIES
+PLACE_MAX_POS = 1 << 30       # NRA_PLACE_MAX_POS
+PLACE_OCC_CEILING = 1024      # NRA_PLACE_OCC_CEILING
+
+
+def place_create(queries, k=15, max_occ=16, device=0):
+    """nra_place_create: the index of the queries -> an opaque handle (place_destroy frees it)."""
+    data, off = pack_reads(list(queries))
+    h = C.c_void_p()
+    _check(load().nra_place_create(device, len(off) - 1, data, _ptr(off, C.c_int64), k, max_occ, C.byref(h)))
+    return h
+
+
+def place_scan(handle, contig, pos0, bases):
+    """nra_place_scan: bases [pos0, pos0 + len(bases)) of contig `contig` (a label >= 0).  Successive chunks of a contig
+    overlap by k - 1 bases; a window given twice counts twice."""
+    data = bases.encode() if isinstance(bases, str) else bytes(bases)
+    _check(load().nra_place_scan(handle, contig, pos0, data, len(data)))
+
+
+def place_candidates(handle, bin=64, max_target_occ=64, min_votes=8, capacity=None):
+    """nra_place_candidates -> dict(query, contig, strand, bin, votes: int32 per candidate, ordered by (query, contig,
+    strand, bin)).  When the candidates exceed `capacity`, the call is repeated once with the capacity the library
+    asked for."""
+    lib = load()
+    if capacity is None:
+        capacity = 4096
+    while True:
+        out = {key: np.zeros(capacity, np.int32) for key in PLACE_KEYS}
+        n_cand = C.c_int64(capacity)
+        rc = lib.nra_place_candidates(handle, bin, max_target_occ, min_votes, C.byref(n_cand),
+                                      *(_ptr(out[key], C.c_int32) for key in PLACE_KEYS))
+        if rc == E_RANGE and n_cand.value > capacity:
+            capacity = int(n_cand.value)
+            continue
+        _check(rc)
+        return {key: v[:n_cand.value] for key, v in out.items()}
+
+
+def place_stats(handle):
+    st = PlaceStats()
+    _check(load().nra_place_stats(handle, C.byref(st)))
+    return st.as_dict()
+
+
+def place_destroy(handle):
+    if handle:
+        _check(load().nra_place_destroy(handle))
 
 
 def extend_tracts(motifs, tracts, read_motif, match=2, mismatch=4, gap=6, device=0):

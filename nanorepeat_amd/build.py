@@ -1,7 +1,7 @@
 """Build nanorepeat_amd/libnanorepeat_amd.so (HIP kernels + C ABI) in-tree for gfx950.
 
 hipcc cross-compiles without a GPU.  The kernel file is split into parts
-(-DNRA_PART=1..42) that compile in parallel; the shared library carries only gfx950 code.
+(-DNRA_PART=1..43) that compile in parallel; the shared library carries only gfx950 code.
 """
 import os
 import subprocess
@@ -34,11 +34,12 @@ KERNELS = (("nra_kernels.hip", (1, 2, 3, 4)),
            ("nra_censored.hip", (39,)),
            ("nra_methyl.hip", (40,)),
            ("nra_scan.hip", (41,)),
-           ("nra_sketch.hip", (42,)))
+           ("nra_sketch.hip", (42,)),
+           ("nra_place.hip", (43,)))
 HOSTS = ("nra_host.cpp", "nra_plan1d.cpp", "nra_plan2d.cpp", "nra_screen_host.cpp", "nra_structure_host.cpp", "nra_motif_host.cpp", "nra_extend_host.cpp",
          "nra_mixture_host.cpp", "nra_consensus_host.cpp", "nra_split_host.cpp", "nra_segment_host.cpp",
          "nra_period_host.cpp", "nra_bootstrap_host.cpp", "nra_flank_host.cpp", "nra_censored_host.cpp", "nra_methyl_host.cpp",
-         "nra_scan_host.cpp", "nra_sketch_host.cpp")
+         "nra_scan_host.cpp", "nra_sketch_host.cpp", "nra_place_host.cpp")
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))
 SOURCES = [k for k, _ in KERNELS] + list(HOSTS) + HEADERS
 ARCH = "gfx950"

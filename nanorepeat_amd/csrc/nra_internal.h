@@ -284,6 +284,19 @@ struct NraSketchPair {
     int32_t a, b, shared, pad;
 };
 
+// Placement (nra_place.hip, nra_place_host.cpp).  The index is the screen's table (key, number
+// of postings, first posting; the postings stay on the host) with one 32-bit occurrence counter per slot.  A record is
+// one target window whose canonical k-mer is a key: the slot, the contig and position << 1 | forward bit.
+#define NRA_PLACE_TILE 4096                   // target windows per workgroup
+#define NRA_PLACE_THREADS 256
+#define NRA_PLACE_LAUNCH_WINDOWS (1 << 23)    // target windows per launch: the record list holds one record per window
+
+struct NraPlaceRecord {
+    uint32_t slot;
+    int32_t contig;
+    uint32_t pos_fwd;
+};
+
 // Repeat structure (nra_structure.hip, nra_structure_host.cpp): the wraparound edit-distance alignment of a read's tract
 // against its motif repeated without end, one lane per read.  A launch takes reads of one phase
 // capacity P (motif length p <= P), sorted by tract length, descending, 64 to a wave.
@@ -639,6 +652,14 @@ int nra_launch_sketch_pairs(hipStream_t st, int64_t tile0, int64_t n_tiles, int3
                             const int32_t* order, const int32_t* grp_end, const int64_t* sk_off, const uint32_t* sketch,
                             const int32_t* sk_len, int min_shared, NraSketchPair* pairs, unsigned long long cap,
                             unsigned long long* count);
+
+// placement (nra_place.hip): one workgroup per tile of NRA_PLACE_TILE windows of the n_win windows whose bytes start at
+// `seqs` (16-byte aligned, padded by 64 bytes); the window at byte w has contig position pos0 + w.  A window whose
+// canonical k-mer is a key adds 1 to occ[slot] and appends a record, unless it read occ[slot] > ceiling.  `records`
+// holds n_win records: it cannot overflow.  *count ends as the number of records, *n_valid grows by the valid windows
+int nra_launch_place_hits(hipStream_t st, int64_t n_win, const uint8_t* seqs, int k, const uint64_t* table,
+                          int log2_slots, uint32_t* occ, uint32_t ceiling, int32_t contig, int64_t pos0,
+                          NraPlaceRecord* records, unsigned long long* count, unsigned long long* n_valid);
 
 // repeat structure (nra_structure.hip): one lane per read, forward DP then traceback.  P in {1..6, 8, 16, 32, 64};
 // res[2 i] = edits, res[2 i + 1] = start phase of read i

@@ -182,11 +182,19 @@ def fetch_reads(path, indices, chunk_bases=1 << 28):
 
 def discover_file(reads_path, out_prefix, repeat_region_bed=None, k=11, max_gap=100, min_span=200, no_details=False,
                   device=0, chunk_bases=1 << 28, engine=None, stream=None, group_loci=False, flank_len=500, sketch_k=13,
-                  min_shared=None, min_locus_reads=3, sketch_engine=None):
+                  min_shared=None, min_locus_reads=3, sketch_engine=None, place_ref=None, place_options=None,
+                  place_engine=None, place_aligner=None):
     """scan_reads of the file -> `<out_prefix>.discovered_runs.tsv` (not with no_details) and
     `<out_prefix>.NanoRepeat_discovered.tsv`, and one NOTICE counting the classes with runs and no BED region.  Returns
     the summary rows (class_rows).  group_loci=True (loci.py) also groups the runs into loci by
-    their flanks and writes the four locus files; the two files above are what they are without it."""
+    their flanks and writes the four locus files; the two files above are what they are without it.  place_ref (a
+    FASTA file; place.py) beside it places the loci on that reference and writes the two placement
+    files; place_options are place.check_options' keywords."""
+    if place_ref is not None:
+        from . import place as nr_place
+        if not group_loci:
+            raise ValueError("placing loci on a reference needs group_loci=True")
+        nr_place.check_options(**(place_options or {}))
     if group_loci:
         from . import loci as nr_loci
         min_shared = nr_loci.check_options(flank_len, sketch_k, min_shared, min_locus_reads)
@@ -202,6 +210,10 @@ def discover_file(reads_path, out_prefix, repeat_region_bed=None, k=11, max_gap=
         print(f"NOTICE: {new} repeat class(es) have runs of at least {min_span} bases in the reads and no region in "
               f"the BED file", file=stream or sys.stderr)
     if group_loci:
-        nr_loci.loci_files(reads_path, out_prefix, rows, catalogue, sketch_k, min_shared, min_locus_reads, no_details,
-                           device, chunk_bases, sketch_engine, stream)
+        table, grouped = nr_loci.loci_files(reads_path, out_prefix, rows, catalogue, sketch_k, min_shared,
+                                            min_locus_reads, no_details, device, chunk_bases, sketch_engine, stream)
+        if place_ref is not None:
+            nr_place.place_files(reads_path, out_prefix, rows, grouped, table, place_ref, repeat_region_bed,
+                                 device=device, engine=place_engine, aligner=place_aligner, stream=stream,
+                                 reads_chunk_bases=chunk_bases, **(place_options or {}))
     return classes

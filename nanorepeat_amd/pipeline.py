@@ -515,7 +515,9 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
                         flank_min_sites=2, censored_fit=False, censored_error_rate=None, censored_max_alleles=6,
                         censored_bootstrap=0, methylation=False, meth_flank=2000, meth_bin=200, meth_hi=192,
                         meth_lo=63, meth_mod_code="m", discover_repeats=False, group_loci=False, locus_flank_len=500,
-                        sketch_k=13, min_shared=None, min_locus_reads=3, **engines):
+                        sketch_k=13, min_shared=None, min_locus_reads=3, place_loci=False, place_k=15, place_bin=64,
+                        place_min_votes=None, place_max_occ=16, place_max_target_occ=64, place_flank_len=1000,
+                        max_ref_span=50000, **engines):
     """The FASTQ / FASTA command (nanoRepeat.py:109, `-t fastq|fasta`) from files to files, without a genome mapper:
     the reads each region sees are chosen by the anchor k-mer screen (screen.reads_by_region) instead of a
     genome-wide mapping and a BAM window, then the BAM command's steps run unchanged.  Every region's reference
@@ -542,11 +544,23 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
     their flanks (locus_flank_len bases a side -- discover_repeats()' flank_len, which is the flank haplotypes' keyword
     here --, sketch_k, min_shared: None is the measured default) and a pseudo-reference with a BED file for the core
     loci with at least min_locus_reads spanned runs; without discover_repeats=True it is a ValueError.
+    place_loci=True beside group_loci=True adds the two placement files (place.py): every locus's
+    representative placed on ref_fasta by the place_flank_len bases on either side of its run (place_k, place_bin,
+    place_min_votes: None is the measured default, place_max_occ, place_max_target_occ, max_ref_span), and a BED file of
+    the placed loci on ref_fasta; without group_loci=True it is a ValueError.
     `engines` may carry aligner / scorer / screener / structure_engine / motif_engine / extension_engine /
     mixture_engine / consensus_engine / split_engine / segment_engine / path_aligner / period_engine /
-    bootstrap_engine / flank_engine / censored_engine / methylation_engine / scan_engine / sketch_engine stand-ins.
-    Returns the regions."""
+    bootstrap_engine / flank_engine / censored_engine / methylation_engine / scan_engine / sketch_engine /
+    place_engine stand-ins.  Returns the regions."""
     from . import screen as nr_screen, mixture as nr_mixture
+    place_options = None
+    if place_loci:
+        from . import place as nr_place
+        if not group_loci:
+            raise ValueError("place_loci=True needs group_loci=True")
+        place_options = _place_options(place_k, place_bin, place_min_votes, place_max_occ, place_max_target_occ,
+                                       place_flank_len, max_ref_span)
+        nr_place.check_options(**place_options)
     if group_loci:
         from . import loci as nr_loci
         if not discover_repeats:
@@ -607,13 +621,24 @@ def quantify_from_reads(in_reads, ref_fasta, repeat_region_bed, out_prefix, data
         nr_discover.discover_file(in_reads, out_prefix, repeat_region_bed, no_details=no_details, device=device,
                                   chunk_bases=chunk_bases, engine=engines.get("scan_engine"), group_loci=group_loci,
                                   flank_len=locus_flank_len, sketch_k=sketch_k, min_shared=min_shared,
-                                  min_locus_reads=min_locus_reads, sketch_engine=engines.get("sketch_engine"))
+                                  min_locus_reads=min_locus_reads, sketch_engine=engines.get("sketch_engine"),
+                                  place_ref=ref_fasta if place_loci else None, place_options=place_options,
+                                  place_engine=engines.get("place_engine"), place_aligner=engines.get("aligner"))
     return regions
+
+
+def _place_options(place_k, place_bin, place_min_votes, place_max_occ, place_max_target_occ, place_flank_len,
+                   max_ref_span):
+    """The placement switches under place.check_options' names."""
+    return dict(k=place_k, bin=place_bin, min_votes=place_min_votes, max_occ=place_max_occ,
+                max_target_occ=place_max_target_occ, flank_len=place_flank_len, max_ref_span=max_ref_span)
 
 
 def discover_repeats(reads_path, out_prefix, repeat_region_bed=None, k=11, max_gap=100, min_span=200, no_details=False,
                      device=0, engine=None, group_loci=False, flank_len=500, sketch_k=13, min_shared=None,
-                     min_locus_reads=3, sketch_engine=None):
+                     min_locus_reads=3, sketch_engine=None, place_ref=None, place_k=15, place_bin=64,
+                     place_min_votes=None, place_max_occ=16, place_max_target_occ=64, place_flank_len=1000,
+                     max_ref_span=50000, place_engine=None, place_aligner=None):
     """The discovery command from files to files (no counterpart in the reference): every read of a FASTQ / FASTA / BAM
     file through the repeat scan (discover.py), with no region, anchor or motif given ->
     `<out_prefix>.discovered_runs.tsv` (one row per tandem run of at least min_span bases; not with no_details) and
@@ -623,12 +648,24 @@ def discover_repeats(reads_path, out_prefix, repeat_region_bed=None, k=11, max_g
     sides match at min_shared shared ones: None is the measured default) and adds `<out_prefix>.discovered_loci.tsv`,
     `.discovered_locus_runs.tsv` (not with no_details) and `.discovered_loci.fa` / `.bed`, a pseudo-reference of the
     core loci with at least min_locus_reads spanned runs that quantify_from_reads takes as its reference and BED file;
-    `sketch_engine` stands in for _capi.sketch_pairs.  A bad value is a ValueError.  Returns the class rows."""
+    `sketch_engine` stands in for _capi.sketch_pairs.  place_ref="ref.fa" beside group_loci=True (place.py; DESIGN.md
+    section 31) places every locus's representative on that reference: the place_flank_len bases on either side of its
+    run are looked for in the reference, streamed contig by contig (canonical place_k-mers; diagonal bins of place_bin
+    bases; a side is placed at place_min_votes votes, None: the measured default, that beat the runner-up 1.5-fold;
+    place_max_occ and place_max_target_occ mask the k-mers repeated in the sides and in the reference), and a locus whose
+    two sides land on one contig and strand at most max_ref_span bases apart is placed.  It adds
+    `<out_prefix>.discovered_loci_placed.tsv` and `.discovered_loci.ref.bed`, a BED file of the placed loci on ref.fa
+    that quantify_from_bam and quantify_from_reads take; place_engine stands in for _capi's place_* functions and
+    place_aligner for _capi.align_pairs.  A bad value, or place_ref without group_loci, is a ValueError.  Returns the
+    class rows."""
     from . import discover as nr_discover
+    place_options = None if place_ref is None else _place_options(place_k, place_bin, place_min_votes, place_max_occ,
+                                                                  place_max_target_occ, place_flank_len, max_ref_span)
     return nr_discover.discover_file(reads_path, out_prefix, repeat_region_bed, k, max_gap, min_span, no_details, device,
                                      engine=engine, group_loci=group_loci, flank_len=flank_len, sketch_k=sketch_k,
                                      min_shared=min_shared, min_locus_reads=min_locus_reads,
-                                     sketch_engine=sketch_engine)
+                                     sketch_engine=sketch_engine, place_ref=place_ref, place_options=place_options,
+                                     place_engine=place_engine, place_aligner=place_aligner)
 
 
 def _fastq_mod_tags(in_reads):
